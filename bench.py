@@ -6,7 +6,14 @@ DEEP composition + FRI + proof-of-work + openings, default ProofOptions) over on
 resident in HBM (`value`); a second timed region starts from the trace in pinned host memory, the upload overlapped with the
 extension (`prover_ms_incl_upload`, the PCIe-inclusive figure).  Prints ONE JSON line on rank 0.
 
-    python bench.py --gpus 1 --steps 20 --warmup 5
+A plain run sets up, warms up, times the steps and prints the line (`value`, `ms_per_step`, phase and step times).  Everything
+else -- the upload leg, the kernel table and rooflines, the calibration kernels and box fingerprint, the oracle's verification of
+the timed proof and the CPU baseline -- runs only with --full.  --dump-outputs DIR writes what the last timed step returned (the
+proof, or the trace root for --workload commit) as DIR/<name>.npy, one float64 per byte.  A plain run times its steps without
+events; --full brackets the heavy kernels with events inside the timed region, as every line before the option existed did
+(BENCH_r*.json, profiles/): that costs about 0.2 % of a step, so a plain ms_per_step reads that much lower than those lines.
+
+    python bench.py --gpus 1 --steps 20 --warmup 5 [--full] [--dump-outputs DIR]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P bench.py --gpus N ...
 """
 import argparse
@@ -340,6 +347,15 @@ def splitmix_columns(log_n, W):
     return cols
 
 
+def dump_outputs(directory, outputs):
+    """--dump-outputs: what the timed path returned in its last step, one DIR/<name>.npy per output, float64 with one element per byte
+    (exact; a proof is at most 4 MiB -- the binding's buffer -- so at most 32 MiB of float64).  The inputs depend on the arguments alone
+    (Fibonacci trace of the library's VM, splitmix64 columns for config 2), so two builds can be compared output for output."""
+    os.makedirs(directory, exist_ok=True)
+    for name, raw in outputs.items():
+        np.save(os.path.join(directory, name + ".npy"), np.frombuffer(raw, dtype=np.uint8).astype(np.float64))
+
+
 def cpu_baseline_commit(cols, blowup):
     """config 2's CPU leg: the oracle's TraceTable::extend + build_merkle_tree (prover.rs:22-35) on the same columns"""
     import oracle as O
@@ -440,6 +456,9 @@ def main():
     ap.add_argument("--no-upload-leg", action="store_true", help="skip the second timed region (trace starting in pinned host memory)")
     ap.add_argument("--force-sharded", action="store_true", help="run the sharded (multi-GPU) code path even with one rank")
     ap.add_argument("--allow-lib-override", action="store_true", help="measure whatever library DISTAFF_HIP_LIB names instead of refusing anything but distaff_amd/libdistaff_hip.so")
+    ap.add_argument("--full", action="store_true",
+                    help="also the upload leg, kernel table, rooflines, calibration kernels, box fingerprint, oracle verification and CPU baseline (off: the headline figure only)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="write what the last timed step returned as DIR/<name>.npy (float64, one element per byte)")
     args = ap.parse_args()
     if args.log_n is None:
         args.log_n = int(os.environ.get("BENCH_LOG_N", "16" if args.workload == "commit" else "20"))
@@ -474,6 +493,8 @@ def run(args):
     world = int(os.environ.get("WORLD_SIZE", "1"))
     if world != args.gpus:
         raise SystemExit("--gpus %d does not match WORLD_SIZE %d" % (args.gpus, world))
+    if args.steps < 1 or args.warmup < 0:
+        raise SystemExit("--steps must be at least 1 and --warmup at least 0")
     lib_ident = library_identity(D, args.allow_lib_override)
     if not torch.cuda.is_available():
         raise SystemExit("bench.py needs a GPU: the HIP prover has no CPU fallback")
@@ -631,10 +652,12 @@ def run(args):
         proof = prove()
         progress()
     # timed region: HIP events around the heavy kernels only (NTT passes, constraint kernel, leaf hashing: the dominant kernel is one
-    # of them); bracketing all ~300 launches of a proof costs ~5 % and is done on one extra, untimed step for the kernel table
+    # of them); bracketing all ~300 launches of a proof costs ~5 % and is done on one extra, untimed step for the kernel table.  Both
+    # only with --full: a plain run times the steps without events
     progress("timed region")
-    ctx.set_profiling(2)
-    ctx.kernel_stats(reset=True)
+    if args.full:
+        ctx.set_profiling(2)
+        ctx.kernel_stats(reset=True)
     barrier()
     t0 = time.perf_counter()
     phase_sum = [0.0] * 9
@@ -660,17 +683,21 @@ def run(args):
         t = torch.tensor([elapsed], dtype=torch.float64, device="cpu" if host_group else "cuda")
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         elapsed = float(t.item())
-    progress("kernel table")
-    stats = ctx.kernel_stats(reset=True)
-    ctx.set_profiling(1)
-    prove()                                                        # untimed: every launch bracketed, for the "kernels" table
-    all_stats = ctx.kernel_stats(reset=True)
-    ctx.set_profiling(0)
+    if args.dump_outputs and rank == 0:
+        progress("dump outputs")
+        dump_outputs(args.dump_outputs, {"trace_root" if args.workload == "commit" else "proof": proof})
+    if args.full:
+        progress("kernel table")
+        stats = ctx.kernel_stats(reset=True)
+        ctx.set_profiling(1)
+        prove()                                                    # untimed: every launch bracketed, for the "kernels" table
+        all_stats = ctx.kernel_stats(reset=True)
+        ctx.set_profiling(0)
 
     # second timed region (single context only): the trace starts in page-locked HOST memory, as stark::prove receives it (prover.rs:17);
     # the upload is asynchronous DMA and the registers are extended group by group as they arrive
     incl_upload_ms = None
-    if transport == "none" and not args.no_upload_leg:
+    if args.full and transport == "none" and not args.no_upload_leg:
         progress("upload leg")
         table, handle = ctx.pinned_trace(cols)
         for _ in range(max(1, args.warmup)):
@@ -696,19 +723,12 @@ def run(args):
     ms_per_step = elapsed / args.steps * 1e3
     cells = n * W_FIB
     value = cells / (elapsed / args.steps)                      # one proof per step regardless of the number of GPUs
-    # kernels by device time, measured with HIP events on the launch stream inside the timed region.  `roofline` is the kernel with the
-    # largest total time IN THIS RUN; `roofline_transform` is always the first pass of the transforms (the kernel profiles/README.md
-    # describes), so that the two can be told apart when another kernel is dominant on some box; `rooflines` lists the top five.
-    PMC_WORKLOAD["tag"] = pmc_workload_tag(args.workload, log_n, blowup, args.queries, world)      # which committed counter passes (if any) were taken on this workload
-    default_workload = PMC_WORKLOAD["tag"] is not None
-    rooflines = kernel_rooflines(stats, args.steps, default_workload)
-    note = ("the path is 128-bit modular integer arithmetic on the VALU (valu_issue_frac, alu_roofline, DESIGN.md section 3), not HBM-bound; `frac` is the per-KERNEL figure: "
-            "its algorithmic bytes include the staging array the two-pass transform writes in pass A and re-reads in pass B, which SURVEY section 8(d) does not count -- "
-            "the phase-level fraction with section 8(d)'s bytes counted once is phase_hbm.lde (and phase_hbm.proof for the whole proof)")
-    roofline = dict(rooflines[0], note=note) if rooflines else None
-    transform = [r for r in kernel_rooflines(stats, args.steps, default_workload, top=len(stats)) if r["kernel"].startswith("ntt_pass_a")]
-    roofline_transform = dict(transform[0], note=note) if transform else None
-    dom = (roofline["kernel"], stats[roofline["kernel"]]) if roofline else (None, None)
+    if args.workload == "commit":
+        workload = ("BASELINE config 2: LDE (iNTT + coset NTTs) + BLAKE3 row hashing + Merkle tree of %d uniform random columns (splitmix64, SURVEY.md 8(d)) of 2^%d steps, "
+                    "blowup %d: TraceTable::extend + build_merkle_tree (prover.rs:22-35) only" % (W_FIB, log_n, blowup))
+    else:
+        workload = ("Fibonacci program (src/examples/fibonacci.rs), 2^%d-step trace, W=20 registers, full stark::prove with %sProofOptions (blowup %d, %d queries, grinding 20, blake3)"
+                    % (log_n, "default " if (blowup, args.queries) == (32, 50) else "", blowup, args.queries))
     # phase-level HBM fractions: SURVEY section 8(d)'s bytes counted once per phase, against the phase's wall time
     phase_names = ["lde", "trace_merkle", "constraint_eval", "combine", "constraint_lde_merkle", "deep_composition", "fri", "pow_queries", "openings"]
     phase_hbm = None
@@ -724,6 +744,55 @@ def run(args):
         total_b = sum(pb.values())
         gbs = total_b / (ms_per_step * 1e-3) / 1e9
         phase_hbm["proof" if args.workload == "prove" else "commit"] = {"algorithmic_GiB": round(total_b / 2**30, 3), "GBps": round(gbs, 1), "frac": round(gbs / HBM_PEAK_GBS, 4)}
+    out = {
+        "metric": "trace_cells_per_sec", "value": value, "unit": "trace-cells/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
+        "ms_per_step": ms_per_step, "higher_is_better": True, "scaling": "weak" if world == 1 else "strong", "vs_baseline": None,
+        "dtype": "u128 (prime field 2^128-45*2^40+1, 4x u32 limbs)", "data": "synthetic",
+        "config": {"workload": workload,
+                   "trace_steps": n, "registers": W_FIB, "blowup": blowup, "queries": args.queries, "grinding": 20,
+                   "parallelism": "1 GPU" if (world == 1 and not args.force_sharded) else "one proof sharded over %d GPUs: interpolation by trace columns (coefficients all-gathered), everything on the LDE domain by cosets; "
+                                  "Merkle trees finished per k-range (all-to-all of boundary nodes, all-gather of subtree roots), all-gather of constraint evaluations and of the "
+                                  "first small FRI layer; %s" % (world, transport)},
+        "prover_ms": ms_per_step,
+        "phase_ms": None if transport.startswith("torch") else {k: round(v / args.steps, 3) for k, v in zip(phase_names, phase_sum) if args.workload == "prove" or k in ("lde", "trace_merkle")},
+        "proof_bytes": len(proof),
+        "library": lib_ident,
+        "shard_stage_ms_rank0": {k: round(v / args.steps, 3) for k, v in stage_sum.items()} or None,
+        # enqueue -> completion of rank 0's collectives per kind and proof, from events on the streams they were queued on (dst_shard_exchange_ms)
+        "exchange_ms_rank0": {k: round(v / args.steps, 3) for k, v in exchange_sum.items()} or None,
+        "step_ms": {"min": round(min(step_ms), 3), "median": round(float(np.median(step_ms)), 3), "max": round(max(step_ms), 3), "all": [round(x, 3) for x in step_ms]},
+        "phase_hbm": phase_hbm,
+    }
+    if world > 1 or args.force_sharded:
+        out["devices"] = {"visible": ndev, "ranks": world, "shared": shared_devices,
+                          "note": ("%d ranks share %d device(s): a FUNCTIONAL run of the N-process path on this box, not a scaling measurement" % (world, ndev)) if shared_devices else None}
+        out["comm"] = comm_info
+        if transport_note:
+            out["transport_note"] = transport_note
+    if args.workload == "commit":
+        out["proof_bytes"] = None
+        out["trace_root_hex"] = proof.hex()
+    if not args.full:
+        emit(json.dumps(out))
+        ctx.close()
+        if dist is not None:
+            dist.barrier()
+            dist.destroy_process_group()
+        return
+
+    # kernels by device time, measured with HIP events on the launch stream inside the timed region.  `roofline` is the kernel with the
+    # largest total time IN THIS RUN; `roofline_transform` is always the first pass of the transforms (the kernel profiles/README.md
+    # describes), so that the two can be told apart when another kernel is dominant on some box; `rooflines` lists the top five.
+    PMC_WORKLOAD["tag"] = pmc_workload_tag(args.workload, log_n, blowup, args.queries, world)      # which committed counter passes (if any) were taken on this workload
+    default_workload = PMC_WORKLOAD["tag"] is not None
+    rooflines = kernel_rooflines(stats, args.steps, default_workload)
+    note = ("the path is 128-bit modular integer arithmetic on the VALU (valu_issue_frac, alu_roofline, DESIGN.md section 3), not HBM-bound; `frac` is the per-KERNEL figure: "
+            "its algorithmic bytes include the staging array the two-pass transform writes in pass A and re-reads in pass B, which SURVEY section 8(d) does not count -- "
+            "the phase-level fraction with section 8(d)'s bytes counted once is phase_hbm.lde (and phase_hbm.proof for the whole proof)")
+    roofline = dict(rooflines[0], note=note) if rooflines else None
+    transform = [r for r in kernel_rooflines(stats, args.steps, default_workload, top=len(stats)) if r["kernel"].startswith("ntt_pass_a")]
+    roofline_transform = dict(transform[0], note=note) if transform else None
+    dom = (roofline["kernel"], stats[roofline["kernel"]]) if roofline else (None, None)
     # integer-multiplier roofline: the peak of v_mad_u64_u32 (the 32x32+64 multiply-add every field multiplication is made of) measured
     # on this device, against the multiply-adds the kernels execute: NTT launches count theirs (18 per table-pair multiplication), the
     # constraint kernels are priced with the static instruction counts of the current build (distaff_amd/_build_info.json)
@@ -774,12 +843,6 @@ def run(args):
     except Exception as e:                                           # noqa: BLE001
         mulmod_peak = 5.0e11
         calibration_note = calibration_note or "mulmod calibration failed (%s): the pool's usual figure" % e
-    if args.workload == "commit":
-        workload = ("BASELINE config 2: LDE (iNTT + coset NTTs) + BLAKE3 row hashing + Merkle tree of %d uniform random columns (splitmix64, SURVEY.md 8(d)) of 2^%d steps, "
-                    "blowup %d: TraceTable::extend + build_merkle_tree (prover.rs:22-35) only" % (W_FIB, log_n, blowup))
-    else:
-        workload = ("Fibonacci program (src/examples/fibonacci.rs), 2^%d-step trace, W=20 registers, full stark::prove with %sProofOptions (blowup %d, %d queries, grinding 20, blake3)"
-                    % (log_n, "default " if (blowup, args.queries) == (32, 50) else "", blowup, args.queries))
     box = box_fingerprint(cal, mad_peak, mulmod_peak)
     vi = alu.get("valu_issue")
     if isinstance(vi, dict) and vi.get("proof_frac") is not None and (vi.get("sclk_MHz_time_weighted") or box.get("sclk_under_load_MHz")):
@@ -793,46 +856,21 @@ def run(args):
         vi["kernel_frac_at_measured_clock"] = {k: (None if v is None else round(v * NOMINAL_SCLK_MHZ / (kc.get(k) or mean_clock), 4)) for k, v in vi["kernel_frac"].items()}
         vi["measured_clock_note"] = ("clock per kernel from the stamped counter summary where present (kernel_sclk_MHz), else %s MHz from this run's calibration kernel "
                                      "(field multiplications on every SIMD; box.sclk_under_load_MHz); nominal %.0f MHz" % (box.get("sclk_under_load_MHz"), NOMINAL_SCLK_MHZ))
-    out = {
-        "metric": "trace_cells_per_sec", "value": value, "unit": "trace-cells/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
-        "ms_per_step": ms_per_step, "higher_is_better": True, "scaling": "weak" if world == 1 else "strong", "vs_baseline": None,
-        "dtype": "u128 (prime field 2^128-45*2^40+1, 4x u32 limbs)", "data": "synthetic",
-        "config": {"workload": workload,
-                   "trace_steps": n, "registers": W_FIB, "blowup": blowup, "queries": args.queries, "grinding": 20,
-                   "parallelism": "1 GPU" if (world == 1 and not args.force_sharded) else "one proof sharded over %d GPUs: interpolation by trace columns (coefficients all-gathered), everything on the LDE domain by cosets; "
-                                  "Merkle trees finished per k-range (all-to-all of boundary nodes, all-gather of subtree roots), all-gather of constraint evaluations and of the "
-                                  "first small FRI layer; %s" % (world, transport)},
-        "prover_ms": ms_per_step,
-        "phase_ms": None if transport.startswith("torch") else {k: round(v / args.steps, 3) for k, v in zip(phase_names, phase_sum) if args.workload == "prove" or k in ("lde", "trace_merkle")},
-        "proof_bytes": len(proof),
-        "library": dict(lib_ident, calibration_note=calibration_note),
-        "shard_stage_ms_rank0": {k: round(v / args.steps, 3) for k, v in stage_sum.items()} or None,
-        # enqueue -> completion of rank 0's collectives per kind and proof, from events on the streams they were queued on (dst_shard_exchange_ms)
-        "exchange_ms_rank0": {k: round(v / args.steps, 3) for k, v in exchange_sum.items()} or None,
+    out["library"] = dict(lib_ident, calibration_note=calibration_note)
+    out.update({
         "roofline": roofline,
         "roofline_transform": roofline_transform,
         "rooflines": rooflines,
-        "step_ms": {"min": round(min(step_ms), 3), "median": round(float(np.median(step_ms)), 3), "max": round(max(step_ms), 3), "all": [round(x, 3) for x in step_ms]},
         "box": box,
         "alu_roofline": dict(alu, mulmod_peak_measured=mulmod_peak, mulmod_kernel="mulmod_bench_kernel: general fe_mul, 4 dependent chains per lane (21 mads + 50 other VALU instructions each)"),
-        "phase_hbm": phase_hbm,
         "prover_ms_incl_upload": incl_upload_ms,
         "upload_note": None if incl_upload_ms is None else "trace (%d MiB) in pinned host memory at the start of every step; asynchronous upload in groups of 4 registers, each group interpolated and extended as it lands" % (n * W_FIB * 16 >> 20),
         "kernels": {k: {"launches": v["launches"], "ms_per_step": round(v["ms"], 3), "GBps": round(v["bytes"] / max(v["ms"], 1e-9) / 1e6, 1)}
                     for k, v in sorted(all_stats.items(), key=lambda kv: -kv[1]["ms"])},
         "kernels_note": "one extra untimed proof with every launch bracketed by events; the roofline kernel is timed inside the timed region",
-    }
-    if world > 1 or args.force_sharded:
-        out["devices"] = {"visible": ndev, "ranks": world, "shared": shared_devices,
-                          "note": ("%d ranks share %d device(s): a FUNCTIONAL run of the N-process path on this box, not a scaling measurement" % (world, ndev)) if shared_devices else None}
-        out["comm"] = comm_info
-        if transport_note:
-            out["transport_note"] = transport_note
+    })
     progress("verification")
-    if args.workload == "commit":
-        out["proof_bytes"] = None
-        out["trace_root_hex"] = proof.hex()
-    elif not args.no_verify:
+    if args.workload != "commit" and not args.no_verify:
         # the checker, outside every timed region: the oracle's restatement of the reference verifier must accept the timed proof
         import oracle as O
         ok, err = O.verify(proof, program_hash, [1, 0], [result])

@@ -47,11 +47,13 @@ SELECTION = [
     "test_host_side_abort_from_another_thread",
     "test_sharded_phase_and_exchange_times",
     "test_prove_sharded_in_separate_processes_sharing_the_gpu[2-12-one]",
+    "test_prove_sharded_in_separate_processes_sharing_the_gpu[8-12-one]",
     "test_prove_sharded_in_separate_processes_sharing_the_gpu[8-12-overlap]",
     "test_bench_with_n_processes_on_one_device[2]",
     "test_bench_with_n_processes_on_one_device[8]",
     "test_bench_prints_an_error_line_instead_of_hanging",
     "test_bench_config2_line",
+    "test_bench_plain_line_and_dumped_outputs",
     "test_sampled_oracle_parity_small[7-5]",
     "test_sampled_oracle_parity_small[10-4]",
     "test_deep_stacks_and_nested_blocks[]",
@@ -174,7 +176,7 @@ def test_bench_control_flow_on_cpu_stand_ins(emulated_library, ranks, orch):
     env = dict(os.environ, DISTAFF_HIP_LIB=emulated_library, DISTAFF_HIP_RUNTIME="none", DISTAFF_EMU_THREADS="2", DISTAFF_SHARD_ORCH=orch,
                DISTAFF_SHARD_HANDOFF="device")       # CPU tensors and the emulated build's host pointers: the tensor hand-off bench.py uses with device tensors on GPUs
     harness = os.path.join(EMU_DIR, "bench_harness.py")
-    args = ["--gpus", str(ranks), "--steps", "1", "--warmup", "1", "--log-n", "8", "--cpu-log-n", "7"]
+    args = ["--gpus", str(ranks), "--steps", "1", "--warmup", "1", "--log-n", "8", "--cpu-log-n", "7", "--full"]
     if ranks == 1:
         cmd = [sys.executable, harness] + args
     else:

@@ -1631,6 +1631,23 @@ def test_sharded_prover_two_processes_over_gloo(tmp_path):
         assert (tmp_path / ("proof_%d.bin" % r)).read_bytes() == expected
 
 
+# Processes that may have the GPU open at the same time during a test run, the test runner included: DISTAFF_TEST_GPU_PROCESSES,
+# 6 by default.  The tests that start rank processes on the GPU check, before they start anything, that their ranks and the runner fit.
+GPU_PROCESSES_DEFAULT = 6
+
+
+def _require_gpu_processes(ranks):
+    """Skips the test when `ranks` processes on the GPU and this test runner are more than the run allows.  The CPU emulation
+    (DISTAFF_HIP_RUNTIME=none, tests/test_emulated_kernels.py) opens no device and has no such limit."""
+    import os
+    if os.environ.get("DISTAFF_HIP_RUNTIME") == "none":
+        return
+    allowed = int(os.environ.get("DISTAFF_TEST_GPU_PROCESSES", str(GPU_PROCESSES_DEFAULT)))
+    if ranks + 1 > allowed:
+        pytest.skip("needs %d processes with the GPU open at once (%d ranks and the test runner), this run allows %d (DISTAFF_TEST_GPU_PROCESSES)"
+                    % (ranks + 1, ranks, allowed))
+
+
 _CALLBACK_WORKER = r"""
 import os, sys
 sys.path.insert(0, %r)
@@ -1681,13 +1698,15 @@ def test_prove_sharded_in_separate_processes_sharing_the_gpu(tmp_path, world, lo
     (dst_comm_init_callbacks + dst_comm_copy).  RCCL refuses several ranks on one device, so this is the closest a one-GPU box gets to
     the driver's N-process run; every rank must write the single-context proof, twice.  The ranks also compare the ORDER in which they issued
     the collectives (dst_comm_trace): kind, size and stream of every one -- with `streams` = overlap in the two-stream choreography the
-    RCCL transport uses (coefficient all-gathers and the exchange of the constraint evaluations on the collective stream)."""
+    RCCL transport uses (coefficient all-gathers and the exchange of the constraint evaluations on the collective stream).  Skips when the
+    run allows fewer processes on the GPU at once than the ranks and the runner (_require_gpu_processes)."""
     import json
     import os
     import socket
     import subprocess
     import sys
     import distaff_amd as D
+    _require_gpu_processes(world)
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     sock = socket.socket(); sock.bind(("127.0.0.1", 0)); port = sock.getsockname()[1]; sock.close()
     script = tmp_path / "worker.py"
@@ -1717,18 +1736,20 @@ def test_prove_sharded_in_separate_processes_sharing_the_gpu(tmp_path, world, lo
 def test_bench_with_n_processes_on_one_device(ranks):
     """bench.py launched exactly as the driver launches it for N > 1 (`python -m torch.distributed.run ...`) on a box with ONE GPU: the
     ranks share the device, the collectives of dst_prove_sharded travel through the callback transport over gloo, and rank 0 prints one
-    well-formed line that says so (a functional run of the N-process path, not a scaling measurement)."""
+    well-formed line that says so (a functional run of the N-process path, not a scaling measurement).  Skips when the run allows fewer
+    processes on the GPU at once than the ranks and the runner (_require_gpu_processes)."""
     import json
     import os
     import socket
     import subprocess
     import sys
+    _require_gpu_processes(ranks)
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     sock = socket.socket(); sock.bind(("127.0.0.1", 0)); port = sock.getsockname()[1]; sock.close()
     harness = os.environ.get("DISTAFF_BENCH_ENTRY", os.path.join(root, "bench.py"))      # the CPU run of this test goes through tests/emu/bench_harness.py
     env = dict(os.environ, BENCH_LOG_N="12", BENCH_CPU_LOG_N="8")
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", str(ranks), "--master-addr", "127.0.0.1",
-           "--master-port", str(port), harness, "--gpus", str(ranks), "--steps", "2", "--warmup", "1"]
+           "--master-port", str(port), harness, "--gpus", str(ranks), "--steps", "2", "--warmup", "1", "--full"]
     r = subprocess.run(cmd, cwd=root, env=env, stdout=subprocess.PIPE, stderr=subprocess.PIPE, timeout=900)
     assert r.returncode == 0, r.stderr.decode()[-3000:]
     lines = [ln for ln in r.stdout.decode().splitlines() if ln.startswith("{")]
@@ -1756,7 +1777,7 @@ def test_bench_falls_back_to_the_callback_transport_over_nccl():
     import sys
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     env = dict(os.environ, BENCH_LOG_N="12", BENCH_SIMULATE_RCCL_FAILURE="0")
-    r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "1", "--force-sharded", "--steps", "2", "--warmup", "1", "--no-cpu-baseline"], cwd=root, env=env,
+    r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "1", "--force-sharded", "--steps", "2", "--warmup", "1", "--no-cpu-baseline", "--full"], cwd=root, env=env,
                        stdout=subprocess.PIPE, stderr=subprocess.PIPE, timeout=600)
     assert r.returncode == 0, r.stderr.decode()[-3000:]
     d = json.loads([ln for ln in r.stdout.decode().splitlines() if ln.startswith("{")][0])
@@ -1795,7 +1816,7 @@ def test_bench_config2_line(tmp_path):
     import sys
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     entry = os.environ.get("DISTAFF_BENCH_ENTRY", os.path.join(root, "bench.py"))
-    r = subprocess.run([sys.executable, entry, "--workload", "commit", "--log-n", "10", "--steps", "2", "--warmup", "1"], cwd=root, stdout=subprocess.PIPE, stderr=subprocess.PIPE, timeout=600)
+    r = subprocess.run([sys.executable, entry, "--workload", "commit", "--log-n", "10", "--steps", "2", "--warmup", "1", "--full"], cwd=root, stdout=subprocess.PIPE, stderr=subprocess.PIPE, timeout=600)
     assert r.returncode == 0, r.stderr.decode()[-3000:]
     d = json.loads([ln for ln in r.stdout.decode().splitlines() if ln.startswith("{")][0])
     assert "config 2" in d["config"]["workload"] and set(d["phase_ms"]) == {"lde", "trace_merkle"} and d["cpu_baseline"]["root_hex"] == d["trace_root_hex"]
@@ -1819,7 +1840,7 @@ def test_bench_line_contract(tmp_path):
     import sys
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     env = dict(os.environ, BENCH_LOG_N="12", BENCH_CPU_LOG_N="8")
-    out = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "1", "--steps", "2", "--warmup", "1"], env=env, capture_output=True, text=True, timeout=600)
+    out = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "1", "--steps", "2", "--warmup", "1", "--full"], env=env, capture_output=True, text=True, timeout=600)
     assert out.returncode == 0, out.stderr[-2000:]
     lines = [ln for ln in out.stdout.splitlines() if ln.strip()]
     assert len(lines) == 1
@@ -1838,6 +1859,34 @@ def test_bench_line_contract(tmp_path):
     ref = c["same_size_reference"]
     assert ref["log_n"] == 20 and ref["value"] > 0 and ref["source"].startswith("profiles/") and ref["kind"] == "port"
     assert d["box"]["sclk_nominal_MHz"] == 2400.0 and 500.0 < d["box"]["sclk_under_load_MHz"] <= 2500.0, d["box"]
+
+
+def test_bench_plain_line_and_dumped_outputs(oracle, tmp_path):
+    """bench.py without --full: ONE line with the headline fields and nothing of what --full adds, exactly --steps timed steps, and
+    --dump-outputs writes the proof of the last timed step -- the oracle's proof of the same trace, byte for byte."""
+    import json
+    import os
+    import subprocess
+    import sys
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    entry = os.environ.get("DISTAFF_BENCH_ENTRY", os.path.join(root, "bench.py"))
+    env = dict(os.environ, BENCH_LOG_N="12")
+    out = subprocess.run([sys.executable, entry, "--gpus", "1", "--steps", "3", "--warmup", "1", "--dump-outputs", str(tmp_path / "out")], cwd=root, env=env,
+                         capture_output=True, text=True, timeout=600)
+    assert out.returncode == 0, out.stderr[-2000:]
+    lines = [ln for ln in out.stdout.splitlines() if ln.strip()]
+    assert len(lines) == 1, out.stdout[-2000:]
+    d = json.loads(lines[0])
+    for key in ("metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "higher_is_better", "dtype", "config", "phase_ms", "step_ms"):
+        assert key in d, key
+    assert d["metric"] == "trace_cells_per_sec" and d["unit"] == "trace-cells/s" and d["higher_is_better"] is True
+    assert d["steps"] == 3 and d["warmup"] == 1 and len(d["step_ms"]["all"]) == 3
+    assert abs(d["value"] - d["config"]["trace_steps"] * d["config"]["registers"] / (d["ms_per_step"] * 1e-3)) < 1e-6 * d["value"]
+    assert not set(d) & {"cpu_baseline", "roofline", "rooflines", "box", "alu_roofline", "kernels", "prover_ms_incl_upload", "proof_verified"}, sorted(d)
+    assert os.listdir(tmp_path / "out") == ["proof.npy"]
+    dumped = np.load(tmp_path / "out" / "proof.npy")
+    assert dumped.dtype == np.float64 and dumped.size == d["proof_bytes"]
+    assert dumped.astype(np.uint8).tobytes() == oracle.Prover.from_trace(oracle.fibonacci_trace(1 << 12), 1).prove()
 
 
 @pytest.mark.parametrize("steps,log_blowup", [(128, 7), (256, 8)])

@@ -2,7 +2,7 @@
 # On the GPU box: the short bench for the base library (tools/ab_base.sh) and for the working tree under each given environment setting.
 #   bash tools/ab_run.sh "" "DISTAFF_NTT_B8=1" ...
 run() {
-    env $1 python bench.py --steps 5 --warmup 2 --no-cpu-baseline --no-upload-leg --no-verify 2>&1 | grep "^{" | python -c "
+    env $1 python bench.py --steps 5 --warmup 2 --full --no-cpu-baseline --no-upload-leg --no-verify 2>&1 | grep "^{" | python -c "
 import json, sys
 b = json.loads(sys.stdin.read())
 k = b['kernels']

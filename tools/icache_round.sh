@@ -17,7 +17,7 @@ cd /tmp
 rocprofv3 --pmc $CTRS --kernel-trace --output-format csv -d $OUT/probe_pmc -o p -- $R/tools/icache_probe/_build/icache_probe > $OUT/probe_pmc.log 2>&1
 cd $R
 run() {
-    env $1 python bench.py --steps 5 --warmup 2 --no-cpu-baseline --no-upload-leg --no-verify 2>&1 | grep "^{" | python -c "
+    env $1 python bench.py --steps 5 --warmup 2 --full --no-cpu-baseline --no-upload-leg --no-verify 2>&1 | grep "^{" | python -c "
 import json, sys
 b = json.loads(sys.stdin.read())
 k = b['kernels']
@@ -33,6 +33,6 @@ done
 run "X_=1" "product again"
 } | tee $OUT/air_ab.txt
 cd /tmp
-rocprofv3 --pmc $CTRS --kernel-trace --output-format csv -d $OUT/bench_pmc -o p -- python $R/bench.py --steps 2 --warmup 1 --no-cpu-baseline --no-upload-leg --no-verify > $OUT/bench_pmc.log 2>&1
+rocprofv3 --pmc $CTRS --kernel-trace --output-format csv -d $OUT/bench_pmc -o p -- python $R/bench.py --steps 2 --warmup 1 --full --no-cpu-baseline --no-upload-leg --no-verify > $OUT/bench_pmc.log 2>&1
 cd $R
 python tools/icache_summary.py $OUT | tee $OUT/summary.txt

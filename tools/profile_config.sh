@@ -7,9 +7,9 @@ export TMPDIR=/tmp BENCH_TRACE_CACHE=${BENCH_TRACE_CACHE:-/tmp/dtc}
 R=$PWD
 OUT=$R/gpurun_out/prof_$TAG
 rm -rf $OUT; mkdir -p $OUT $R/gpurun_out/profiles_$TAG
-python $R/bench.py $ARGS 2> $OUT/bench.err | grep "^{" > $R/gpurun_out/profiles_$TAG/${TAG}_bench.json      # the line of its own, no profiler (CPU leg included)
+python $R/bench.py $ARGS --full 2> $OUT/bench.err | grep "^{" > "$(dirname "$OUT")/profiles_$TAG/${TAG}_bench.json"      # the line of its own, no profiler (CPU leg included)
 cd /tmp
-CMD="python $R/bench.py $ARGS --steps 3 --warmup 1 --no-cpu-baseline --no-upload-leg --no-verify"
+CMD="python $R/bench.py $ARGS --steps 3 --warmup 1 --full --no-cpu-baseline --no-upload-leg --no-verify"
 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/stats -o p -- $CMD > $OUT/stats.log 2>&1
 rocprofv3 --pmc FETCH_SIZE --kernel-trace --output-format csv -d $OUT/fetch -o p -- $CMD > $OUT/fetch.log 2>&1
 rocprofv3 --pmc WRITE_SIZE --kernel-trace --output-format csv -d $OUT/write -o p -- $CMD > $OUT/write.log 2>&1

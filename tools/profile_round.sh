@@ -7,7 +7,7 @@ R=$PWD
 OUT=$R/gpurun_out/prof_$TAG
 rm -rf $OUT; mkdir -p $OUT
 cd /tmp
-CMD="python $R/bench.py --steps $STEPS --warmup 1 --no-cpu-baseline --no-upload-leg"
+CMD="python $R/bench.py --steps $STEPS --warmup 1 --full --no-cpu-baseline --no-upload-leg"
 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/stats -o p -- $CMD > $OUT/stats.log 2>&1
 rocprofv3 --pmc FETCH_SIZE --kernel-trace --output-format csv -d $OUT/fetch -o p -- $CMD > $OUT/fetch.log 2>&1
 rocprofv3 --pmc WRITE_SIZE --kernel-trace --output-format csv -d $OUT/write -o p -- $CMD > $OUT/write.log 2>&1
@@ -32,5 +32,5 @@ json.dump({"tag": "$TAG", "csrc_sha16": bench.csrc_digest(), "git_head": info.ge
            "note": "git_head is the commit the shared library was built at (the GPU box has no .git); csrc_sha16 is the digest of distaff_amd/csrc at the time of the run"},
           open(os.path.join("$R", "gpurun_out", "profiles_$TAG", "${TAG}_meta.json"), "w"), indent=1)
 PY
-python bench.py 2>&1 | grep "^{" > $R/gpurun_out/profiles_$TAG/${TAG}_bench_default.json
+python bench.py --full 2>&1 | grep "^{" > "$(dirname "$OUT")/profiles_$TAG/${TAG}_bench_default.json"
 ls -la $R/gpurun_out/profiles_$TAG

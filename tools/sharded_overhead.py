@@ -11,7 +11,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
 def run(extra):
-    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "5", "--warmup", "2", "--no-cpu-baseline", "--no-upload-leg", "--no-verify"] + extra,
+    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "5", "--warmup", "2", "--full", "--no-cpu-baseline", "--no-upload-leg", "--no-verify"] + extra,
                          stdout=subprocess.PIPE, stderr=subprocess.DEVNULL).stdout.decode()
     return json.loads([l for l in out.splitlines() if l.startswith("{")][-1])
 

@@ -2,6 +2,7 @@
 // tests/, __graft_entry__.smoke() and bench.py's cpu_baseline leg (and by nothing else).
 // Field elements cross this boundary as 16-byte little-endian integers.
 #include "verifier.hpp"
+#include "check.hpp"
 #include <chrono>
 #include <cstdio>
 
@@ -452,6 +453,34 @@ int orc_fri_prove_verify(const u128* evaluations, size_t domain_size, size_t cla
         return r.ok ? 1 : 0;
     } catch (const std::exception& e) { return fail(e); }
 }
+
+// ---- whole-array checkers (check.hpp): -1 = right, else the first failing index (what failed in orc_last_error), -2 = bad arguments ----
+static long verdict(long r, const std::string& msg) { if (r >= 0) g_error = msg; return r; }
+long orc_chk_noncanonical(const u128* v, size_t n) { return chk_first_noncanonical(v, n); }
+long orc_chk_evals(const u128* a, size_t m, const u128* v, size_t N, const u128* r) { std::string s; return verdict(chk_evals_vs_coeffs(a, m, v, N, *r, s), s); }
+long orc_chk_merkle(const uint8_t* leaves, size_t nleaves, const uint8_t* nodes) { std::string s; return verdict(chk_merkle_nodes(leaves, nleaves, nodes, s), s); }
+long orc_chk_row_leaves(const u128* rows, size_t count, size_t W, const uint8_t* leaves) { std::string s; return verdict(chk_row_leaves(rows, count, W, leaves, s), s); }
+long orc_chk_fri_leaves(const u128* e, size_t M, const uint8_t* leaves) { std::string s; return verdict(chk_fri_leaves(e, M, leaves, s), s); }
+long orc_chk_fri_fold(const u128* e, size_t M, const u128* alpha, const u128* next) { std::string s; return verdict(chk_fri_fold(e, M, *alpha, next, s), s); }
+void orc_fri_fold(const u128* e, size_t M, const u128* alpha, u128* out) { fri_fold_rows(e, M, *alpha, 0, M / 4, out); }
+long orc_chk_composition(const u128* rows, size_t count, size_t start, size_t W, const u128* cevals, const u128* comp, size_t n, size_t N,
+                         const u128* draws516, const u128* z1, const u128* z2, const u128* c_z) {
+    std::string s;
+    return verdict(chk_composition(rows, count, start, W, cevals, comp, n, N, draws516, z1, z2, *c_z, s), s);
+}
+long orc_chk_constraints(size_t trace_length, size_t ctx, size_t lp, size_t st, const u128* coeffs344, const u128* prog_hash2, const u128* op_count,
+                         const u128* inputs, size_t nin, const u128* outputs, size_t nout, const uint64_t* steps, size_t count,
+                         const u128* cur_rows, const u128* nxt_rows, const u128* tvals, const u128* cvals) {
+    try {
+        ConstraintCoefficients cc;
+        cc.init(vec(coeffs344, coeffs344 + 2 * NUM_CONSTRAINTS), ctx, lp, st);
+        Evaluator ev(trace_length, MAX_CONSTRAINT_DEGREE, ctx, lp, st, trace_length * MAX_CONSTRAINT_DEGREE, cc,
+                     vec(prog_hash2, prog_hash2 + PROGRAM_DIGEST_SIZE), *op_count, vec(inputs, inputs + nin), vec(outputs, outputs + nout));
+        std::string s;
+        return verdict(chk_constraints(ev, trace_length, ctx, lp, st, steps, count, cur_rows, nxt_rows, tvals, cvals, s), s);
+    } catch (const std::exception& e) { g_error = e.what(); return -2; }
+}
+void orc_poly_eval_par(const u128* p, size_t n, const u128* x, u128* out) { *out = chk_poly_eval(p, n, *x); }
 
 int orc_verify(const uint8_t* proof, size_t len, const uint8_t* program_hash, const u128* inputs, size_t nin, const u128* outputs, size_t nout, char* err, size_t errcap) {
     try {

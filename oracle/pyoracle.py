@@ -38,7 +38,9 @@ def lib():
         L.orc_last_error.restype = ctypes.c_char_p
         for name in ("orc_vm_execute", "orc_vm_execute_inputs", "orc_vm_execute_ops", "orc_prover_new"):
             getattr(L, name).restype = ctypes.c_void_p
-        for name in ("orc_merkle_prove_batch", "orc_prover_get", "orc_program_debug", "orc_stack_run", "orc_program_traverse"):
+        for name in ("orc_merkle_prove_batch", "orc_prover_get", "orc_program_debug", "orc_stack_run", "orc_program_traverse", "orc_chk_noncanonical",
+                     "orc_chk_evals", "orc_chk_merkle", "orc_chk_row_leaves", "orc_chk_fri_leaves", "orc_chk_fri_fold", "orc_chk_composition",
+                     "orc_chk_constraints"):
             getattr(L, name).restype = ctypes.c_long
         L.orc_infer_degree.restype = ctypes.c_size_t
         L.orc_poly_div.restype = ctypes.c_size_t
@@ -529,3 +531,92 @@ def fri_prove_verify(evaluations, claimed_degree, drop_first_evaluation=False):
     if r < 0:
         raise RuntimeError(last_error())
     return r == 1, err.value.decode()
+
+
+# ---- whole-array checkers (oracle/check.hpp) ----------------------------------------------------------------------------------
+# Each verifies EVERY element of an array a prover produced (read back from the device) in O(size) host-thread work and returns
+# (-1, "") when it is right, else (first failing index, what failed).  Every checker also rejects a stored value >= p.
+def _raw(x):
+    return np.frombuffer(x, dtype=np.uint8) if isinstance(x, (bytes, bytearray)) else np.ascontiguousarray(x)
+
+
+def _verdict(k):
+    if k < -1:
+        raise RuntimeError(last_error())
+    return (-1, "") if k == -1 else (int(k), last_error())
+
+
+def check_noncanonical(values):
+    """index of the first stored value >= p, or -1"""
+    a = _c(values)
+    return int(lib().orc_chk_noncanonical(_p(a), ctypes.c_size_t(a.size // 2)))
+
+
+def check_evaluations(coeffs, evals, r):
+    """evals[pos] == sum_j coeffs[j] g^(j pos) on the len(evals)-point domain, every pos: the sum identity at the random point r,
+    then a bisection that names the first disagreeing evaluation"""
+    a, v = _c(coeffs), _c(evals)
+    return _verdict(lib().orc_chk_evals(_p(a), ctypes.c_size_t(a.size // 2), _p(v), ctypes.c_size_t(v.size // 2), _p(_el(r))))
+
+
+def check_merkle(leaves, nodes):
+    """every node of a tree (nodes[1:], 32 bytes each, as many as leaves) is the hash of its children; names the deepest wrong node"""
+    lv, nd = _raw(leaves), _raw(nodes)
+    assert lv.nbytes == nd.nbytes and lv.nbytes % 64 == 0
+    return _verdict(lib().orc_chk_merkle(_p(lv), ctypes.c_size_t(lv.nbytes // 32), _p(nd)))
+
+
+def check_row_leaves(rows, leaves):
+    """rows [count, W, 2]: leaf i == BLAKE3 of row i (trace_table.rs:174)"""
+    r, lv = _c(rows), _raw(leaves)
+    assert lv.nbytes == 32 * r.shape[0]
+    return _verdict(lib().orc_chk_row_leaves(_p(r), ctypes.c_size_t(r.shape[0]), ctypes.c_size_t(r.shape[1]), _p(lv)))
+
+
+def check_fri_leaves(evals, leaves):
+    """a FRI layer in natural order: leaf r == BLAKE3(e[r], e[r+R], e[r+2R], e[r+3R]) (fri/utils.rs:16)"""
+    e, lv = _c(evals), _raw(leaves)
+    assert lv.nbytes == 32 * (e.shape[0] // 4)
+    return _verdict(lib().orc_chk_fri_leaves(_p(e), ctypes.c_size_t(e.shape[0]), _p(lv)))
+
+
+def fri_fold(evals, alpha):
+    """the next FRI layer of a layer in natural order (the checker's 4-point inverse DFT form)"""
+    e = _c(evals); out = np.zeros((e.shape[0] // 4, 2), dtype=np.uint64)
+    lib().orc_fri_fold(_p(e), ctypes.c_size_t(e.shape[0]), _p(_el(alpha)), _p(out))
+    return out
+
+
+def check_fri_fold(evals, alpha, folded):
+    e, f = _c(evals), _c(folded)
+    assert f.shape[0] == e.shape[0] // 4
+    return _verdict(lib().orc_chk_fri_fold(_p(e), ctypes.c_size_t(e.shape[0]), _p(_el(alpha)), _p(f)))
+
+
+def check_composition(rows, start, cevals, comp, n, N, draws, z1, z2, c_z):
+    """DEEP composition at the positions [start, start + len(rows)) of the N-point domain, from the LDE rows [count, W, 2], the
+    constraint LDE and the 516 draws of prng_vector(constraint root) (draws[0] = z); z1, z2: the trace polynomials at z and z g"""
+    r, cv, cp, d, a, b = _c(rows), _c(cevals), _c(comp), _c(draws), _c(z1), _c(z2)
+    assert cv.shape[0] == cp.shape[0] == r.shape[0] and d.shape[0] == 516 and a.shape[0] == b.shape[0] == r.shape[1]
+    return _verdict(lib().orc_chk_composition(_p(r), ctypes.c_size_t(r.shape[0]), ctypes.c_size_t(start), ctypes.c_size_t(r.shape[1]), _p(cv), _p(cp),
+                                              ctypes.c_size_t(n), ctypes.c_size_t(N), _p(d), _p(a), _p(b), _p(_el(c_z))))
+
+
+def check_constraints(trace_length, ctx, lp, st, coeffs344, program_hash2, op_count, inputs, outputs, steps, cur_rows, nxt_rows, tvals, cvals):
+    """the reference evaluator at the listed steps of the 8n-point domain (cur / nxt: LDE rows at s B/8 and s B/8 + B) against the
+    transition combination `tvals` and, off the trace domain, the constraint LDE `cvals` at those positions; the index is into `steps`"""
+    s = np.ascontiguousarray(steps, dtype=np.uint64)
+    cur, nxt, tv, cv = _c(cur_rows), _c(nxt_rows), _c(tvals), _c(cvals)
+    assert cur.shape[0] == nxt.shape[0] == tv.shape[0] == cv.shape[0] == s.shape[0]
+    i = to_arr(list(inputs)) if len(inputs) else np.zeros((1, 2), dtype=np.uint64)
+    o = to_arr(list(outputs)) if len(outputs) else np.zeros((1, 2), dtype=np.uint64)
+    return _verdict(lib().orc_chk_constraints(ctypes.c_size_t(trace_length), ctypes.c_size_t(ctx), ctypes.c_size_t(lp), ctypes.c_size_t(st), _p(_c(coeffs344)),
+                                              _p(to_arr(list(program_hash2))), _p(_el(op_count)), _p(i), ctypes.c_size_t(len(inputs)), _p(o),
+                                              ctypes.c_size_t(len(outputs)), _p(s), ctypes.c_size_t(s.shape[0]), _p(cur), _p(nxt), _p(tv), _p(cv)))
+
+
+def poly_eval_par(p, x):
+    """poly_eval on host threads (Horner per chunk)"""
+    a = _c(p); out = np.zeros((1, 2), dtype=np.uint64)
+    lib().orc_poly_eval_par(_p(a), ctypes.c_size_t(a.shape[0]), _p(_el(x)), _p(out))
+    return to_ints(out)[0]

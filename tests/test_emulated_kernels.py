@@ -17,7 +17,9 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 EMU_DIR = os.path.join(ROOT, "tests", "emu")
 EMU_LIB = os.path.join(EMU_DIR, "_build", "libdistaff_emu.so")
 
-SELECTION = [
+WHOLE_DOMAIN = ["test_whole_domain_parity_small[7-5]", "test_whole_domain_parity_small[10-4]"]
+
+SELECTION = WHOLE_DOMAIN + [
     "test_fibonacci_all_phases[7]",
     "test_fibonacci_all_phases[10]",
     "test_boundary_constraints_by_evaluation[]",
@@ -105,6 +107,14 @@ def test_parity_selection_on_the_emulated_build(emulated_library):
     out = r.stdout.decode()
     assert r.returncode == 0, out[-4000:]
     assert "%d passed" % len(SELECTION) in out, out[-2000:]
+
+
+def test_whole_domain_parity_on_the_emulated_build(emulated_library):
+    """the whole-domain driver of the selection above on its own (the checkers' CPU tests are selected with it by `-k whole`)"""
+    r = _run(emulated_library, ["tests/test_gpu_parity.py::" + t for t in WHOLE_DOMAIN])
+    out = r.stdout.decode()
+    assert r.returncode == 0, out[-4000:]
+    assert "%d passed" % len(WHOLE_DOMAIN) in out, out[-2000:]
 
 
 def test_emulated_build_is_not_a_product_path():

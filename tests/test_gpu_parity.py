@@ -632,9 +632,20 @@ def test_sharded_prover_over_torch_distributed_world1(oracle, monkeypatch):
         dist.destroy_process_group()
 
 
+P_LO = 2**64 - 45 * 2**40 + 1                                            # low limb of p; its high limb is 2^64 - 1
+
+
 def _random_columns(W, n, seed):
+    """uniform over all of [0, p), with 0, 1, p - 1, p - 2 and 2^127 forced into rows 0, 1, n - 1 and next to tile boundaries"""
     rng = np.random.default_rng(seed)
-    cols = rng.integers(0, 2**63, size=(W, n, 2), dtype=np.uint64)      # high limb < 2^63: always below the modulus
+    cols = rng.integers(0, 2**64, size=(W, n, 2), dtype=np.uint64, endpoint=False)
+    over = (cols[..., 1] == np.uint64(2**64 - 1)) & (cols[..., 0] >= np.uint64(P_LO))
+    cols[..., 0][over] -= np.uint64(P_LO)                                    # the few values >= p: minus p
+    special = np.array([[0, 0], [1, 0], [P_LO - 1, 2**64 - 1], [P_LO - 2, 2**64 - 1], [0, 2**63]], dtype=np.uint64)
+    rows = {0, 1, n - 1} | {r for t in (64, 256, 1024, 2048, 4096) for r in (t - 1, t, t + 1) if t + 1 < n}
+    for k, r in enumerate(sorted(rows)):
+        for c in range(W):
+            cols[c, r] = special[(k + c) % len(special)]
     return cols
 
 
@@ -677,8 +688,17 @@ def test_lde_every_tile_length(oracle, monkeypatch, family, log_n, log_blowup):
     ctx = D.Context(log_n, W, 0, 0, log_blowup=log_blowup)
     ctx.upload(cols)
     ctx.commit_trace()
+    polys = ctx.read_elements("polys").reshape(W, n, 2)
+    # every element: interpolation and extension of every register (at 2^23 / 2^24: four of them, the first and the last among them)
+    # against the coefficients, through the sum identity of oracle/check.hpp at a random point
+    rng = np.random.default_rng(log_n)
+    for c in (range(W) if log_n <= 22 else (0, 5, 10, W - 1)):
+        res = O.check_evaluations(polys[c], cols[c], int.from_bytes(rng.bytes(16), "little") % O.P)
+        assert res[0] == -1, ("interpolation", c) + res
+        res = O.check_evaluations(polys[c], ctx.read_elements("lde", c), int.from_bytes(rng.bytes(16), "little") % O.P)
+        assert res[0] == -1, ("extension", c) + res
     c = 5
-    poly = ctx.read_elements("polys").reshape(W, n, 2)[c]
+    poly = polys[c]
     lde = ctx.read_elements("lde", c)
     ctx.close()
     assert lde.shape == (n * B, 2)
@@ -892,6 +912,161 @@ def test_config3_sampled_oracle_parity_at_full_size(oracle):
     _sampled_parity(oracle, D, 20, points=32, horner_rows=32)
 
 
+def _lde_rows(ctx, positions, W):
+    """LDE rows at natural positions, [count, W, 2], through dst_shard_read in pieces that fit its 8 MiB staging buffer"""
+    positions = np.asarray(positions, dtype=np.uint64)
+    piece = ((8 << 20) // (16 * W + 8) - 64) // 1024 * 1024
+    out = np.empty((len(positions), W, 2), dtype=np.uint64)
+    for i in range(0, len(positions), piece):
+        out[i:i + piece] = np.frombuffer(ctx.shard_read(10, 0, positions[i:i + piece]), dtype=np.uint64).reshape(-1, W, 2)
+    return out
+
+
+def _evaluator_steps(n, points, rng):
+    """`points` steps of the 8n-point domain: the first and last 4096, +-64 around every multiple of 2^16, random ones"""
+    D = 8 * n
+    s = [np.arange(min(4096, D)), np.arange(max(D - 4096, 0), D)]
+    s += [np.arange(max(m - 64, 0), min(m + 64, D)) for m in range(1 << 16, D, 1 << 16)]
+    s = np.unique(np.concatenate(s))
+    while len(s) < min(points, D):
+        s = np.unique(np.concatenate([s, rng.integers(0, D, size=points - len(s))]))
+    return s
+
+
+def _whole_domain_parity(O, D, log_n, log_blowup=5, num_queries=50, seed=1, trace=None, num_outputs=1, evaluator_points=None):
+    """EVERY element of every phase of a proof against the whole-array checkers of oracle/check.hpp (host threads, no GPU work in the
+    reference), with the library's own Fiat-Shamir draws as in _sampled_parity:
+      * interpolation and extension of every register, the constraint LDE and the composition LDE against their coefficients (sum identity
+        at a random point, then a bisection that names the first wrong element); the degree bounds of both coefficient vectors;
+      * every trace leaf (BLAKE3 of its LDE row) and every node of the trace and constraint trees;
+      * the reference evaluator at every step of the 8n-point domain (`evaluator_points`: that many steps instead) against the transition
+        combination and the constraint LDE;
+      * the DEEP values of every register (Horner), every element of the composition LDE rebuilt from its row and constraint value;
+      * every FRI layer: every leaf, every node, every folded entry, down to the remainder.
+    Host memory: one LDE column and one block of rows at a time besides the N-element constraint and composition LDEs."""
+    P = O.P
+    if trace is None:
+        cols, program_hash, result = _fib(log_n)
+        W, ctx_depth, loop_depth, stack_depth, inputs, outputs = 20, 1, 0, 4, [1, 0], [result]
+    else:
+        cols, log_n = trace.columns, trace.length.bit_length() - 1
+        W, ctx_depth, loop_depth, stack_depth = trace.width, trace.ctx_depth, trace.loop_depth, trace.stack_depth
+        inputs, outputs = trace.public_inputs, trace.outputs(num_outputs)
+    n, B = 1 << log_n, 1 << log_blowup
+    N = n * B
+    rng = np.random.default_rng(seed)
+    rand = lambda: int.from_bytes(rng.bytes(16), "little") % P                                                    # noqa: E731
+    ints = lambda a: [int(lo) | (int(hi) << 64) for lo, hi in np.asarray(a, dtype=np.uint64).reshape(-1, 2)]      # noqa: E731
+
+    def ok(res, *what):
+        assert res[0] == -1, what + res
+
+    ctx = D.Context(log_n, W, ctx_depth, loop_depth, log_blowup=log_blowup, num_queries=num_queries)
+    ctx.upload(cols)
+    root = ctx.commit_trace()
+    coeffs = D.prng_vector(root, 344)
+    croot = ctx.eval_constraints(inputs, outputs, coeffs)
+    draws = D.prng_vector(croot, 516)
+    z1, z2 = ctx.compose(draws)
+    z = ints(draws[:1])[0]
+    zg = z * O.root_of_unity(n) % P
+
+    # ---- steps 1-2 and the DEEP values: every register
+    polys = ctx.read_elements("polys").reshape(W, n, 2)
+    for c in range(W):
+        ok(O.check_evaluations(polys[c], cols[c], rand()), "interpolation", c)
+        ok(O.check_evaluations(polys[c], ctx.read_elements("lde", c), rand()), "extension", c)
+        assert O.poly_eval_par(polys[c], z) == ints(z1[c])[0] and O.poly_eval_par(polys[c], zg) == ints(z2[c])[0], ("DEEP value", c)
+    del polys
+
+    # ---- steps 3-5: constraint polynomial, its LDE and tree; step 6: composition polynomial and its LDE
+    cpoly = ctx.read_elements("cpoly")
+    assert not cpoly[7 * n + 1:].any(), "constraint polynomial above degree 7n"
+    cevals = ctx.read_elements("cevals")
+    ok(O.check_evaluations(cpoly, cevals, rand()), "constraint LDE")
+    c_z = O.poly_eval_par(cpoly, z)
+    del cpoly
+    cnodes = ctx.read("cnodes")
+    assert cnodes[32:64].tobytes() == croot
+    ok(O.check_merkle(cevals, cnodes), "constraint tree")
+    del cnodes
+    comp_poly = ctx.read_elements("comp_poly")
+    assert not comp_poly[7 * n:].any(), "composition polynomial above the composition degree 7n - 1"
+    comp = ctx.read_elements("comp_evals")
+    ok(O.check_evaluations(comp_poly, comp, rand()), "composition LDE")
+    del comp_poly
+
+    # ---- every LDE row: its trace leaf and the composition value at its position
+    leaves = ctx.read("trace_leaves")
+    for start in range(0, N, 1 << 18):
+        end = min(start + (1 << 18), N)
+        rows = _lde_rows(ctx, np.arange(start, end, dtype=np.uint64), W)
+        res = O.check_row_leaves(rows, leaves[32 * start:32 * end])
+        assert res[0] == -1, ("trace leaf", start + res[0], res[1])
+        res = O.check_composition(rows, start, cevals[start:end], comp[start:end], n, N, draws, z1, z2, c_z)
+        assert res[0] == -1, ("composition", start + res[0], res[1])
+    del rows
+    nodes = ctx.read("trace_nodes")
+    assert nodes[32:64].tobytes() == root
+    ok(O.check_merkle(leaves, nodes), "trace tree")
+    del leaves, nodes
+
+    # ---- the evaluator: transition combination and constraint LDE
+    steps = np.arange(8 * n, dtype=np.uint64) if evaluator_points is None else _evaluator_steps(n, evaluator_points, rng).astype(np.uint64)
+    op_count, ph = ints(cols[0, n - 1])[0], [ints(cols[1, n - 1])[0], ints(cols[2, n - 1])[0]]
+    for i in range(0, len(steps), 1 << 17):
+        s = steps[i:i + (1 << 17)]
+        pos = s * np.uint64(B // 8)
+        cur, nxt = _lde_rows(ctx, pos, W), _lde_rows(ctx, (pos + np.uint64(B)) % np.uint64(N), W)
+        tv = np.frombuffer(ctx.shard_read(11, 0, (s % np.uint64(8)) * np.uint64(n) + s // np.uint64(8)), dtype=np.uint64).reshape(-1, 2)
+        res = O.check_constraints(n, ctx_depth, loop_depth, stack_depth, coeffs, ph, op_count, inputs, outputs, s, cur, nxt, tv, cevals[pos.astype(np.int64)])
+        assert res[0] == -1, ("constraints", int(s[res[0]]), res[1])
+    del cevals
+
+    # ---- step 7: every FRI layer
+    e, d = comp, 0
+    while True:
+        lroot, more = ctx.fri_commit_layer()
+        fleaves, fnodes = ctx.read("fri_leaves", d), ctx.read("fri_nodes", d)
+        assert fnodes[32:64].tobytes() == lroot, ("FRI root", d)
+        ok(O.check_fri_leaves(e, fleaves), "FRI leaves", d)
+        ok(O.check_merkle(fleaves, fnodes), "FRI tree", d)
+        if not more:
+            break
+        x = ints(D.prng_vector(lroot, 1))[0]
+        ctx.fri_fold(x)
+        nxt = ctx.read_elements("fri_evals", d + 1)
+        ok(O.check_fri_fold(e, x, nxt), "FRI fold", d)
+        e, d = nxt, d + 1
+    assert e.shape[0] <= 256 and d == (N.bit_length() - 1 - 8 + 1) // 2, (e.shape, d)       # the remainder: every element checked above
+    ctx.close()
+
+
+@pytest.mark.parametrize("log_n,log_blowup", [(7, 5), (10, 4)])
+def test_whole_domain_parity_small(oracle, log_n, log_blowup):
+    """the whole-domain checks at sizes where every intermediate is ALSO compared with the oracle's own (test_fibonacci_all_phases):
+    pins the driver itself, and runs on the CPU-emulated build"""
+    import distaff_amd as D
+    _whole_domain_parity(oracle, D, log_n, log_blowup=log_blowup)
+
+
+def test_whole_domain_parity_on_a_loop_trace(oracle):
+    """the whole-domain checks on a trace that is not the Fibonacci shape: the Collatz example from 27 (111 iterations of a `while` loop
+    with a nested if / else: 2^15 rows, 26 registers, loop depth 1, context depth 2), evaluator at all 2^18 steps"""
+    import distaff_amd as D
+    O = oracle
+    t = O.Trace("begin pad read dup push.1 ne while.true swap push.1 add swap dup isodd.128 if.true push.3 mul push.1 add else push.2 div end "
+                "dup push.1 ne end swap end", [], [27])
+    _whole_domain_parity(O, D, None, trace=t)
+
+
+def test_config3_whole_domain_parity(oracle):
+    """BASELINE config 3 (2^20 steps, default options, the bench.py headline): every element of every phase -- all 20 registers, the
+    evaluator at all 2^23 steps of the constraint domain, every FRI layer"""
+    import distaff_amd as D
+    _whole_domain_parity(oracle, D, 20)
+
+
 def test_config4_trace_full_size_on_one_gpu(oracle):
     """BASELINE config 4's trace (2^22 steps, default ProofOptions) on ONE GPU: three-pass transforms, 40 GiB of extension; the
     oracle's restatement of the reference verifier accepts the proof and rejects a wrong output / a flipped byte."""
@@ -909,6 +1084,13 @@ def test_config4_sampled_oracle_parity_at_full_size(oracle):
     (32 evaluator points; 8 LDE rows and 8 DEEP registers by Horner -- 4 M coefficients each)."""
     import distaff_amd as D
     _sampled_parity(oracle, D, 22, points=32, horner_rows=8, deep_registers=8, seed=2)
+
+
+def test_config4_whole_domain_parity(oracle):
+    """BASELINE config 4's trace (2^22 steps, three-pass transforms): every element of every phase, the evaluator at 2^18 steps (first and
+    last 4096, +-64 around every multiple of 2^16, random ones)"""
+    import distaff_amd as D
+    _whole_domain_parity(oracle, D, 22, seed=4, evaluator_points=1 << 18)
 
 
 def test_config5_full_size_on_one_gpu(oracle):
@@ -930,6 +1112,13 @@ def test_config5_sampled_oracle_parity_at_full_size(oracle):
     (32 evaluator points; 2 LDE rows and 4 DEEP registers by Horner -- 16 M coefficients each)."""
     import distaff_amd as D
     _sampled_parity(oracle, D, 24, log_blowup=4, num_queries=100, points=32, horner_rows=2, deep_registers=4, seed=3)
+
+
+def test_config5_whole_domain_parity(oracle):
+    """BASELINE config 5 (2^24 steps, blowup 16, 100 queries): every element of every phase -- the 2^28-row LDE read one column / one
+    block of rows at a time --, the evaluator at 2^18 steps"""
+    import distaff_amd as D
+    _whole_domain_parity(oracle, D, 24, log_blowup=4, num_queries=100, seed=5, evaluator_points=1 << 18)
 
 
 def _sharded_local_equals_single_context(log_n, world, **options):

@@ -116,12 +116,13 @@ def test_parity_selection_on_the_product_library_itself():
     """The phase-by-phase parity tests bind the test build (same sources, more switches).  A selection of them -- those that need no test-only
     switch -- is run here against distaff_amd/libdistaff_hip.so itself: every intermediate of every phase and the proof bytes, Fibonacci
     traces, other program shapes, traces of the whole instruction set with loops, the sharded prover with thread-ranks -- and the FULL-SIZE
-    checks (config 3: sampled oracle point computations in every phase at 2^20; config 5: 2^24 steps, the oracle's verifier accepts, a tampered
+    checks (config 3: sampled oracle point computations in every phase at 2^20, and every element of every phase against the whole-array
+    checkers of oracle/check.hpp; config 5: 2^24 steps, the oracle's verifier accepts, a tampered
     proof is rejected), which before round 6 had only ever run on the test build, a different code object."""
     selection = ["test_which_library_is_bound", "test_fibonacci_all_phases", "test_other_program_shapes", "test_program_shapes_with_stack_depth_5_to_8", "test_blowup_16_and_64",
                  "test_tiny_traces_of_32_and_16_rows", "test_thread_rank_transport_issue_order_and_peer_access", "test_loops_and_macros_at_2_13_and_2_15",
                  "test_whole_instruction_set_and_flow_blocks and not generic", "test_prove_sharded_peer_that_never_arrives",
-                 "test_config3_sampled_oracle_parity_at_full_size", "test_config5_full_size_on_one_gpu"]
+                 "test_config3_sampled_oracle_parity_at_full_size", "test_config3_whole_domain_parity", "test_config5_full_size_on_one_gpu"]
     env = dict(os.environ, DISTAFF_PRODUCT_ONLY="1")
     env.pop("DISTAFF_TEST_HOOKS", None)
     env.pop("DISTAFF_HIP_LIB", None)

@@ -7,6 +7,7 @@
 #include "host_proof.h"
 #include "host_util.h"
 #include "host_vm.h"
+#include "verify/host_verify.h"
 
 using namespace dsth;
 
@@ -890,6 +891,41 @@ int dst_fibonacci_trace(uint32_t log_n, uint8_t* cols, uint8_t program_hash[32],
     if (r) return DST_ERR_ARG;
     memcpy(program_hash, ph, 32);
     memcpy(result, &res, 16);
+    return DST_OK;
+}
+
+// ---- stark::verify on the host (verify/host_verify.h): no context, no HIP call --------------------------------------------------------
+static void put_text(char* err, size_t err_cap, const std::string& s) { if (err && err_cap) snprintf(err, err_cap, "%s", s.c_str()); }
+int dst_verify(const uint8_t program_hash[32], const dst_public* pub, const uint8_t* proof, size_t len, int* accepted, char* err, size_t err_cap) {
+    if (accepted) *accepted = 0;
+    put_text(err, err_cap, "");
+    if (!program_hash || !pub || !accepted || pub->num_inputs > 8 || pub->num_outputs > 8) { put_text(err, err_cap, "invalid argument"); return DST_ERR_ARG; }
+    hver::VProof p;
+    std::string why;
+    if (hver::parse_proof(proof, len, p, why)) { put_text(err, err_cap, why); return DST_ERR_ARG; }
+    u128 in[8], out[8];
+    memcpy(in, pub->inputs, sizeof(in)); memcpy(out, pub->outputs, sizeof(out));
+    for (uint32_t i = 0; i < 8; i++)
+        if ((i < pub->num_inputs && in[i] >= FIELD_P) || (i < pub->num_outputs && out[i] >= FIELD_P)) { put_text(err, err_cap, "public value not below the modulus"); return DST_ERR_ARG; }
+    hver::VerifyResult r = hver::verify_proof(program_hash, in, pub->num_inputs, out, pub->num_outputs, p);
+    *accepted = r.ok ? 1 : 0;
+    put_text(err, err_cap, r.error);
+    return DST_OK;
+}
+int dst_proof_info(const uint8_t* proof, size_t len, dst_proof_info_t* info) {
+    if (!info) return DST_ERR_ARG;
+    memset(info, 0, sizeof(*info));
+    hver::VProof p;
+    std::string why;
+    if (hver::parse_proof(proof, len, p, why)) return DST_ERR_ARG;
+    info->log_trace_length = (uint32_t)p.domain_depth - p.log_blowup;
+    info->extension_factor = 1u << p.log_blowup; info->num_queries = p.num_queries; info->grinding_factor = p.grinding;
+    info->ctx_depth = p.ctx_depth; info->loop_depth = p.loop_depth; info->stack_depth = p.stack_depth;
+    info->register_count = 15u + p.ctx_depth + p.loop_depth + p.stack_depth;
+    info->op_count = p.op_count;
+    info->fri_layers = (uint32_t)p.layers.size(); info->remainder_length = (uint32_t)p.rem_values.size();
+    info->security_level = hver::security_level(p, true); info->security_level_proven = hver::security_level(p, false);
+    info->pow_nonce = p.pow_nonce;
     return DST_OK;
 }
 

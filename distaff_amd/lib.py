@@ -54,13 +54,15 @@ EXPORTS = ["dst_ctx_create", "dst_ctx_destroy", "dst_last_error", "dst_phase_ms"
            "dst_shard_commit_trace", "dst_shard_eval_constraints", "dst_shard_combine", "dst_shard_fri_layer", "dst_shard_fri_fold",
            "dst_shard_export_size", "dst_shard_export", "dst_shard_import", "dst_shard_read", "dst_shard_fri_begin", "dst_shard_fri_end", "dst_shard_fri_roots", "dst_shard_open", "dst_shard_assemble", "dst_shard_info",
            "dst_comm_unique_id", "dst_comm_init", "dst_comm_init_local", "dst_comm_init_callbacks", "dst_comm_destroy", "dst_comm_last_error", "dst_comm_copy", "dst_prove_sharded", "dst_prove_sharded_local", "dst_shard_stage_ms",
-           "dst_comm_describe", "dst_comm_trace", "dst_test_hooks", "dst_comm_set_timeout", "dst_comm_abort", "dst_shard_exchange_ms", "dst_bench_clock"]
+           "dst_comm_describe", "dst_comm_trace", "dst_test_hooks", "dst_comm_set_timeout", "dst_comm_abort", "dst_shard_exchange_ms", "dst_bench_clock",
+           "dst_verify", "dst_proof_info"]
 
 
 class DistaffError(RuntimeError):
     def __init__(self, code, message):
         super().__init__("libdistaff_hip error %d: %s" % (code, message))
         self.code = code
+        self.reason = message
 
 
 class Params(ctypes.Structure):
@@ -78,6 +80,11 @@ class CommInfo(ctypes.Structure):
     _fields_ = [("transport", ctypes.c_uint32), ("rank", ctypes.c_uint32), ("world", ctypes.c_uint32), ("device", ctypes.c_int32),
                 ("rccl_ranks", ctypes.c_uint32), ("rccl_rank", ctypes.c_uint32), ("rccl_version", ctypes.c_uint32),
                 ("peers_other_device", ctypes.c_uint32), ("peers_enabled", ctypes.c_uint32)]
+
+
+class ProofInfo(ctypes.Structure):
+    _fields_ = [(f, ctypes.c_uint32) for f in ("log_trace_length", "extension_factor", "num_queries", "grinding_factor", "register_count", "ctx_depth", "loop_depth",
+                                               "stack_depth", "op_count", "fri_layers", "remainder_length", "security_level", "security_level_proven")] + [("pow_nonce", ctypes.c_uint64)]
 
 
 _lib = None
@@ -185,6 +192,34 @@ def blake3(data):
     out = ctypes.create_string_buffer(32)
     load().dst_blake3(bytes(data), ctypes.c_size_t(len(data)), out)
     return out.raw
+
+
+def verify(proof, program_hash, inputs, outputs, lib=None):
+    """stark::verify (src/lib.rs:72) on the host through dst_verify: no context, no GPU.  -> (accepted, error): (True, "") for a valid proof,
+    (False, the reference's error string) for a well-formed proof that does not verify.  Bytes that are not a StarkProof raise DistaffError
+    (DST_ERR_ARG) with the reason."""
+    proof, program_hash = bytes(proof), bytes(program_hash)
+    if len(program_hash) != 32:
+        raise DistaffError(DST_ERR_ARG, "program_hash must be 32 bytes")
+    if len(inputs) > 8 or len(outputs) > 8:
+        raise DistaffError(DST_ERR_ARG, "at most 8 public inputs and 8 outputs")
+    pub = make_public(inputs, outputs)
+    accepted = ctypes.c_int(0)
+    err = ctypes.create_string_buffer(512)
+    r = (lib or load()).dst_verify(program_hash, ctypes.byref(pub), proof, ctypes.c_size_t(len(proof)), ctypes.byref(accepted), err, ctypes.c_size_t(512))
+    if r != DST_OK:
+        raise DistaffError(r, err.value.decode())
+    return accepted.value == 1, err.value.decode()
+
+
+def proof_info(proof, lib=None):
+    """dst_proof_info: what a proof says about itself, without verifying it (trace length, options, register counts, FRI layers, security level)."""
+    proof = bytes(proof)
+    info = ProofInfo()
+    r = (lib or load()).dst_proof_info(proof, ctypes.c_size_t(len(proof)), ctypes.byref(info))
+    if r != DST_OK:
+        raise DistaffError(r, "not a StarkProof")
+    return {f: int(getattr(info, f)) for f, _ in ProofInfo._fields_}
 
 
 def fibonacci_trace(log_n):

@@ -122,6 +122,29 @@ DST_API int dst_build_proof(dst_ctx* ctx, const uint64_t* positions, uint32_t nu
 /* ---- the whole of stark::prove (prover.rs:17-168) on a trace already uploaded with dst_trace_upload ------------------- */
 DST_API int dst_prove(dst_ctx* ctx, const dst_public* pub, uint8_t* proof_out, size_t cap, size_t* proof_len);
 
+/* ---- the other half of the reference's public pair: stark::verify (src/lib.rs:72, src/stark/verifier.rs:11) ------------
+ * Host only: no context, no device, no HIP call -- it works on a machine without a GPU.  Returns DST_OK and *accepted = 1 for a valid
+ * proof; DST_OK and *accepted = 0 with the reference's error string in `err` for a well-formed proof that does not verify; DST_ERR_ARG
+ * (and a reason in `err`) for bytes that are not a StarkProof: truncated input, a length prefix that runs past the end, trailing bytes,
+ * options outside ProofOptions::new (options.rs:35-46), a hash tag other than 0, depths outside lib.rs:80-83,138, a field element (in the
+ * proof or in `pub`) that is not below p, a remainder longer than 256 values or not the last layer of the proof's own FRI layers.  `err` may be NULL;
+ * the text is cut to err_cap - 1 characters.  Re-entrant: no globals.  Milliseconds on one core at any trace length. */
+DST_API int dst_verify(const uint8_t program_hash[32], const dst_public* pub, const uint8_t* proof, size_t len,
+                       int* accepted, char* err, size_t err_cap);
+/* what a proof says about itself without verifying it (proof.rs:11-37, options.rs:16-27, 68-79) */
+typedef struct dst_proof_info_t {
+    uint32_t log_trace_length;          /* domain depth - log2(extension factor) */
+    uint32_t extension_factor, num_queries, grinding_factor;
+    uint32_t register_count;            /* 15 + ctx_depth + loop_depth + stack_depth */
+    uint32_t ctx_depth, loop_depth, stack_depth;
+    uint32_t op_count;
+    uint32_t fri_layers, remainder_length;
+    uint32_t security_level;            /* ProofOptions::security_level(optimistic = true), options.rs:68-79 */
+    uint32_t security_level_proven;     /* ... (optimistic = false) */
+    uint64_t pow_nonce;
+} dst_proof_info_t;
+DST_API int dst_proof_info(const uint8_t* proof, size_t len, dst_proof_info_t* out);
+
 /* ---- host-side helpers that the Rust host would otherwise take from `rand` (they run on the CPU) -------------------- */
 DST_API void dst_prng_vector(const uint8_t seed[32], uint32_t count, uint8_t* out /* count*16 */);          /* field.rs:271 */
 DST_API int dst_query_positions(const uint8_t seed[32], uint64_t domain_size, uint32_t blowup, uint32_t num_queries, uint64_t* out); /* utils/mod.rs:25 */

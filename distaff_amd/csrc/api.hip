@@ -7,6 +7,7 @@
 #include "host_proof.h"
 #include "host_util.h"
 #include "host_vm.h"
+#include "host_rescue.h"
 #include "verify/host_verify.h"
 
 using namespace dsth;
@@ -926,6 +927,168 @@ int dst_proof_info(const uint8_t* proof, size_t len, dst_proof_info_t* info) {
     info->fri_layers = (uint32_t)p.layers.size(); info->remainder_length = (uint32_t)p.rem_values.size();
     info->security_level = hver::security_level(p, true); info->security_level_proven = hver::security_level(p, false);
     info->pow_nonce = p.pow_nonce;
+    return DST_OK;
+}
+
+// ---- Rescue digests and Rescue Merkle trees (kernels_hash.hip / rescue_dev.h on the device, host_rescue.h on the host): no context ---------
+struct dst_rtree {
+    int device = -1;                      // < 0: the nodes live in `host`
+    uint32_t log_leaves = 0;
+    fe* dev = nullptr;                    // node array on the device: 2 elements per node, nodes[1] = root, nodes[leaves ..) = the leaves
+    std::vector<u128> host;
+    double device_ms = 0;                 // events around the level launches of the build
+    std::string err;
+};
+static thread_local std::string g_rtree_error;         // error of the calling thread's last failed call without a tree (dst_rtree_last_error(NULL))
+#define RT_HIP(errstr, expr, cleanup)                                                                \
+    do {                                                                                            \
+        hipError_t _e = (expr);                                                                     \
+        if (_e != hipSuccess) { (errstr) = std::string(#expr) + ": " + hipGetErrorString(_e); cleanup; return DST_ERR_HIP; } \
+    } while (0)
+static bool all_below_p(const uint8_t* p, size_t elems) {
+    for (size_t i = 0; i < elems; i++) { u128 v; memcpy(&v, p + 16 * i, 16); if (v >= FIELD_P) return false; }
+    return true;
+}
+
+// utils::hasher::digest (src/utils/hasher.rs:12)
+int dst_rescue_digest_many(int device, const uint8_t* in, size_t count, uint8_t* out) {
+    if ((!in || !out) && count) return DST_ERR_ARG;
+    if (count == 0) return DST_OK;
+    if (count > ((size_t)1 << 32)) return DST_ERR_ARG;
+    if (device < 0) {
+        if (!all_below_p(in, 4 * count)) { g_rtree_error = "an input element is not below the modulus"; return DST_ERR_ARG; }
+        try {
+            std::vector<u128> v(4 * count), d(2 * count);                  // the caller's buffers need only byte alignment
+            memcpy(v.data(), in, 64 * count);
+            rescue_digest_many_host(v.data(), count, d.data());
+            memcpy(out, d.data(), 32 * count);
+        } catch (const std::bad_alloc&) { g_rtree_error = "out of host memory"; return DST_ERR_HIP; }
+        return DST_OK;
+    }
+    fe *d_in = nullptr, *d_out = nullptr; uint32_t* d_bad = nullptr; hipStream_t st = nullptr;
+    auto cleanup = [&]() { if (d_in) hipFree(d_in); if (d_out) hipFree(d_out); if (d_bad) hipFree(d_bad); if (st) hipStreamDestroy(st); };
+    RT_HIP(g_rtree_error, hipSetDevice(device), cleanup());
+    RT_HIP(g_rtree_error, hipStreamCreateWithFlags(&st, hipStreamNonBlocking), cleanup());
+    RT_HIP(g_rtree_error, hipMalloc((void**)&d_in, count * 64), cleanup());
+    RT_HIP(g_rtree_error, hipMalloc((void**)&d_out, count * 32), cleanup());
+    RT_HIP(g_rtree_error, hipMalloc((void**)&d_bad, 4), cleanup());
+    RT_HIP(g_rtree_error, hipMemsetAsync(d_bad, 0, 4, st), cleanup());
+    RT_HIP(g_rtree_error, hipMemcpyAsync(d_in, in, count * 64, hipMemcpyHostToDevice, st), cleanup());
+    if (k_rescue_digests(st, d_in, d_out, count, d_bad)) { g_rtree_error = "rescue_digest_kernel: launch failed"; cleanup(); return DST_ERR_HIP; }
+    uint32_t bad = 0;
+    RT_HIP(g_rtree_error, hipMemcpyAsync(&bad, d_bad, 4, hipMemcpyDeviceToHost, st), cleanup());
+    RT_HIP(g_rtree_error, hipMemcpyAsync(out, d_out, count * 32, hipMemcpyDeviceToHost, st), cleanup());
+    RT_HIP(g_rtree_error, hipStreamSynchronize(st), cleanup());
+    cleanup();
+    if (bad) { g_rtree_error = "an input element is not below the modulus"; return DST_ERR_ARG; }
+    return DST_OK;
+}
+
+// the tree whose paths smpath / pmpath authenticate: parent = digest(l0, l1, r0, r1) (src/examples/merkle.rs:112-145)
+int dst_rtree_build(int device, const uint8_t* leaves, uint32_t log_leaves, dst_rtree** out) {
+    if (out) *out = nullptr;
+    if (!leaves || !out || log_leaves < 1 || log_leaves > 26) { g_rtree_error = "invalid argument (1 <= log_leaves <= 26)"; return DST_ERR_ARG; }
+    const size_t n = (size_t)1 << log_leaves;
+    dst_rtree* t = new (std::nothrow) dst_rtree;
+    if (!t) { g_rtree_error = "out of host memory"; return DST_ERR_HIP; }
+    t->device = device < 0 ? -1 : device; t->log_leaves = log_leaves;
+    if (device < 0) {
+        if (!all_below_p(leaves, 2 * n)) { g_rtree_error = "a leaf element is not below the modulus"; delete t; return DST_ERR_ARG; }
+        try { t->host.assign(4 * n, 0); } catch (const std::bad_alloc&) { g_rtree_error = "out of host memory"; delete t; return DST_ERR_HIP; }
+        memcpy(t->host.data() + 2 * n, leaves, 32 * n);
+        rescue_tree_host(t->host.data(), n);
+        *out = t;
+        return DST_OK;
+    }
+    uint32_t* d_bad = nullptr; hipStream_t st = nullptr; hipEvent_t e0 = nullptr, e1 = nullptr;
+    auto cleanup = [&]() { if (d_bad) hipFree(d_bad); if (st) hipStreamDestroy(st); if (e0) hipEventDestroy(e0); if (e1) hipEventDestroy(e1); };
+    auto fail = [&]() { cleanup(); if (t->dev) hipFree(t->dev); delete t; };
+    RT_HIP(g_rtree_error, hipSetDevice(device), fail());
+    RT_HIP(g_rtree_error, hipStreamCreateWithFlags(&st, hipStreamNonBlocking), fail());
+    RT_HIP(g_rtree_error, hipEventCreate(&e0), fail());
+    RT_HIP(g_rtree_error, hipEventCreate(&e1), fail());
+    RT_HIP(g_rtree_error, hipMalloc((void**)&t->dev, 64 * n), fail());
+    RT_HIP(g_rtree_error, hipMalloc((void**)&d_bad, 4), fail());
+    RT_HIP(g_rtree_error, hipMemsetAsync(d_bad, 0, 4, st), fail());
+    RT_HIP(g_rtree_error, hipMemsetAsync(t->dev, 0, 32, st), fail());                       // nodes[0] is not part of the tree
+    RT_HIP(g_rtree_error, hipMemcpyAsync(t->dev + 2 * n, leaves, 32 * n, hipMemcpyHostToDevice, st), fail());
+    RT_HIP(g_rtree_error, hipEventRecord(e0, st), fail());
+    if (k_rescue_tree(st, t->dev, n, d_bad)) { g_rtree_error = "rescue_tree_level_kernel: launch failed"; fail(); return DST_ERR_HIP; }
+    RT_HIP(g_rtree_error, hipEventRecord(e1, st), fail());
+    uint32_t bad = 0;
+    RT_HIP(g_rtree_error, hipMemcpyAsync(&bad, d_bad, 4, hipMemcpyDeviceToHost, st), fail());
+    RT_HIP(g_rtree_error, hipStreamSynchronize(st), fail());
+    float ms = 0;
+    RT_HIP(g_rtree_error, hipEventElapsedTime(&ms, e0, e1), fail());
+    t->device_ms = ms;
+    if (bad) { g_rtree_error = "a leaf element is not below the modulus"; fail(); return DST_ERR_ARG; }
+    cleanup();
+    *out = t;
+    return DST_OK;
+}
+void dst_rtree_destroy(dst_rtree* t) {
+    if (!t) return;
+    if (t->dev) { (void)hipSetDevice(t->device); hipFree(t->dev); }
+    delete t;
+}
+const char* dst_rtree_last_error(const dst_rtree* t) { return t ? t->err.c_str() : g_rtree_error.c_str(); }
+int dst_rtree_build_ms(const dst_rtree* t, double* device_ms) {
+    if (!t) return DST_ERR_ARG;
+    if (!device_ms) { const_cast<dst_rtree*>(t)->err = "null pointer"; return DST_ERR_ARG; }
+    *device_ms = t->device_ms;
+    return DST_OK;
+}
+// `count` nodes at the node-array positions pos[] -> out (32 bytes each)
+static int rtree_gather(const dst_rtree* ct, const uint64_t* pos, size_t count, uint8_t* out) {
+    dst_rtree* t = const_cast<dst_rtree*>(ct);
+    if (t->device < 0) { for (size_t k = 0; k < count; k++) memcpy(out + 32 * k, t->host.data() + 2 * pos[k], 32); return DST_OK; }
+    RT_HIP(t->err, hipSetDevice(t->device), (void)0);
+    for (size_t k = 0; k < count; k++) RT_HIP(t->err, hipMemcpy(out + 32 * k, t->dev + 2 * pos[k], 32, hipMemcpyDeviceToHost), (void)0);
+    return DST_OK;
+}
+int dst_rtree_read_nodes(const dst_rtree* t, uint64_t first, uint64_t count, uint8_t* out) {
+    if (!t) return DST_ERR_ARG;
+    if (!out && count) { const_cast<dst_rtree*>(t)->err = "null pointer"; return DST_ERR_ARG; }
+    const uint64_t total = (uint64_t)2 << t->log_leaves;
+    if (first > total || count > total - first) { const_cast<dst_rtree*>(t)->err = "node range past the end of the node array"; return DST_ERR_ARG; }
+    if (count == 0) return DST_OK;
+    if (t->device < 0) { memcpy(out, t->host.data() + 2 * first, 32 * count); return DST_OK; }
+    RT_HIP(const_cast<dst_rtree*>(t)->err, hipSetDevice(t->device), (void)0);
+    RT_HIP(const_cast<dst_rtree*>(t)->err, hipMemcpy(out, t->dev + 2 * first, 32 * count, hipMemcpyDeviceToHost), (void)0);
+    return DST_OK;
+}
+int dst_rtree_root(const dst_rtree* t, uint8_t root[32]) {
+    if (!t) return DST_ERR_ARG;
+    if (!root) { const_cast<dst_rtree*>(t)->err = "null pointer"; return DST_ERR_ARG; }
+    return dst_rtree_read_nodes(t, 1, 1, root);
+}
+int dst_rtree_path(const dst_rtree* t, uint64_t index, uint8_t* path) {
+    if (!t) return DST_ERR_ARG;
+    if (!path) { const_cast<dst_rtree*>(t)->err = "null pointer"; return DST_ERR_ARG; }
+    if (index >> t->log_leaves) { const_cast<dst_rtree*>(t)->err = "leaf index past the end"; return DST_ERR_ARG; }
+    uint64_t pos[27];
+    rescue_path_positions(t->log_leaves, index, pos);
+    return rtree_gather(t, pos, t->log_leaves + 1, path);
+}
+// generate_program_inputs (src/examples/merkle.rs:63-94)
+int dst_rtree_tapes(const dst_rtree* t, uint64_t index, uint32_t what, uint8_t* tape_a, uint8_t* tape_b, size_t cap_elems, size_t* elems) {
+    if (!t) return DST_ERR_ARG;
+    if (!elems || what < 1 || what > 3) { const_cast<dst_rtree*>(t)->err = "elems missing, or what outside 1..3"; return DST_ERR_ARG; }
+    const size_t n = t->log_leaves + 1;
+    *elems = ((what & 1u) ? 2 * n - 1 : 0) + ((what & 2u) ? n - 1 : 0);
+    if (!tape_a && !tape_b) {                                                              // size query
+        if (index >> t->log_leaves) { const_cast<dst_rtree*>(t)->err = "leaf index past the end"; return DST_ERR_ARG; }
+        return DST_OK;
+    }
+    if (!tape_a || !tape_b || cap_elems < *elems) { const_cast<dst_rtree*>(t)->err = "tape buffers missing or too small"; return DST_ERR_ARG; }
+    u128 path[2 * 27];
+    int r = dst_rtree_path(t, index, (uint8_t*)path);
+    if (r != DST_OK) return r;
+    try {
+        std::vector<u128> a, b;
+        rescue_tapes(path, n, index, what, a, b);
+        memcpy(tape_a, a.data(), 16 * a.size()); memcpy(tape_b, b.data(), 16 * b.size());
+    } catch (const std::bad_alloc&) { const_cast<dst_rtree*>(t)->err = "out of host memory"; return DST_ERR_HIP; }
     return DST_OK;
 }
 

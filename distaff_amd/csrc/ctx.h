@@ -373,3 +373,6 @@ void k_fri_fold_cm(dst_ctx* c, const fe* e, fe* out, size_t nd, int layer, fe sp
 void k_fri_draw_at(dst_ctx* c, const digest* nodes, fe* alpha_out, digest* root_out);    // x = prng(nodes[1]) on the device
 void k_copy(dst_ctx* c, void* dst, const void* src, size_t bytes);
 int k_field_op(dst_ctx* c, int op, const uint8_t* a, const uint8_t* b, uint8_t* out, size_t count);
+// Rescue digests / trees (kernels_hash.hip, rescue_dev.h): no context, the caller's stream; -1 when a launch fails; *bad = 1 for an input element >= p
+int k_rescue_digests(hipStream_t stream, const fe* in /* 4 per digest */, fe* out /* 2 per digest */, size_t count, uint32_t* bad);
+int k_rescue_tree(hipStream_t stream, fe* nodes /* 2 elements per node, leaf level in place */, size_t leaves, uint32_t* bad);

@@ -7,6 +7,7 @@
 // KT*16-byte runs along k and global writes are JT*32-byte runs along the leaf index.
 #include "ctx.h"
 #include "blake3_dev.h"
+#include "rescue_dev.h"
 
 #define HASH_THREADS 256
 
@@ -371,4 +372,66 @@ __global__ void __launch_bounds__(HASH_THREADS) fri_leaves_cm_kernel(const fe* _
 void k_fri_leaves_cm(dst_ctx* c, const fe* e, digest* leaves, size_t nd) {
     size_t total = nd / 4 * c->Bc;
     { KScope ks_(c, "fri_leaves_cm_kernel", 96.0 * total); hipLaunchKernelGGL(fri_leaves_cm_kernel, dim3((unsigned)((total + HASH_THREADS - 1) / HASH_THREADS)), dim3(HASH_THREADS), 0, c->stream, e, leaves, nd, (uint32_t)c->Bc); }
+}
+
+// ---- Rescue digests and Rescue Merkle trees (rescue_dev.h): utils::hasher::digest (src/utils/hasher.rs:12) and the trees that the VM's
+//      smpath / pmpath authenticate (parent = digest(l0, l1, r0, r1), src/examples/merkle.rs:112-145).  They need no prover context: the
+//      launchers take a stream.  A node is two field elements; node arrays have the layout of k_merkle_levels (nodes[1] = root,
+//      nodes[count .. 2 count) = the level of `count` nodes).  `bad` receives 1 when an input element is not below p. ------------------
+__global__ void __launch_bounds__(RESCUE_THREADS) rescue_digest_kernel(const fe* __restrict__ in, fe* __restrict__ out, size_t count, uint32_t* __restrict__ bad) {
+    const size_t i = (size_t)blockIdx.x * RESCUE_THREADS + threadIdx.x;
+    if (i >= count) return;
+    const fe v0 = in[4 * i], v1 = in[4 * i + 1], v2 = in[4 * i + 2], v3 = in[4 * i + 3];
+    if (!(rescue_canonical(v0) && rescue_canonical(v1) && rescue_canonical(v2) && rescue_canonical(v3))) *bad = 1u;
+    fe d0, d1;
+    rescue_digest4(v0, v1, v2, v3, d0, d1);
+    out[2 * i] = d0; out[2 * i + 1] = d1;
+}
+// one level, one lane per parent: nodes[count + i] = digest(nodes[2 (count + i)], nodes[2 (count + i) + 1]); check: the children are leaves
+__global__ void __launch_bounds__(RESCUE_THREADS) rescue_tree_level_kernel(fe* nodes, size_t count, uint32_t check, uint32_t* __restrict__ bad) {
+    const size_t i = (size_t)blockIdx.x * RESCUE_THREADS + threadIdx.x;
+    if (i >= count) return;
+    const size_t p = count + i;
+    const fe v0 = nodes[4 * p], v1 = nodes[4 * p + 1], v2 = nodes[4 * p + 2], v3 = nodes[4 * p + 3];
+    if (check && !(rescue_canonical(v0) && rescue_canonical(v1) && rescue_canonical(v2) && rescue_canonical(v3))) *bad = 1u;
+    fe d0, d1;
+    rescue_digest4(v0, v1, v2, v3, d0, d1);
+    nodes[2 * p] = d0; nodes[2 * p + 1] = d1;
+}
+// the same level with one parent per group of eight lanes (six of them working, one state element each): the narrow levels, where a launch
+// lasts one wavefront's dependent chain whatever its width -- the chain per lane is a sixth as long
+__global__ void __launch_bounds__(RESCUE_THREADS) rescue_tree_level_spread_kernel(fe* nodes, size_t count, uint32_t check, uint32_t* __restrict__ bad) {
+    __shared__ fe xch[RESCUE_THREADS];
+    const uint32_t e = threadIdx.x & 7u;
+    const size_t i = (size_t)blockIdx.x * (RESCUE_THREADS / 8u) + (threadIdx.x >> 3);
+    const bool live = i < count;                                       // lanes past the end keep the barriers and store nothing
+    const size_t p = count + (live ? i : 0);
+    fe v = fe_zero();                                                  // state after hasher.rs:18: (0, 0, r1, r0, l1, l0)
+    if (e >= 2u && e < 6u) {
+        v = nodes[4 * p + (5u - e)];
+        if (check && live && !rescue_canonical(v)) *bad = 1u;
+    }
+    rescue_permute_lane(v, e, xch + (threadIdx.x & ~7u));
+    if (live && (e == 5u || e == 4u)) nodes[2 * p + (5u - e)] = v;
+}
+// compile-time knob (profiles/rescue_tree.md): levels of at most this many parents use the spread form
+#ifndef RESCUE_SPREAD_MAX
+#define RESCUE_SPREAD_MAX ((size_t)1 << 15)
+#endif
+
+int k_rescue_digests(hipStream_t stream, const fe* in, fe* out, size_t count, uint32_t* bad) {
+    hipLaunchKernelGGL(rescue_digest_kernel, dim3((unsigned)((count + RESCUE_THREADS - 1) / RESCUE_THREADS)), dim3(RESCUE_THREADS), 0, stream, in, out, count, bad);
+    return hipGetLastError() == hipSuccess ? 0 : -1;
+}
+// fills nodes[1 .. leaves) of a node array whose leaf level nodes[leaves .. 2 leaves) is in place
+int k_rescue_tree(hipStream_t stream, fe* nodes, size_t leaves, uint32_t* bad) {
+    for (size_t count = leaves >> 1; count >= 1; count >>= 1) {
+        const uint32_t check = count == (leaves >> 1) ? 1u : 0u;
+        if (count <= RESCUE_SPREAD_MAX)
+            hipLaunchKernelGGL(rescue_tree_level_spread_kernel, dim3((unsigned)((count + RESCUE_THREADS / 8 - 1) / (RESCUE_THREADS / 8))), dim3(RESCUE_THREADS), 0, stream, nodes, count, check, bad);
+        else
+            hipLaunchKernelGGL(rescue_tree_level_kernel, dim3((unsigned)((count + RESCUE_THREADS - 1) / RESCUE_THREADS)), dim3(RESCUE_THREADS), 0, stream, nodes, count, check, bad);
+        if (hipGetLastError() != hipSuccess) return -1;
+    }
+    return 0;
 }

@@ -55,7 +55,9 @@ EXPORTS = ["dst_ctx_create", "dst_ctx_destroy", "dst_last_error", "dst_phase_ms"
            "dst_shard_export_size", "dst_shard_export", "dst_shard_import", "dst_shard_read", "dst_shard_fri_begin", "dst_shard_fri_end", "dst_shard_fri_roots", "dst_shard_open", "dst_shard_assemble", "dst_shard_info",
            "dst_comm_unique_id", "dst_comm_init", "dst_comm_init_local", "dst_comm_init_callbacks", "dst_comm_destroy", "dst_comm_last_error", "dst_comm_copy", "dst_prove_sharded", "dst_prove_sharded_local", "dst_shard_stage_ms",
            "dst_comm_describe", "dst_comm_trace", "dst_test_hooks", "dst_comm_set_timeout", "dst_comm_abort", "dst_shard_exchange_ms", "dst_bench_clock",
-           "dst_verify", "dst_proof_info"]
+           "dst_verify", "dst_proof_info",
+           "dst_rescue_digest_many", "dst_rtree_build", "dst_rtree_root", "dst_rtree_path", "dst_rtree_tapes", "dst_rtree_read_nodes", "dst_rtree_build_ms",
+           "dst_rtree_destroy", "dst_rtree_last_error"]
 
 
 class DistaffError(RuntimeError):
@@ -233,6 +235,107 @@ def fibonacci_trace(log_n):
         raise DistaffError(r, "dst_fibonacci_trace failed")
     return cols, ph.raw, int.from_bytes(res.raw, "little")
 
+
+def _elements(values, per_item):
+    """-> contiguous uint64 array [count, per_item, 2] from such an array or from a sequence of `per_item`-tuples of ints"""
+    if isinstance(values, np.ndarray) and values.dtype == np.uint64:
+        a = np.ascontiguousarray(values)
+    else:
+        rows = [tuple(v) for v in values]
+        if any(len(r) != per_item for r in rows):
+            raise DistaffError(DST_ERR_ARG, "every item must have %d elements" % per_item)
+        a = ints_to_arr([x for r in rows for x in r])
+    if a.size % (2 * per_item):
+        raise DistaffError(DST_ERR_ARG, "expected [count, %d, 2] uint64 words" % per_item)
+    return a.reshape(-1, per_item, 2)
+
+
+def _rtree_error(lib, handle=None):
+    lib.dst_rtree_last_error.restype = ctypes.c_char_p
+    lib.dst_rtree_last_error.argtypes = [ctypes.c_void_p]
+    return (lib.dst_rtree_last_error(handle) or b"").decode()
+
+
+def rescue_digest(values, device=0, lib=None):
+    """utils::hasher::digest (src/utils/hasher.rs:12) of every 4-tuple of `values` (a sequence of 4-tuples of ints, or uint64 words
+    [count, 4, 2]) through dst_rescue_digest_many -> uint64 words [count, 2, 2] (arr_to_ints turns them into ints).  device >= 0: on that GPU;
+    device < 0: on the host, no GPU needed.  An element that is not below p raises DistaffError(DST_ERR_ARG)."""
+    lib = lib or load()
+    a = _elements(values, 4)
+    out = np.zeros((a.shape[0], 2, 2), dtype=np.uint64)
+    r = lib.dst_rescue_digest_many(ctypes.c_int(device), _ptr(a), ctypes.c_size_t(a.shape[0]), _ptr(out))
+    if r != DST_OK:
+        raise DistaffError(r, _rtree_error(lib) or "dst_rescue_digest_many failed")
+    return out
+
+
+class RescueTree:
+    """A Merkle tree of the kind the VM's smpath.n / pmpath.n authenticate (``dst_rtree``): nodes of two field elements, parent =
+    hasher::digest(l0, l1, r0, r1).  `leaves`: a sequence of 2^k pairs of ints or uint64 words [2^k, 2, 2], 1 <= k <= 26.  device >= 0 builds
+    it on that GPU and keeps it there; device < 0 builds it on the host."""
+
+    def __init__(self, leaves, device=0, lib=None):
+        self.lib = lib or load()
+        a = _elements(leaves, 2)
+        n = a.shape[0]
+        if n < 2 or n & (n - 1):
+            raise DistaffError(DST_ERR_ARG, "the number of leaves must be a power of two >= 2")
+        self.log_leaves = n.bit_length() - 1
+        h = ctypes.c_void_p()
+        r = self.lib.dst_rtree_build(ctypes.c_int(device), _ptr(a), ctypes.c_uint32(self.log_leaves), ctypes.byref(h))
+        if r != DST_OK:
+            raise DistaffError(r, _rtree_error(self.lib))
+        self._h = h
+
+    def _check(self, r):
+        if r != DST_OK:
+            raise DistaffError(r, _rtree_error(self.lib, self._h))
+
+    def close(self):
+        if getattr(self, "_h", None):
+            self.lib.dst_rtree_destroy.restype = None
+            self.lib.dst_rtree_destroy(self._h)
+            self._h = None
+
+    def __del__(self):
+        self.close()
+
+    @property
+    def root(self):
+        """(r0, r1)"""
+        out = np.zeros((2, 2), dtype=np.uint64)
+        self._check(self.lib.dst_rtree_root(self._h, _ptr(out)))
+        return tuple(arr_to_ints(out))
+
+    @property
+    def build_ms(self):
+        """device milliseconds of the level kernels of the build (0 for a host tree)"""
+        ms = ctypes.c_double(0)
+        self._check(self.lib.dst_rtree_build_ms(self._h, ctypes.byref(ms)))
+        return ms.value
+
+    def path(self, index):
+        """authentication path of leaf `index`: [leaf, sibling, uncle, ...] as pairs of ints, log_leaves + 1 nodes"""
+        out = np.zeros((self.log_leaves + 1, 2, 2), dtype=np.uint64)
+        self._check(self.lib.dst_rtree_path(self._h, ctypes.c_uint64(index), _ptr(out)))
+        v = arr_to_ints(out)
+        return [(v[2 * k], v[2 * k + 1]) for k in range(self.log_leaves + 1)]
+
+    def tapes(self, index, what=3):
+        """secret tapes (A, B) as lists of ints for the program of src/examples/merkle.rs:46-56 with n = log_leaves + 1 and this index:
+        ProgramInputs::new(&[], &a, &b).  what = 1: the leaf and the smpath inputs only, 2: the pmpath inputs only, 3: both."""
+        n = ctypes.c_size_t(0)
+        self._check(self.lib.dst_rtree_tapes(self._h, ctypes.c_uint64(index), ctypes.c_uint32(what), None, None, ctypes.c_size_t(0), ctypes.byref(n)))
+        a = np.zeros((max(n.value, 1), 2), dtype=np.uint64)
+        b = np.zeros((max(n.value, 1), 2), dtype=np.uint64)
+        self._check(self.lib.dst_rtree_tapes(self._h, ctypes.c_uint64(index), ctypes.c_uint32(what), _ptr(a), _ptr(b), ctypes.c_size_t(n.value), ctypes.byref(n)))
+        return arr_to_ints(a[:n.value]), arr_to_ints(b[:n.value])
+
+    def nodes(self, first, count):
+        """`count` nodes of the node array from `first` as uint64 words [count, 2, 2]: index 1 = root, [2^log_leaves, 2^(log_leaves+1)) = the leaves"""
+        out = np.zeros((count, 2, 2), dtype=np.uint64)
+        self._check(self.lib.dst_rtree_read_nodes(self._h, ctypes.c_uint64(first), ctypes.c_uint64(count), _ptr(out)))
+        return out
 
 class Comm:
     """One rank's communicator handle (``dst_comm``) for ``Context.prove_sharded``: RCCL over xGMI, the unique id created by

@@ -145,6 +145,34 @@ typedef struct dst_proof_info_t {
 } dst_proof_info_t;
 DST_API int dst_proof_info(const uint8_t* proof, size_t len, dst_proof_info_t* out);
 
+/* ---- Rescue digests and Rescue Merkle trees: what the VM's smpath.n / pmpath.n authenticate ----------------------------------------------
+ * A node is two field elements (32 bytes); parent = utils::hasher::digest([l0, l1, r0, r1]): ten Rescue rounds on a six-element state
+ * (src/utils/hasher.rs:12-40).  The reference only ever walks a pseudo-random path through an imaginary tree (src/examples/merkle.rs:96-108);
+ * these build the tree, hand out authentication paths and lay them out as the secret tapes of the example's program.  No dst_ctx.
+ * device >= 0: on that GPU (inputs are checked there); device < 0: on the host, one thread, no HIP call -- works on a machine without a GPU,
+ * like dst_verify.  DST_ERR_ARG: null pointer, index past the end, log_leaves out of range, an element not below p. */
+/* utils::hasher::digest (hasher.rs:12) on `count` inputs of 4 elements each -> 2 elements each */
+DST_API int dst_rescue_digest_many(int device, const uint8_t* in /* count*64 */, size_t count, uint8_t* out /* count*32 */);
+typedef struct dst_rtree dst_rtree;
+/* tree over 2^log_leaves nodes of 2 elements (32 bytes), 1 <= log_leaves <= 26; parent = digest(l0, l1, r0, r1) (merkle.rs:112-145) */
+DST_API int dst_rtree_build(int device, const uint8_t* leaves, uint32_t log_leaves, dst_rtree** out);
+DST_API int dst_rtree_root(const dst_rtree* t, uint8_t root[32]);
+/* authentication path of leaf `index`: [leaf, sibling, uncle, ...], log_leaves + 1 nodes = a path of "depth n = log_leaves + 1" in the
+ * sense of merkle.rs:98-145 (compute_merkle_root of that path and index gives the root) */
+DST_API int dst_rtree_path(const dst_rtree* t, uint64_t index, uint8_t* path /* (log_leaves+1)*32 */);
+/* the secret tapes A and B that the program `read.ab dup.2 smpath.n swap.2 push.<index> roll.4 swap swap.2 pmpath.n` consumes
+ * (generate_program_inputs, merkle.rs:63-94), n = log_leaves + 1: 3n - 2 elements per tape.  what = 1: the leaf and the smpath inputs only
+ * (2n - 1 elements), 2: the pmpath inputs only (n - 1), 3: both.  *elems receives the count; tape_a = tape_b = NULL: size query. */
+DST_API int dst_rtree_tapes(const dst_rtree* t, uint64_t index, uint32_t what, uint8_t* tape_a, uint8_t* tape_b, size_t cap_elems, size_t* elems);
+/* `count` nodes of the node array from `first`: index 1 = root, [2^k, 2^(k+1)) = the level of 2^k nodes, [2^log_leaves, 2^(log_leaves+1)) = the leaves */
+DST_API int dst_rtree_read_nodes(const dst_rtree* t, uint64_t first, uint64_t count, uint8_t* out);
+/* milliseconds the level kernels of dst_rtree_build took on the device (0 for a host tree).  The library owns the stream of the build, so events
+ * around the launches -- without the allocation and the upload of the leaves, which a caller's clock around dst_rtree_build includes -- can only be
+ * recorded here; tools/rescue_tree_time.py reports this figure, as dst_phase_ms does for the prover's steps. */
+DST_API int dst_rtree_build_ms(const dst_rtree* t, double* device_ms);
+DST_API void dst_rtree_destroy(dst_rtree* t);
+DST_API const char* dst_rtree_last_error(const dst_rtree* t);     /* t may be NULL: the error of the calling thread's last failed dst_rtree_build / dst_rescue_digest_many */
+
 /* ---- host-side helpers that the Rust host would otherwise take from `rand` (they run on the CPU) -------------------- */
 DST_API void dst_prng_vector(const uint8_t seed[32], uint32_t count, uint8_t* out /* count*16 */);          /* field.rs:271 */
 DST_API int dst_query_positions(const uint8_t seed[32], uint64_t domain_size, uint32_t blowup, uint32_t num_queries, uint64_t* out); /* utils/mod.rs:25 */

@@ -1,0 +1,70 @@
+#!/usr/bin/env python3
+"""Device time of Rescue Merkle trees (dst_rtree_build: events around the level launches), the host path on one core, and the bound the
+device's own modular-multiplication rate sets.
+    python tools/rescue_tree_time.py [--host-log 12] [--lib path/to/another/build.so] [log_leaves ...]        (default 12 16 20)
+One digest is counted as 9 180 field multiplications, the reference's own count per hasher::digest: ten rounds of 6 x 2 for the cubes, 6 x 139
+for x^INV_ALPHA by the addition chain (127 squarings + 12 multiplications) and 2 x 36 for the two MDS products."""
+import argparse
+import os
+import sys
+import time
+
+import numpy as np
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+import distaff_amd as D
+
+MULS_PER_DIGEST = 10 * (6 * 2 + 6 * 139 + 2 * 36)
+
+ap = argparse.ArgumentParser()
+ap.add_argument("--host-log", type=int, default=12, help="size of the host-path tree (one core); 0: skip")
+ap.add_argument("--lib", default=None, help="another build of the library (a different RESCUE_SPREAD_MAX)")
+ap.add_argument("--runs", type=int, default=5)
+ap.add_argument("sizes", nargs="*", type=int)
+args = ap.parse_args()
+lib = D.lib._open(os.path.abspath(args.lib)) if args.lib else None       # through the binding: one HIP runtime per process
+
+
+def leaves(log_leaves):
+    a = np.random.default_rng(log_leaves).integers(0, 1 << 64, size=(1 << log_leaves, 2, 2), dtype=np.uint64)
+    a[..., 1] >>= np.uint64(1)                      # below p
+    return a
+
+
+try:                                                # what was measured: the commit, the digest of the kernel sources, the code objects (build()'s record)
+    import json
+    info = json.load(open(os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "distaff_amd", "_build_info.json")))
+    print("git HEAD %s, kernel sources %s%s" % (info.get("git_head"), info.get("csrc_sha16"), ", trees built by %s" % args.lib if args.lib else ""))
+    for name, k in sorted(info["kernels"].items()):
+        if "rescue" in name and not args.lib:
+            print("   %s: %d bytes of code, %s" % (name.split("(")[0], k["code_bytes"], ", ".join("%s %s" % (key, k[key]) for key in sorted(k) if key != "code_bytes")))
+except (OSError, KeyError, ValueError):
+    print("no distaff_amd/_build_info.json: run __graft_entry__.build()")
+cal = D.Calibration()
+cal.bench_mulmod()                                  # warm-up: clocks, code
+lanes, iters = 1 << 20, 1024
+mul_ms = min(cal.bench_mulmod(lanes, iters) for _ in range(5))
+cal.close()
+mul_rate = lanes * iters * 4 / (mul_ms * 1e-3)                       # four multiplication chains per lane and iteration (bench.py counts the same way)
+bound = mul_rate / MULS_PER_DIGEST
+print("dst_bench_mulmod: %.3e modular multiplications/s (%d lanes x %d iterations x 4 chains in %.3f ms) -> at most %.3e digests/s at %d multiplications per digest"
+      % (mul_rate, lanes, iters, mul_ms, bound, MULS_PER_DIGEST))
+for log_leaves in args.sizes or [12, 16, 20]:
+    a = leaves(log_leaves)
+    D.RescueTree(a, device=0, lib=lib).close()      # warm-up
+    ms = []
+    for _ in range(args.runs):
+        t = D.RescueTree(a, device=0, lib=lib)
+        ms.append(t.build_ms)
+        root = t.root
+        t.close()
+    best, digests = min(ms), (1 << log_leaves) - 1
+    print("2^%d leaves: %.3f ms on the device (min of %d; all: %s), %.3e digests/s, %.1f %% of the multiplication-rate bound, root %032x %032x"
+          % (log_leaves, best, args.runs, " ".join("%.3f" % v for v in ms), digests / (best * 1e-3), 100.0 * digests / (best * 1e-3) / bound, root[0], root[1]))
+if args.host_log:
+    a = leaves(args.host_log)
+    t0 = time.perf_counter()
+    t = D.RescueTree(a, device=-1, lib=lib)
+    s = time.perf_counter() - t0
+    print("2^%d leaves on the host path, one core: %.1f ms, %.3e digests/s, root %032x %032x" % ((args.host_log, s * 1e3, ((1 << args.host_log) - 1) / s) + t.root))
+    t.close()

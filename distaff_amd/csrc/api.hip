@@ -1,9 +1,9 @@
 // C-ABI of libdistaff_hip.so (include/distaff_hip.h): context, tables, the prover phases and proof assembly.
 // The phase order and every Fiat-Shamir dependency follow stark::prove (/root/reference/src/stark/prover.rs:17-168).
-#include <chrono>
 #include <cstdio>
 #include <cstdlib>
 #include "ctx.h"
+#include "host/steps.h"
 #include "host_proof.h"
 #include "host_util.h"
 #include "host_vm.h"
@@ -11,10 +11,11 @@
 #include "verify/host_verify.h"
 
 using namespace dsth;
+#include "host/steps_impl.h"    // the steps this file's drivers share with shard.hip's (host/steps.h), compiled with this unit
+using step::wall_ms;
+using step::event_ms;
 
 static std::string g_create_error;
-
-static double wall_ms() { return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now().time_since_epoch()).count(); }
 
 // ---- small host field helpers on limbs (fe.h compiles for the host too) ---------------------------------------------------------
 static fe h_root_of_unity(uint32_t log_order) {               // field.rs:228: G^(2^(40 - log_order))
@@ -282,17 +283,22 @@ static int ctx_init(dst_ctx* c) {
 static const fe* as_fe(const uint8_t* p) { return reinterpret_cast<const fe*>(p); }
 static std::vector<fe> copy_fe(const uint8_t* p, size_t count) { std::vector<fe> v(count); memcpy(v.data(), p, count * 16); return v; }
 
-extern "C" int dst_internal_build_proof(dst_ctx* c, const uint64_t* positions, uint32_t num_positions, uint64_t pow_nonce, std::vector<uint8_t>& proof);   // shard.hip
-extern "C" int dst_internal_shard_buffers(dst_ctx* c);      // shard.hip: exchange buffers of a sharded context
+// an asynchronous upload still in flight writes the same buffer from upload_stream: drain it before another upload starts
+static int drain_pending_upload(dst_ctx* c) {
+    if (c->upload_pending && c->upload_stream) HIP_TRY(c, hipStreamSynchronize(c->upload_stream));
+    c->upload_pending = false;
+    return DST_OK;
+}
 
-extern "C" {
+// The exported functions below have C linkage and default visibility through their declarations in include/distaff_hip.h; everything
+// else in this file is ordinary C++ and stays inside the library.
 
 int dst_ctx_create(const dst_params* params, dst_ctx** out) {
     if (!params || !out) { g_create_error = "null argument"; return DST_ERR_ARG; }
     dst_ctx* c = new dst_ctx();
     c->prm = *params;
     int r = ctx_init(c);
-    if (r == DST_OK && c->prm.world > 1) r = dst_internal_shard_buffers(c);       // a rank can join every collective from its first proof on
+    if (r == DST_OK && c->prm.world > 1) r = ensure_shard_buffers(c);       // a rank can join every collective from its first proof on
     if (r != DST_OK) { g_create_error = c->err; free_all(c); delete c; *out = nullptr; return r; }
     *out = c;
     return DST_OK;
@@ -300,13 +306,6 @@ int dst_ctx_create(const dst_params* params, dst_ctx** out) {
 void dst_ctx_destroy(dst_ctx* c) { if (!c) return; hipSetDevice(c->device); free_all(c); delete c; }
 const char* dst_last_error(const dst_ctx* c) { return c ? c->err.c_str() : g_create_error.c_str(); }
 int dst_phase_ms(const dst_ctx* c, double out_ms[9]) { if (!c || !out_ms) return DST_ERR_ARG; for (int i = 0; i < 9; i++) out_ms[i] = c->phase_ms[i]; return DST_OK; }
-
-// an asynchronous upload still in flight writes the same buffer from upload_stream: drain it before another upload starts
-static int drain_pending_upload(dst_ctx* c) {
-    if (c->upload_pending && c->upload_stream) HIP_TRY(c, hipStreamSynchronize(c->upload_stream));
-    c->upload_pending = false;
-    return DST_OK;
-}
 
 int dst_trace_upload(dst_ctx* c, const uint8_t* const* cols) {
     if (!c || !cols) return DST_ERR_ARG;
@@ -414,9 +413,9 @@ int dst_commit_trace(dst_ctx* c, uint8_t trace_root[32]) {
     memcpy(trace_root, c->trace_root, 32);
     {
         // extension = what the stream spent up to the event; the rest of the call's wall time is the tree (and the host's share)
-        float lde_ms = 0;
         const double total = wall_ms() - t0;
-        if (hipEventElapsedTime(&lde_ms, c->ph_ev[4], c->ph_ev[5]) != hipSuccess || lde_ms > total) lde_ms = 0;
+        double lde_ms = event_ms(c->ph_ev[4], c->ph_ev[5]);
+        if (lde_ms < 0 || lde_ms > total) lde_ms = 0;
         c->phase_ms[0] = lde_ms; c->phase_ms[1] = total - lde_ms;
     }
     c->committed = true; c->constraints_done = c->composed = false;
@@ -424,168 +423,22 @@ int dst_commit_trace(dst_ctx* c, uint8_t trace_root[32]) {
 }
 
 // ---- steps 3-5 ------------------------------------------------------------------------------------------------------------------
-// constraint degrees in constraint-index order (decoder/mod.rs:31-47, stack/mod.rs:40-41) and the coefficient each
-// constraint receives when they are visited in degree-group order (evaluator.rs:335-358,385-406; coefficients.rs:140-185)
-// the 344 constraint coefficients and the compacted transition coefficients -> device, queued from the page-locked staging area (the
-// callers' vectors go out of scope while the copies may still be pending: the evaluation's verdict is not waited for)
-int dst_internal_upload_draws(dst_ctx* c, const fe* draws344, const std::vector<fe>& tc, fe* d_coef, fe* d_tc) {
-    if ((344 + tc.size()) * sizeof(fe) > HS_DRAWS_BYTES) { c->err = "too many transition coefficients for the staging area"; return DST_ERR_ARG; }
-    fe* h = reinterpret_cast<fe*>(c->h_stage + HS_DRAWS);
-    memcpy(h, draws344, 344 * sizeof(fe));
-    memcpy(h + 344, tc.data(), tc.size() * sizeof(fe));
-    HIP_TRY(c, hipMemcpyAsync(d_coef, h, 344 * sizeof(fe), hipMemcpyHostToDevice, c->stream));
-    HIP_TRY(c, hipMemcpyAsync(d_tc, h + 344, tc.size() * sizeof(fe), hipMemcpyHostToDevice, c->stream));
-    return DST_OK;
-}
-void dst_internal_transition_coefficients(const dst_ctx* c, const fe* draws344, std::vector<fe>& tc) {
-    const size_t cl = c->prm.ctx_depth > 1 ? c->prm.ctx_depth : 1, ll = c->prm.loop_depth > 1 ? c->prm.loop_depth : 1;
-    const size_t sl = c->stack_depth > 8 ? c->stack_depth : 8;
-    std::vector<int> deg = {2, 2, 2, 2, 2, 2, 2, 2, 2, 2, 3, 8, 8, 6, 4, 6, 7, 6, 6, 4};
-    deg.resize(20 + cl + ll, 4);
-    deg.resize(20 + cl + ll + 2 + c->stack_depth, 7);
-    // compacted coefficient list (build_transition_coefficients)
-    const fe* t = draws344 + 188;
-    std::vector<fe> cc;
-    auto take = [&](size_t from, size_t cnt) { for (size_t i = 0; i < cnt; i++) cc.push_back(t[from + i]); };
-    take(0, 40); take(40, 2 * cl); take(72, 2 * ll); take(88, 4); take(92, 2 * sl);
-    const size_t nc = deg.size();
-    tc.assign(2 * nc, fe_zero());
-    size_t i = 0;
-    for (int d = 0; d <= 8; d++)
-        for (size_t k = 0; k < nc; k++)
-            if (deg[k] == d) { tc[k] = cc[2 * i]; tc[nc + k] = cc[2 * i + 1]; i++; }
-}
-
-// The two boundary combinations (evaluator.rs:181-326) in COEFFICIENT form.  With v_k(x) = T_k(x) - const_k for the constrained
-// registers k, the reference evaluates I(x) = sum_k v_k(x) * (cc_k + cc'_k * x^p), p = 6n + 2, on the 8n-point domain and interpolates
-// it again (constraint_table.rs:54-62).  I has degree < 7n + 2 < 8n, so the interpolant is I itself, and its coefficients are two
-// linear combinations of the trace polynomials: A = sum_k cc_k v_k at [0, n) and A' = sum_k cc'_k v_k at [p, p + n).  Nothing is
-// evaluated and nothing is interpolated: ip / fp (8n coefficients each, before the divisions) are written directly.
-// DISTAFF_BOUNDARY=eval keeps the evaluate-and-interpolate route (the tests compare its evaluation vectors with the oracle's).
-bool dst_internal_boundary_by_evaluation(const dst_ctx* c) { return DST_TEST_HOOKS && c->sw_is("DISTAFF_BOUNDARY", "eval"); }
-int dst_internal_boundary_polys(dst_ctx* c, const fe* draws344, fe* ip, fe* fp, fe* o0, fe* o1, fe* o2, fe* o3) {
-    const size_t n = c->n, D = 8 * n, W = c->W, p = 6 * n + 2;
-    const uint32_t ctx_depth = c->prm.ctx_depth, loop_depth = c->prm.loop_depth;
-    const size_t sd = c->stack_depth;
-    const size_t cl = ctx_depth > 1 ? ctx_depth : 1, ll = loop_depth > 1 ? loop_depth : 1;
-    // host: weights per trace register (plain, degree-adjusted) and the constant terms, for the first-step and last-step combinations
-    std::vector<u128> w(4 * W, 0);                       // [pass][adj][register]
-    u128 g[4] = {0, 0, 0, 0};                            // [pass][adj]
-    const u128 one = 1;
-    for (int pass = 0; pass < 2; pass++) {
-        const fe* cc = draws344 + pass * 94;
-        auto term = [&](int col, u128 constant, size_t idx) {       // value = T_col(x) - constant (col < 0: no register, value = -constant)
-            for (int adj = 0; adj < 2; adj++) {
-                const u128 k = fe_to_u128(cc[idx + adj]);
-                if (col >= 0) w[(pass * 2 + adj) * W + col] = hf_add(w[(pass * 2 + adj) * W + col], k);
-                if (constant != 0) g[pass * 2 + adj] = hf_add(g[pass * 2 + adj], hf_mul(k, constant));
-            }
-        };
-        term(0, pass ? (u128)c->op_count : 0, 0);
-        if (pass == 0) { for (int i = 0; i < 4; i++) term(1 + i, 0, 2 + 2 * i); }
-        else { for (int i = 0; i < 2; i++) term(1 + i, fe_to_u128(c->program_hash[i]), 2 + 2 * i); }
-        for (int i = 0; i < 3; i++) term(5 + i, pass ? one : 0, 10 + 2 * i);
-        for (int i = 0; i < 5; i++) term(8 + i, pass ? one : 0, 16 + 2 * i);
-        for (int i = 0; i < 2; i++) term(13 + i, pass ? one : 0, 26 + 2 * i);
-        for (size_t i = 0; i < cl; i++) if (i < ctx_depth) term(15 + (int)i, 0, 30 + 2 * i);
-        for (size_t i = 0; i < ll; i++) if (i < loop_depth) term(15 + (int)ctx_depth + (int)i, 0, 62 + 2 * i);
-        const uint32_t nio = pass ? c->pub.num_outputs : c->pub.num_inputs;
-        for (uint32_t i = 0; i < nio && i < 8; i++) {
-            u128 v; memcpy(&v, pass ? c->pub.outputs[i] : c->pub.inputs[i], 16);
-            term(i < sd ? 15 + (int)ctx_depth + (int)loop_depth + (int)i : -1, v, 78 + 2 * i);
-        }
-    }
-    std::vector<fe> up(4 * W + 4);
-    for (size_t i = 0; i < 4 * W; i++) up[i] = fe_from_u128(w[i]);
-    for (int i = 0; i < 4; i++) up[4 * W + i] = fe_from_u128(g[i]);
-    fe* d_w = (fe*)c->d_stage;                           // staging area is free until the openings
-    // through the page-locked staging area: the copy is queued and the host moves on
-    fe* h_w = reinterpret_cast<fe*>(c->h_stage + HS_WEIGHTS);
-    memcpy(h_w, up.data(), up.size() * sizeof(fe));
-    HIP_TRY(c, hipMemcpyAsync(d_w, h_w, up.size() * sizeof(fe), hipMemcpyHostToDevice, c->stream));
-    fe* outs[4] = {o0, o1, o2, o3};                       // [pass][adj]
-    if (ip) {                                            // the 8n-coefficient polynomials themselves (DISTAFF_COMBINE=steps)
-        HIP_TRY(c, hipMemsetAsync(ip, 0, D * sizeof(fe), c->stream));
-        HIP_TRY(c, hipMemsetAsync(fp, 0, D * sizeof(fe), c->stream));
-        outs[0] = ip; outs[1] = ip + p; outs[2] = fp; outs[3] = fp + p;
-    }
-    k_lincomb4(c, c->polys, W, n, d_w, outs[0], outs[1], outs[2], outs[3]);
-    for (int q = 0; q < 4; q++) k_sub_at0(c, outs[q], d_w + 4 * W + q);
-    return DST_OK;
-}
-
-// DISTAFF_COMBINE=steps: combine_polys and the DEEP composition as the reference's sequence of whole-array steps (boundary polynomials of
-// 8n coefficients, their divisions, additions; copy / division / multiply-adds of the composition) instead of the fused passes.  Tests
-// run both; the boundary-by-evaluation route implies it.
-bool dst_internal_combine_by_steps(const dst_ctx* c) { return DST_TEST_HOOKS && (c->sw_is("DISTAFF_COMBINE", "steps") || dst_internal_boundary_by_evaluation(c)); }
-
-// What the fused combination (k_combine_fused) reads of the two boundary constraints: I = A + x^p A', F = C + x^p C' (see
-// dst_internal_boundary_polys), p = 6n + 2, each of A, A', C, C' a linear combination of the trace polynomials with n coefficients.  Written
-// behind a leading zero and divided in place -- A, A' by (x - 1), C, C' by (x - x_last) -- so that q4[k][0] is the sum / the value at
-// x_last and q4[k][1 + i] the quotient coefficient i.  Four divisions over n + 1 coefficients instead of two over 8n.
-int dst_internal_boundary_quotients(dst_ctx* c, const fe* draws344, fe* q4, size_t stride) {
-    const size_t n = c->n;
-    HIP_TRY(c, hipMemsetAsync(q4, 0, 4 * stride * sizeof(fe), c->stream));
-    // ip = q4[0] (A at offset 0) ... dst_internal_boundary_polys writes A, A', C, C' at (ip, ip + p, fp, fp + p): hand it views whose
-    // "+ p" lands on the next array
-    int r = dst_internal_boundary_polys(c, draws344, nullptr, nullptr, q4 + 1, q4 + stride + 1, q4 + 2 * stride + 1, q4 + 3 * stride + 1);
-    if (r) return r;
-    fe* arrays[4] = {q4, q4 + stride, q4 + 2 * stride, q4 + 3 * stride};
-    const fe divisors[4] = {fe_one(), fe_one(), c->x_last, c->x_last};
-    k_syn_div_batch(c, arrays, divisors, 4, n + 1);            // one set of launches for the four
-    return DST_OK;
-}
-
-// milliseconds between two phase-boundary events of the last proof (recorded on the stream: no host wait at the boundary itself)
-static double event_ms(dst_ctx* c, int from, int to) {
-    float ms = 0;
-    return hipEventElapsedTime(&ms, c->ph_ev[from], c->ph_ev[to]) == hipSuccess ? (double)ms : 0.0;
-}
-
+// (the evaluation and combine_polys are stated in host/steps_impl.h, for this driver and the sharded ones)
 int dst_eval_constraints(dst_ctx* c, const dst_public* pub, const uint8_t* coeffs, uint8_t constraint_root[32], int64_t* bad_step) {
     if (!c || !pub || !coeffs || !constraint_root) return DST_ERR_ARG;
     if (!c->committed) { c->err = "dst_eval_constraints: trace not committed"; return DST_ERR_STATE; }
     if (pub->num_inputs > 8 || pub->num_outputs > 8) { c->err = "too many public inputs / outputs"; return DST_ERR_ARG; }
     if (c->prm.world != 1) { c->err = "dst_eval_constraints: multi-GPU combination is driven by the host (see distaff_amd/sharded.py)"; return DST_ERR_ARG; }
     HIP_TRY(c, hipSetDevice(c->device));
-    c->pub = *pub;
     const double t0 = wall_ms();
     HIP_TRY(c, hipEventRecord(c->ph_ev[0], c->stream));
-    std::vector<fe> draws = copy_fe(coeffs, 344), tc;
-    dst_internal_transition_coefficients(c, draws.data(), tc);
-    fe* d_coef = c->scratch + c->scratch_elems - 1024;           // tail of the scratch area
-    fe* d_tc = d_coef + 344;
-    if (int ru = dst_internal_upload_draws(c, draws.data(), tc, d_coef, d_tc)) return ru;
     // The host does not wait for the evaluation's verdict (evaluator.rs:152-158) before it queues the combination: the flag travels back
     // with the constraint root, and a trace that fails is reported then (the work queued behind it is wasted only in that case).
     const bool steps = dst_internal_combine_by_steps(c);
-    int r = k_eval_constraints(c, d_coef, d_tc, bad_step, /*defer_check=*/!steps);   // prover.rs:53-64
-    if (r == DST_ERR_AIR) { c->err = "transition constraints were not satisfied"; return r; }
+    int r = step::eval_constraints(c, pub, coeffs, bad_step, /*defer_check=*/!steps);
     if (r != DST_OK) return r;
     HIP_TRY(c, hipEventRecord(c->ph_ev[1], c->stream));
-    // combine_polys (constraint_table.rs:54-88)
-    const size_t n = c->n, D = 8 * n;
-    fe* work = c->cwork + 3 * D;
-    if (steps) {
-        fe* ip = c->cwork; fe* fp = c->cwork + D; fe* tp = c->cwork + 2 * D;
-        if (dst_internal_boundary_by_evaluation(c)) {
-            k_intt8_cosets(c, c->ceval, ip, work);
-            k_intt8_cosets(c, c->ceval + D, fp, work);
-        } else if ((r = dst_internal_boundary_polys(c, draws.data(), ip, fp))) return r;
-        k_syn_div(c, ip, D, fe_one());
-        k_syn_div(c, fp, D, c->x_last);
-        k_intt8_cosets(c, c->ceval + 2 * D, tp, work);
-        k_syn_div_expanded(c, tp, c->cpoly, D, n, c->x_last);
-        k_add(c, c->cpoly, ip, D);
-        k_add(c, c->cpoly, fp, D);
-    } else {
-        // boundary quotients (4 x (n + 1) coefficients), the eight inverse coset transforms, then ONE pass: 8-point step across cosets,
-        // division of the transition part, sum (k_combine_fused)
-        fe* q4 = c->cwork; const size_t qs = n + 16;
-        if ((r = dst_internal_boundary_quotients(c, draws.data(), q4, qs))) return r;
-        k_intt_cosets_local(c, c->ceval + 2 * D, work, 8);
-        k_combine_fused(c, work, q4, qs, c->cpoly);
-    }
+    if ((r = step::combine(c, 3))) return r;
     HIP_TRY(c, hipEventRecord(c->ph_ev[2], c->stream));
     // constraint_poly.eval + Merkle tree over raw evaluation pairs (prover.rs:82-86)
     k_lde_fold8(c, c->cpoly, c->cevals);
@@ -600,7 +453,8 @@ int dst_eval_constraints(dst_ctx* c, const dst_public* pub, const uint8_t* coeff
     }
     memcpy(constraint_root, c->constraint_root, 32);
     // phase times from the stream's own clock; what the host spent before the first and after the last event goes to the outer phases
-    const double total = wall_ms() - t0, e1 = event_ms(c, 0, 1), e2 = event_ms(c, 1, 2), e3 = event_ms(c, 2, 3);
+    auto between = [&](int from, int to) { const double ms = event_ms(c->ph_ev[from], c->ph_ev[to]); return ms > 0 ? ms : 0.0; };     // unknown counts as nothing
+    const double total = wall_ms() - t0, e1 = between(0, 1), e2 = between(1, 2), e3 = between(2, 3);
     const double rest = total > e1 + e2 + e3 ? total - (e1 + e2 + e3) : 0.0;
     c->phase_ms[2] = e1 + rest / 2; c->phase_ms[3] = e2; c->phase_ms[4] = e3 + rest / 2;
     c->constraints_done = true; c->composed = false;
@@ -631,8 +485,8 @@ static int compose_impl(dst_ctx* c, const uint8_t* draws_bytes, uint8_t* trace_a
     const fe z = draws[0];
     const fe next_z = fe_mul(z, c->g_trace);
     const fe k1 = draws[513], k2 = draws[514], k3 = draws[515];
-    fe* d_draws = c->scratch + c->scratch_elems - 1024;           // [516] draws, then [W] T(z), [W] T(z*g), [1] C(z)
-    fe* d_tz1 = d_draws + 520; fe* d_tz2 = d_tz1 + 128; fe* d_cz = d_tz2 + 128;
+    const step::ScratchTail tail(c);
+    fe* d_draws = tail.draws(); fe* d_tz1 = tail.tz1(); fe* d_tz2 = tail.tz2(); fe* d_cz = tail.cz();
     {   // queued from the page-locked staging area: `draws` goes out of scope while the copy may still be pending (wait == false)
         fe* h_draws = reinterpret_cast<fe*>(c->h_stage + HS_COMPOSE);
         memcpy(h_draws, draws.data(), 516 * 16);
@@ -703,31 +557,12 @@ int dst_fri_commit_layer(dst_ctx* c, uint8_t layer_root[32], int* more) {
     HIP_TRY(c, hipStreamSynchronize(c->stream));
     HIP_TRY(c, hipGetLastError());
     memcpy(layer_root, root, 32);
-    c->fri_roots.push_back(std::vector<uint8_t>(root, root + 32));
+    step::fri_file_root(c, d, root);
     c->fri_committed = d + 1;
     *more = (d + 1 < c->num_fri_layers) ? 1 : 0;
     if (d == 0) c->phase_ms[6] = 0;
     c->phase_ms[6] += wall_ms() - t0;
     return DST_OK;
-}
-// The rest of the FRI commit phase in ONE launch once the next layer to commit is small (k_fri_tail: rows hashed, trees built, x drawn
-// from every root and the folds done by one workgroup; DISTAFF_FRI_TAIL=0 keeps the per-layer launches, tests compare both).  Returns
-// 1 when the tail ran (all remaining roots appended), 0 when the next layer is still too large, < 0 on error.
-#define DST_FRI_TAIL_MAX_SIZE ((size_t)1 << 13)
-int dst_internal_fri_tail(dst_ctx* c, std::vector<uint8_t>& roots) {
-    const int d = c->fri_committed;
-    if (d < 1 || d != c->fri_folded || d >= c->num_fri_layers || c->fri_size[d] > DST_FRI_TAIL_MAX_SIZE) return 0;
-    if (const char* e = c->sw("DISTAFF_FRI_TAIL")) if (e[0] == '0') return 0;
-    double t0 = wall_ms();
-    const int count = c->num_fri_layers - d;
-    std::vector<uint8_t> r((size_t)count * 32);
-    int rc = k_fri_tail(c, d, r.data());
-    if (rc) return rc;
-    for (int i = 0; i < count; i++) c->fri_roots.push_back(std::vector<uint8_t>(r.begin() + 32 * i, r.begin() + 32 * (i + 1)));
-    roots.insert(roots.end(), r.begin(), r.end());
-    c->fri_committed = c->num_fri_layers; c->fri_folded = c->num_fri_layers - 1;
-    c->phase_ms[6] += wall_ms() - t0;
-    return 1;
 }
 int dst_fri_fold(dst_ctx* c, const uint8_t special_x[16]) {
     if (!c || !special_x) return DST_ERR_ARG;
@@ -766,7 +601,7 @@ int dst_build_proof(dst_ctx* c, const uint64_t* positions_in, uint32_t num_posit
     finish_deep_values(c);                                      // every FRI layer since has synchronised the stream
     // one plan, one batched device gather, one fill (shard.hip; the single-GPU case is the plan with every item local)
     std::vector<uint8_t> proof;
-    int rc = dst_internal_build_proof(c, positions_in, num_positions, pow_nonce, proof);
+    int rc = build_proof_local(c, positions_in, num_positions, pow_nonce, proof);
     if (rc == DST_OK) {
         *out_len = proof.size();
         if (out) {
@@ -778,58 +613,22 @@ int dst_build_proof(dst_ctx* c, const uint64_t* positions_in, uint32_t num_posit
     return rc;
 }
 
-// fri::reduce (fri/prover.rs:11-53) for dst_prove.  chained = true: the layers above the single-launch tail are committed WITHOUT host
-// round trips -- x = prng(root) is drawn on the device from the root where it lies (fri_draw_kernel, the same ChaCha20 / Uniform statement
-// the tail kernel uses) and the fold reads it from device memory; all roots are read back once, with the tail's.  chained = false
-// (DISTAFF_FRI_CHAIN=0, tests): one root read-back and one host draw per layer through the public phase calls.
-static int fri_commit_all(dst_ctx* c, std::vector<uint8_t>& roots, bool chained) {
-    int rc;
-    if (!chained) {
-        for (;;) {
-            if (int rt = dst_internal_fri_tail(c, roots)) { if (rt < 0) return rt; break; }
-            uint8_t root[32]; int more = 0;
-            if ((rc = dst_fri_commit_layer(c, root, &more))) return rc;
-            roots.insert(roots.end(), root, root + 32);
-            if (!more) break;
-            fe sx = prng(root);
-            if ((rc = dst_fri_fold(c, (const uint8_t*)&sx))) return rc;
-        }
-        return DST_OK;
+// fri::reduce (fri/prover.rs:11-53) for dst_prove.  chained = true: no host round trip per layer (step::fri_commit_natural from layer 0).
+// chained = false (DISTAFF_FRI_CHAIN=0, tests): one root read-back and one host draw per layer through the public phase calls, up to
+// the single-launch tail.
+static int fri_commit_all(dst_ctx* c, bool chained) {
+    if (chained) {
+        if (!c->composed || c->fri_committed != 0 || c->fri_folded != 0) { c->err = "dst_prove: FRI state"; return DST_ERR_STATE; }
+        return step::fri_commit_natural(c, 0);
     }
-    if (!c->composed || c->fri_committed != 0 || c->fri_folded != 0) { c->err = "dst_prove: FRI state"; return DST_ERR_STATE; }
-    const int L = c->num_fri_layers;
-    digest* d_roots = reinterpret_cast<digest*>(c->d_fri_chain);
-    fe* d_alpha = reinterpret_cast<fe*>(c->d_fri_chain + DST_MAX_FRI_LAYERS * 32);
-    const char* te = c->sw("DISTAFF_FRI_TAIL");
-    const bool tail_on = !(te && te[0] == '0');
-    int d = 0;
-    for (; d < L; d++) {
-        if (tail_on && d >= 1 && c->fri_size[d] <= DST_FRI_TAIL_MAX_SIZE) break;          // the rest in one launch
-        if (d == 0) k_fri_leaves_layer0(c); else k_fri_leaves(c, d);
-        k_merkle_levels(c, c->fri_leaves[d], c->fri_nodes[d], c->fri_size[d] / 4);
-        k_fri_draw(c, d, d_alpha + d, d_roots + d);
-        if (d + 1 < L) k_fri_fold_dev(c, d, d_alpha + d);
+    for (;;) {
+        if (fri_tail_starts_at(c, c->fri_committed)) return step::fri_commit_natural(c, c->fri_committed);
+        uint8_t root[32]; int more = 0, rc;
+        if ((rc = dst_fri_commit_layer(c, root, &more))) return rc;
+        if (!more) return DST_OK;
+        fe sx = prng(root);
+        if ((rc = dst_fri_fold(c, (const uint8_t*)&sx))) return rc;
     }
-    const int big = d;                                                // layers committed by the per-layer kernels
-    uint8_t* h_roots = c->h_stage + HS_FRI_ROOTS;                      // page-locked: queued, picked up after the wait below
-    if (big) HIP_TRY(c, hipMemcpyAsync(h_roots, d_roots, (size_t)big * 32, hipMemcpyDeviceToHost, c->stream));
-    c->fri_committed = big; c->fri_folded = big < L ? big : L - 1;
-    std::vector<uint8_t> tail_roots;
-    if (big < L) {
-        if (int rt = dst_internal_fri_tail(c, tail_roots)) { if (rt < 0) return rt; }     // synchronises the stream; appends its roots to c->fri_roots
-        else { c->err = "dst_prove: the FRI tail did not run"; return DST_ERR_STATE; }
-    } else {
-        HIP_TRY(c, hipStreamSynchronize(c->stream));
-        HIP_TRY(c, hipGetLastError());
-    }
-    // c->fri_roots in layer order: the tail pushed its own behind what was there (nothing yet): put the big layers' in front
-    std::vector<std::vector<uint8_t>> all;
-    for (int i = 0; i < big; i++) all.emplace_back(h_roots + 32 * i, h_roots + 32 * (i + 1));
-    for (auto& r : c->fri_roots) all.push_back(r);
-    c->fri_roots.swap(all);
-    for (auto& r : c->fri_roots) roots.insert(roots.end(), r.begin(), r.end());
-    c->fri_committed = L; c->fri_folded = L - 1;
-    return DST_OK;
 }
 
 // ---- the whole prover -----------------------------------------------------------------------------------------------------------
@@ -848,23 +647,18 @@ int dst_prove(dst_ctx* c, const dst_public* pub, uint8_t* proof_out, size_t cap,
     std::vector<uint8_t> z1(c->W * 16), z2(c->W * 16);
     const double t_compose = wall_ms();
     if ((rc = compose_impl(c, (const uint8_t*)draws.data(), z1.data(), z2.data(), false))) return rc;
-    std::vector<uint8_t> roots;
     {
         const char* ce = c->sw("DISTAFF_FRI_CHAIN");
-        if ((rc = fri_commit_all(c, roots, !(ce && ce[0] == '0')))) return rc;
+        if ((rc = fri_commit_all(c, !(ce && ce[0] == '0')))) return rc;
         // the commit phase's first wait covered the composition too: split at the device's own boundary (events of compose_impl)
-        const double both = wall_ms() - t_compose;
-        float dev = 0;
-        if (hipEventElapsedTime(&dev, c->ph_ev[0], c->ph_ev[1]) == hipSuccess && dev > 0 && dev < both) { c->phase_ms[5] = dev; c->phase_ms[6] = both - dev; }
+        const double both = wall_ms() - t_compose, dev = event_ms(c->ph_ev[0], c->ph_ev[1]);
+        if (dev > 0 && dev < both) { c->phase_ms[5] = dev; c->phase_ms[6] = both - dev; }
         else { c->phase_ms[6] = both > c->phase_ms[5] ? both - c->phase_ms[5] : 0.0; }
     }
     double t0 = wall_ms();
-    uint8_t seed0[32], seed1[32];
-    if (!blake3_short(roots.data(), roots.size(), seed0)) { c->err = "too many FRI roots"; return DST_ERR_ARG; }   // prover.rs:120-127
     uint64_t nonce = 0;
-    if ((rc = dst_pow_grind(c, seed0, c->prm.grinding_factor, seed1, &nonce))) return rc;
     std::vector<uint64_t> positions;
-    if (query_positions(seed1, c->N, (uint32_t)c->B, c->prm.num_queries, positions)) { c->err = "could not generate enough query positions"; return DST_ERR_ARG; }
+    if ((rc = step::query_seed(c, &nonce, positions))) return rc;
     c->phase_ms[7] = wall_ms() - t0;
     return dst_build_proof(c, positions.data(), (uint32_t)positions.size(), nonce, proof_out, cap, proof_len);
 }
@@ -1148,8 +942,8 @@ int dst_kernel_stats(dst_ctx* c, char* json_out, size_t cap, int reset) {
     HIP_TRY(c, hipSetDevice(c->device));
     HIP_TRY(c, hipStreamSynchronize(c->stream));
     for (auto& e : c->kpending) {
-        float ms = 0;
-        if (hipEventElapsedTime(&ms, e.e0, e.e1) == hipSuccess) { auto& st = c->kstats[e.name]; st.launches++; st.ms += ms; st.bytes += e.bytes; st.mads += e.mads; }
+        const double ms = event_ms(e.e0, e.e1);
+        if (ms >= 0) { auto& st = c->kstats[e.name]; st.launches++; st.ms += ms; st.bytes += e.bytes; st.mads += e.mads; }
         c->event_pool.push_back(e.e0); c->event_pool.push_back(e.e1);
     }
     c->kpending.clear();
@@ -1202,4 +996,3 @@ int dst_bench_clock(dst_ctx* c, uint64_t, uint32_t, double*) { return no_hooks(c
 // 1 when this is the test / bench build
 int dst_test_hooks(void) { return DST_TEST_HOOKS; }
 
-}  // extern "C"

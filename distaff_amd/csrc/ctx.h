@@ -69,7 +69,7 @@ static const dst_switch_def DST_SWITCHES[] = {
     {"DISTAFF_MERKLE_LEVEL2_LOG",  false, "k",               "build two tree levels per launch from 2^k nodes on (default 2^15)"},
     {"DISTAFF_MERKLE_LEVELS",      false, "1",               "one launch per tree level"},
     {"DISTAFF_SYN_DIV_TABLES",     false, "1",               "synthetic division by power tables + scan instead of the blocked form"},
-    {"DISTAFF_FRI_TAIL",           false, "0|k",             "0: no single-launch tail; k: tail from layers of 2^k elements on"},
+    {"DISTAFF_FRI_TAIL",           false, "0",               "no single-launch tail: every FRI layer by its own launches (the tail otherwise starts at the first layer of at most 2^13 elements)"},
     {"DISTAFF_FRI_CHAIN",          false, "0",               "FRI commit phase with a root read-back and a host draw per layer"},
     {"DISTAFF_FRI_REPLICATE_LOG",  false, "k",               "sharded prover: replicate FRI layers from 2^k elements on (default 2^17)"},
     {"DISTAFF_SHARD_FORCE_OVERLAP", false, "1",              "sharded prover: the two-stream choreography of a stream-ordered transport over a blocking one"},
@@ -80,15 +80,15 @@ static const dst_switch_def DST_SWITCHES[] = {
 // staged by the runtime -- which makes the host wait for the stream -- or go out of scope).  Regions are reused per proof: the host
 // synchronises the stream at least once between two uses of the same region.
 enum : size_t {
-    HS_WEIGHTS = 0,                    // boundary weights: 4 W + 4 elements                                   (api.hip dst_internal_boundary_polys)
+    HS_WEIGHTS = 0,                    // boundary weights: 4 W + 4 elements                                   (host/steps_impl.h step::boundary_polys)
     HS_WEIGHTS_BYTES = (4 * 128 + 4) * 16,
     HS_DEEP = 32768,                   // read-back of T(z) at +0 and T(z g) at +HS_DEEP_HALF, W elements each   (api.hip compose_impl)
     HS_DEEP_HALF = 2048,
-    HS_FRI_ROOTS = 40960,              // read-back of the FRI roots: 32 bytes per layer                          (api.hip / shard.hip FRI commit)
+    HS_FRI_ROOTS = 40960,              // read-back of the FRI roots: 32 bytes per layer                          (host/steps_impl.h step::fri_commit_natural)
     HS_FRI_SLOTS = 45056,              // sharded FRI layers: deferred tree records, HS_FRI_SLOT_BYTES per layer  (shard.hip dst_prove_sharded)
     HS_FRI_SLOT_BYTES = 800,           //   G records of 96 bytes + the 32-byte root, G <= 8
     HS_AIR_FLAG = 65536 - 64,          // read-back of the failing step of the constraint check                   (kernels_air.hip)
-    HS_DRAWS = 65536,                  // upload of the 344 constraint coefficients + the compacted transition coefficients (<= 156)
+    HS_DRAWS = 65536,                  // upload of the 344 constraint coefficients + the compacted transition coefficients (<= 156)   (host/steps_impl.h step::eval_constraints)
     HS_DRAWS_BYTES = (344 + 160) * 16,
     HS_COMPOSE = 65536 + 8192,         // upload of the 516 composition draws
     HS_COMPOSE_BYTES = 516 * 16,
@@ -165,7 +165,7 @@ struct dst_ctx {
     size_t Bc = 0, j0 = 0;              // local cosets
     size_t stack_depth = 0;
     NttPlan plan;
-    std::vector<fe> shard_draws;       // shard.hip: the 344 constraint coefficients of the current proof
+    std::vector<fe> air_draws;         // the 344 constraint coefficients of the current proof: step::eval_constraints keeps them for step::combine (host/steps_impl.h)
     std::shared_ptr<void> open_plan;   // shard.hip: plan of the last dst_shard_open, reused by dst_shard_assemble for the same positions
     std::vector<uint64_t> open_plan_positions;
     uint8_t open_plan_root[32] = {0};   // trace root the cached plan was built for
@@ -210,7 +210,7 @@ struct dst_ctx {
     digest *cnodes = nullptr;           // [N/2]
     fe *comp_poly = nullptr;            // [8n]
     fe *comp = nullptr;                 // [Bc][n]
-    fe *scratch = nullptr;              // misc scan / reduction scratch
+    fe *scratch = nullptr;              // misc scan / reduction scratch; its last 1024 elements: the small vectors of the phase in flight (host/steps.h ScratchTail)
     size_t scratch_elems = 0;
     int num_fri_layers = 0, fri_committed = 0, fri_folded = 0;
     fe *fri_e[DST_MAX_FRI_LAYERS] = {nullptr};       // evaluations of layer d (d = 0 aliases comp, coset-major)
@@ -306,12 +306,23 @@ struct KScope {
 int ctx_sync(dst_ctx* c, const char* what);
 #define CTX_SYNC(ctx, what) do { const int _r = ctx_sync((ctx), (what)); if (_r) return _r; } while (0)
 
+// ---- which formulation of a step a context runs: asked by the constraint launchers (kernels_air*.hip) and by the steps themselves
+//      (host/steps.h, host/steps_impl.h) ----------------------------------------------------------------------------------------------
+// DISTAFF_BOUNDARY=eval (test build only): the boundary combinations by evaluation on the 8n domain, the reference's route
+inline bool dst_internal_boundary_by_evaluation(const dst_ctx* c) { return DST_TEST_HOOKS && c->sw_is("DISTAFF_BOUNDARY", "eval"); }
+// DISTAFF_COMBINE=steps (test build only): combine_polys and the DEEP composition as the reference's sequence of whole-array steps
+// (boundary polynomials of 8n coefficients, their divisions, additions; copy / division / multiply-adds of the composition) instead of
+// the fused passes.  Tests run both; the boundary-by-evaluation route implies it.
+inline bool dst_internal_combine_by_steps(const dst_ctx* c) { return DST_TEST_HOOKS && (c->sw_is("DISTAFF_COMBINE", "steps") || dst_internal_boundary_by_evaluation(c)); }
+// Step 7: does the single-launch tail (k_fri_tail: rows hashed, trees built, x drawn from every root and the folds done by one workgroup)
+// start at layer d?  From the first layer after layer 0 of at most 2^13 evaluations on; DISTAFF_FRI_TAIL=0 (test build only): never.
+inline bool fri_tail_starts_at(const dst_ctx* c, int d) {
+    if (d < 1 || d >= c->num_fri_layers || c->fri_size[d] > ((size_t)1 << 13)) return false;
+    const char* e = c->sw("DISTAFF_FRI_TAIL");
+    return !(e && e[0] == '0');
+}
 // ---- kernel launchers (kernels_*.hip) ------------------------------------------------------------------------------------
 // NTT / LDE
-extern "C" bool dst_internal_boundary_by_evaluation(const dst_ctx* c);                             // api.hip: DISTAFF_BOUNDARY=eval (test build only)
-extern "C" int dst_internal_boundary_polys(dst_ctx* c, const fe* draws344, fe* ip, fe* fp, fe* o0 = nullptr, fe* o1 = nullptr, fe* o2 = nullptr, fe* o3 = nullptr);   // api.hip: boundary combinations in coefficient form (ip / fp: 8n coefficients each; or the four n-coefficient pieces)
-extern "C" bool dst_internal_combine_by_steps(const dst_ctx* c);                                   // api.hip: DISTAFF_COMBINE=steps (the reference's sequence of whole-array steps; test build only)
-extern "C" int dst_internal_boundary_quotients(dst_ctx* c, const fe* draws344, fe* q4, size_t stride);   // api.hip: the n-coefficient quotients the fused combination reads
 int k_build_twiddle_tables(dst_ctx* c);                                                 // fills tw4_lde / tw4_fwd / tw4_inv (context creation)
 void k_intt_columns(dst_ctx* c, const fe* src, size_t src_stride, fe* dst, size_t ncols); // size-n inverse NTT of ncols columns src_stride apart -> contiguous columns
 void k_lde_columns(dst_ctx* c, const fe* polys, fe* lde, size_t ncols);                 // n coefficients -> coset-major [Bc][n] per column

@@ -4,26 +4,27 @@
 // boundary nodes and that the constraint evaluations are all-gathered before the cross-coset inverse transform.  The
 // collectives themselves are issued by the host (torch.distributed / RCCL in distaff_amd/sharded.py): this file only
 // exports and imports the shards.
-#include <chrono>
-#include <functional>
 #include <set>
 #include <thread>
 #include "ctx.h"
 #include "comm.h"
+#include "host/steps.h"
 #include "host_util.h"
 #include "host_proof.h"
 
 using namespace dsth;
+using step::wall_ms;
+using step::event_ms;
+using step::fri_nd;
+using step::fri_layer_natural;
 
-extern "C" void dst_internal_transition_coefficients(const dst_ctx* c, const fe* draws344, std::vector<fe>& tc);   // api.hip
-extern "C" int dst_internal_upload_draws(dst_ctx* c, const fe* draws344, const std::vector<fe>& tc, fe* d_coef, fe* d_tc);   // api.hip: queued from the page-locked staging area
+// The exported functions below have C linkage and default visibility through their declarations in include/distaff_hip.h; everything
+// else in this file is ordinary C++ and stays inside the library.
 
 enum { SH_TRACE_TREE = 0, SH_CONSTRAINT_TREE = 1, SH_FRI_TREE = 2, SH_CEVAL = 3, SH_FRI_LAST = 4, SH_FRI_SEND_CAP = 5 };
 enum { RD_TRACE_LEAF = 0, RD_TRACE_NODE = 1, RD_TRACE_UPPER = 2, RD_CEVAL = 3, RD_C_NODE = 4, RD_C_UPPER = 5, RD_FRI_E = 6, RD_FRI_LEAF = 7,
        RD_FRI_NODE = 8, RD_FRI_UPPER = 9, RD_LDE_ROW = 10, RD_TEVAL = 11,
        RD_MID_OFFSET = 32 };            // RD_*_UPPER + RD_MID_OFFSET: the rank's subtree heap of a k-range tree (behind the 2G entries of the top heap)
-
-static size_t fri_nd(const dst_ctx* c, int d) { return c->fri_size[d] / c->B; }     // elements per coset in layer d
 
 // FRI across ranks.  The large layers stay sharded: coset-major evaluations, rank-local leaves and tree levels, one all-gather
 // of boundary nodes per layer.  From the first layer that is small (at most 2^17 elements, 2 MiB) or has fewer than one
@@ -38,10 +39,12 @@ static int fri_replicated_from(const dst_ctx* c) {
         if (c->fri_size[d] <= ((size_t)1 << log_limit) || fri_nd(c, d) < 4) return d;
     return c->num_fri_layers - 1;
 }
-static const fe* fri_layer_natural(const dst_ctx* c, int d) { return (d == 0 && c->fri_rep_from == 0) ? c->fri_nat0 : c->fri_e[d]; }
 static bool fri_layer_replicated(const dst_ctx* c, int d) { return c->sharded_layout && d >= c->fri_rep_from; }
 
-static int ensure_shard_buffers(dst_ctx* c) {
+// Every buffer a collective of the sharded protocol touches exists from context creation on (dst_ctx_create, world > 1): a rank that fails
+// locally at proving time (no trace uploaded, a bad argument) can still take part in every exchange and report its status through
+// them, instead of leaving its peers in a collective it never enters.
+int ensure_shard_buffers(dst_ctx* c) {
     if (c->gather_buf && c->d_status) return DST_OK;
     if (c->gather_buf) { HIP_TRY(c, hipMalloc((void**)&c->d_status, 1024)); return DST_OK; }
     const size_t n = c->n, G = c->prm.world;
@@ -61,11 +64,6 @@ static int ensure_shard_buffers(dst_ctx* c) {
     HIP_TRY(c, hipMalloc((void**)&c->d_status, 1024));     // status records of dst_prove_sharded (one per rank)
     return DST_OK;
 }
-// Every buffer a collective of the sharded protocol touches exists from context creation on (api.hip, world > 1): a rank that fails
-// locally at proving time (no trace uploaded, a bad argument) can still take part in every exchange and report its status through
-// them, instead of leaving its peers in a collective it never enters.
-extern "C" int dst_internal_shard_buffers(dst_ctx* c) { return ensure_shard_buffers(c); }
-static double wall_ms_shard() { return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now().time_since_epoch()).count(); }
 static int copy_in(dst_ctx* c, void* dst, const void* src, size_t bytes, int src_is_device) {
     if (src_is_device && dst == src) return DST_OK;              // dst_prove_sharded gathers straight into the landing buffer
     if (src_is_device) k_copy(c, dst, src, bytes);
@@ -78,8 +76,6 @@ static int copy_out(dst_ctx* c, void* dst, const void* src, size_t bytes, int ds
     HIP_TRY(c, hipStreamSynchronize(c->stream));
     return DST_OK;
 }
-
-extern "C" {
 
 // steps 1-2, local part: LDE of the owned cosets, their leaf digests and the local tree levels (down to one node per k)
 int dst_shard_commit_trace(dst_ctx* c) {
@@ -111,69 +107,25 @@ int dst_shard_commit_trace(dst_ctx* c) {
 }
 
 // step 3, local part: AIR evaluation on the owned evaluation cosets.  *bad_step = first failing trace step seen by this rank (-1: none)
-static int shard_eval_constraints(dst_ctx* c, const dst_public* pub, const uint8_t* coeffs, int64_t* bad_step, bool defer_check);
-int dst_shard_eval_constraints(dst_ctx* c, const dst_public* pub, const uint8_t* coeffs, int64_t* bad_step) { return shard_eval_constraints(c, pub, coeffs, bad_step, false); }
-// defer_check: the host does not wait for the verdict; the failing step (device word c->d_u64, ~0 = none) is picked up later
-static int shard_eval_constraints(dst_ctx* c, const dst_public* pub, const uint8_t* coeffs, int64_t* bad_step, bool defer_check) {
+int dst_shard_eval_constraints(dst_ctx* c, const dst_public* pub, const uint8_t* coeffs, int64_t* bad_step) {
     if (!c || !pub || !coeffs) return DST_ERR_ARG;
     if (!c->committed) { c->err = "dst_shard_eval_constraints: trace not committed"; return DST_ERR_STATE; }
     HIP_TRY(c, hipSetDevice(c->device));
-    c->pub = *pub;
-    std::vector<fe> draws(344), tc;
-    memcpy(draws.data(), coeffs, 344 * 16);
-    c->shard_draws = draws;                                  // dst_shard_combine builds the boundary polynomials from them
-    dst_internal_transition_coefficients(c, draws.data(), tc);
-    fe* d_coef = c->scratch + c->scratch_elems - 1024;
-    fe* d_tc = d_coef + 344;
-    if (int ru = dst_internal_upload_draws(c, draws.data(), tc, d_coef, d_tc)) return ru;
-    int r = k_eval_constraints(c, d_coef, d_tc, bad_step, defer_check);
-    if (r == DST_ERR_AIR) c->err = "transition constraints were not satisfied";
-    return r;
+    return step::eval_constraints(c, pub, coeffs, bad_step, /*defer_check=*/false);
 }
 
 // steps 4-5 after the constraint evaluations of all ranks were imported (SH_CEVAL): combination (replicated), LDE of the owned
 // cosets and the local levels of the constraint tree
-// parts: 1 = the two boundary combinations and their divisions (need nothing from other ranks), 2 = transition part, sum, extension over
-// the owned cosets and the local tree levels.  dst_prove_sharded runs part 1 while the exchange of the evaluations is in flight.
+// parts: as step::combine; part 2 goes on to the extension over the owned cosets and the local tree levels.  dst_prove_sharded runs
+// part 1 while the exchange of the evaluations is in flight.
 static int shard_combine_parts(dst_ctx* c, int parts) {
-    const size_t n = c->n, D = 8 * n;
-    fe* ip = c->cwork; fe* fp = c->cwork + D; fe* tp = c->cwork + 2 * D; fe* work = c->cwork + 3 * D;
-    const bool steps = dst_internal_combine_by_steps(c);         // the reference's sequence of whole-array steps (tests), else the fused pass of the single-GPU path
-    fe* q4 = c->cwork; const size_t qs = n + 16;
-    if (parts & 1) {
-        if (!steps) {
-            int rb = dst_internal_boundary_quotients(c, c->shard_draws.data(), q4, qs);
-            if (rb) return rb;
-        } else {
-            if (dst_internal_boundary_by_evaluation(c)) {
-                k_intt8_cosets(c, c->ceval, ip, work);
-                k_intt8_cosets(c, c->ceval + D, fp, work);
-            } else {
-                int rb = dst_internal_boundary_polys(c, c->shard_draws.data(), ip, fp);
-                if (rb) return rb;
-            }
-            k_syn_div(c, ip, D, fe_one());
-            k_syn_div(c, fp, D, c->x_last);
-        }
-    }
+    if (int r = step::combine(c, parts)) return r;
     if (parts & 2) {
-        if (!steps) {
-            const fe* inv = c->ceval + 2 * D;                   // already inverse-transformed per coset by its owner (dst_prove_sharded) ...
-            if (!c->ceval_inverted) { k_intt_cosets_local(c, c->ceval + 2 * D, work, 8); inv = work; }      // ... or not (host-orchestrated path)
-            c->ceval_inverted = false;
-            k_combine_fused(c, inv, q4, qs, c->cpoly);
-        } else {
-            if (c->ceval_inverted) { k_cross8(c, c->ceval + 2 * D, tp); c->ceval_inverted = false; }
-            else k_intt8_cosets(c, c->ceval + 2 * D, tp, work);
-            k_syn_div_expanded(c, tp, c->cpoly, D, n, c->x_last);
-            k_add(c, c->cpoly, ip, D);
-            k_add(c, c->cpoly, fp, D);
-        }
         if (c->wait_comm && c->sh_ev[4]) (void)hipEventRecord(c->sh_ev[4], c->stream);      // dst_prove_sharded: end of the combination (phase 3 | 4)
         k_lde_fold8(c, c->cpoly, c->cevals);
         if (c->Bc >= 4) {                                   // with two cosets per rank the leaves themselves are the boundary (see dst_shard_export)
             k_constraint_level1(c);
-            k_merkle_local_levels(c, c->cnodes, c->Bc * n / 4, n);
+            k_merkle_local_levels(c, c->cnodes, c->Bc * c->n / 4, c->n);
         }
         c->constraints_done = true; c->composed = false;
     }
@@ -181,7 +133,7 @@ static int shard_combine_parts(dst_ctx* c, int parts) {
 }
 int dst_shard_combine(dst_ctx* c) {
     if (!c) return DST_ERR_ARG;
-    if (!c->committed || c->shard_draws.size() != 344) { c->err = "dst_shard_combine: constraints not evaluated (dst_shard_eval_constraints first)"; return DST_ERR_STATE; }
+    if (!c->committed || c->air_draws.size() != 344) { c->err = "dst_shard_combine: constraints not evaluated (dst_shard_eval_constraints first)"; return DST_ERR_STATE; }
     HIP_TRY(c, hipSetDevice(c->device));
     int r = shard_combine_parts(c, 3);
     if (r) return r;
@@ -198,12 +150,9 @@ int dst_shard_fri_layer(dst_ctx* c, int* more) {
     if (d >= c->num_fri_layers || d != c->fri_folded) { c->err = "dst_shard_fri_layer: fold the previous layer first"; return DST_ERR_STATE; }
     if (d >= c->fri_rep_from) { c->err = "dst_shard_fri_layer: this layer is part of the replicated tail (dst_shard_fri_begin / dst_shard_fri_end)"; return DST_ERR_STATE; }
     HIP_TRY(c, hipSetDevice(c->device));
-    size_t nd = fri_nd(c, d), nb = nd / 4;
-    k_fri_leaves_cm(c, c->fri_e[d], c->fri_leaves[d], nd);
-    k_merkle_levels_to(c, c->fri_leaves[d], c->fri_nodes[d], nb * c->Bc, nb);
+    step::fri_shard_layer(c, d);
     HIP_TRY(c, hipStreamSynchronize(c->stream));
     HIP_TRY(c, hipGetLastError());
-    c->fri_committed = d + 1;
     *more = (d + 1 < c->num_fri_layers) ? 1 : 0;
     return DST_OK;
 }
@@ -212,8 +161,7 @@ int dst_shard_fri_fold(dst_ctx* c, const uint8_t special_x[16]) {
     int d = c->fri_folded;
     if (d + 1 != c->fri_committed || d + 1 >= c->num_fri_layers) { c->err = "dst_shard_fri_fold: nothing to fold"; return DST_ERR_STATE; }
     HIP_TRY(c, hipSetDevice(c->device));
-    k_fri_fold_cm(c, c->fri_e[d], c->fri_e[d + 1], fri_nd(c, d), d, fe_from_bytes(special_x));
-    c->fri_folded = d + 1;
+    step::fri_shard_fold(c, d, fe_from_bytes(special_x));
     return DST_OK;
 }
 
@@ -295,7 +243,7 @@ int dst_shard_import(dst_ctx* c, uint32_t what, uint32_t arg, const void* src, i
     HIP_TRY(c, hipGetLastError());
     if (what == SH_TRACE_TREE) memcpy(c->trace_root, root, 32);
     else if (what == SH_CONSTRAINT_TREE) memcpy(c->constraint_root, root, 32);
-    else { if (c->fri_roots.size() <= arg) c->fri_roots.resize(arg + 1); c->fri_roots[arg].assign(root, root + 32); }
+    else step::fri_file_root(c, (int)arg, root);
     if (root_out) memcpy(root_out, root, 32);
     return DST_OK;
 }
@@ -370,43 +318,12 @@ int dst_shard_fri_begin(dst_ctx* c, void* send, int send_is_device, size_t cap, 
 }
 // commit phase of the replicated tail (fri/prover.rs:11-53 from layer d0 on): every rank on its own, natural order
 static int fri_replicated_tail(dst_ctx* c, const void* gathered, int src_is_device, uint8_t root_out[32]) {
-    const int d0 = c->fri_rep_from, L = c->num_fri_layers;
-    const size_t size0 = c->fri_size[d0];
-    int r = copy_in(c, c->gather_buf, gathered, size0 * 16, src_is_device);            // rank-major pieces = coset-major [B][nd]
+    const int d0 = c->fri_rep_from;
+    int r = copy_in(c, c->gather_buf, gathered, c->fri_size[d0] * 16, src_is_device);            // rank-major pieces = coset-major [B][nd]
     if (r) return r;
-    fe* nat0 = d0 == 0 ? c->fri_nat0 : c->fri_e[d0];
-    k_coset_to_natural_len(c, (const fe*)c->gather_buf, c->B, fri_nd(c, d0), nat0);
-    if (c->fri_roots.size() < (size_t)L) c->fri_roots.resize(L);
-    const char* tail_env = c->sw("DISTAFF_FRI_TAIL");
-    // layers above the single-launch tail: no host round trip per layer -- x = prng(root) is drawn on the device (fri_draw_kernel) and the
-    // fold reads it there; their roots come back with the tail's (as in dst_prove's commit phase, api.hip)
-    digest* d_roots = reinterpret_cast<digest*>(c->d_fri_chain);
-    fe* d_alpha = reinterpret_cast<fe*>(c->d_fri_chain + DST_MAX_FRI_LAYERS * 32);
-    uint8_t* h_roots = c->h_stage + HS_FRI_ROOTS;
-    int d = d0;
-    for (; d < L; d++) {
-        if (d >= 1 && c->fri_size[d] <= ((size_t)1 << 13) && !(tail_env && tail_env[0] == '0')) break;
-        const size_t R = c->fri_size[d] / 4;
-        const fe* e = fri_layer_natural(c, d);
-        k_fri_leaves_at(c, e, c->fri_leaves[d], R);
-        k_merkle_levels(c, c->fri_leaves[d], c->fri_nodes[d], R);
-        k_fri_draw(c, d, d_alpha + d, d_roots + d);
-        if (d + 1 < L) k_fri_fold_at(c, e, c->fri_e[d + 1], R, d, fe_zero(), d_alpha + d);
-    }
-    if (d > d0) HIP_TRY(c, hipMemcpyAsync(h_roots, d_roots + d0, (size_t)(d - d0) * 32, hipMemcpyDeviceToHost, c->stream));
-    if (d < L) {
-        // the small layers in one launch (k_fri_tail, as on a single GPU): the layer's evaluations are in fri_e[d] in natural order
-        std::vector<uint8_t> rs((size_t)(L - d) * 32);
-        int rt = k_fri_tail(c, d, rs.data());                   // synchronises the stream
-        if (rt) return rt;
-        for (int i = d; i < L; i++) c->fri_roots[i].assign(rs.begin() + 32 * (i - d), rs.begin() + 32 * (i - d + 1));
-    } else {
-        CTX_SYNC(c, "the gathered FRI layer");
-        HIP_TRY(c, hipGetLastError());
-    }
-    for (int i = d0; i < d; i++) c->fri_roots[i].assign(h_roots + 32 * (i - d0), h_roots + 32 * (i - d0 + 1));
+    k_coset_to_natural_len(c, (const fe*)c->gather_buf, c->B, fri_nd(c, d0), fri_layer_natural(c, d0));
+    if ((r = step::fri_commit_natural(c, d0))) return r;
     if (root_out) memcpy(root_out, c->fri_roots[d0].data(), 32);
-    c->fri_committed = L; c->fri_folded = L - 1;
     c->fri_tail_pending = false;
     return DST_OK;
 }
@@ -608,7 +525,7 @@ static int gather_requests(dst_ctx* c, const OpenPlan& p, int me, bool everythin
 }
 
 // single-GPU dst_build_proof (api.hip): one plan, every item local
-int dst_internal_build_proof(dst_ctx* c, const uint64_t* positions, uint32_t num_positions, uint64_t pow_nonce, std::vector<uint8_t>& proof) {
+int build_proof_local(dst_ctx* c, const uint64_t* positions, uint32_t num_positions, uint64_t pow_nonce, std::vector<uint8_t>& proof) {
     OpenPlan p;
     int rc = build_open_plan(c, positions, num_positions, pow_nonce, p);
     if (rc) return rc;
@@ -742,13 +659,13 @@ struct Sharded {
     int rc = DST_OK;                       // this rank's own status: sticky, skips its local steps
     int agreed = DST_OK;                   // first failing rank's code once an exchange has shown one
     // a rank-local step; collectives are issued regardless (see above)
-    void local(const std::function<int()>& f) { if (rc == DST_OK) { rc = f(); } }           // (this file's functions sit in an extern "C" block: no member templates)
+    template <class F> void local(F&& f) { if (rc == DST_OK) { rc = f(); } }
     // host time inside the transport's calls (an enqueue on a stream-ordered transport, the whole exchange on a blocking one)
-    int timed(const std::function<int()>& f) { const double t = wall_ms_shard(); const int r = f(); c->shard_ms[0] += wall_ms_shard() - t; return r; }
+    template <class F> int timed(F&& f) { const double t = wall_ms(); const int r = f(); c->shard_ms[0] += wall_ms() - t; return r; }
     // ... and, for a collective on device buffers, two events around it on the stream it is queued on: enqueue -> completion as the device
     // saw it (on RCCL that includes the wait for the slowest peer), read once after the proof's last wait (dst_shard_exchange_ms).
     // kind: index into dst_ctx::exchange_ms (0 coefficients, 1 tree all-to-all, 2 tree all-gather, 3 constraint evaluations, 4 FRI tail)
-    int coll_on(int kind, hipStream_t stream, const std::function<int()>& f) {
+    template <class F> int coll_on(int kind, hipStream_t stream, F&& f) {
         dst_ctx::CollEv* ev = nullptr;
         if (c->coll_used < c->coll_ev.size()) ev = &c->coll_ev[c->coll_used];
         else if (c->coll_ev.size() < 256) {
@@ -763,12 +680,11 @@ struct Sharded {
         return r;
     }
     // all-gather of host values: complete on return, host wall time
-    int coll_host(const std::function<int()>& f) { const double t = wall_ms_shard(); const int r = timed(f); c->exchange_ms[5] += wall_ms_shard() - t; c->exchange_ms[6] += 1; return r; }
+    template <class F> int coll_host(F&& f) { const double t = wall_ms(); const int r = timed(f); c->exchange_ms[5] += wall_ms() - t; c->exchange_ms[6] += 1; return r; }
     void read_collective_events() {
         for (size_t i = 0; i < c->coll_used; i++) {
-            float ms = 0;
-            if (hipEventElapsedTime(&ms, c->coll_ev[i].e0, c->coll_ev[i].e1) == hipSuccess) { c->exchange_ms[c->coll_ev[i].kind] += ms; c->exchange_ms[7] += 1; }
-            else (void)hipGetLastError();
+            const double ms = event_ms(c->coll_ev[i].e0, c->coll_ev[i].e1);
+            if (ms >= 0) { c->exchange_ms[c->coll_ev[i].kind] += ms; c->exchange_ms[7] += 1; }
         }
     }
     void fail(int code, const std::string& msg) { if (rc == DST_OK) { rc = code; c->err = msg; } }
@@ -850,7 +766,7 @@ void tree_exchange(Sharded& S, uint32_t what, uint32_t arg, uint8_t root[32], co
         if (!okd) S.fail(DST_ERR_HIP, "tree_exchange: read-back could not be queued");
         return;
     }
-    const double t_wait = wall_ms_shard();
+    const double t_wait = wall_ms();
     // into PAGE-LOCKED memory: a copy into pageable memory would make the host wait inside hipMemcpyAsync for everything queued before it --
     // the exchange included -- without any bound (found by the stalled-collective test over the stream-ordered in-process transport)
     uint8_t* const host = c->h_stage + HS_TREE_READBACK;
@@ -860,7 +776,7 @@ void tree_exchange(Sharded& S, uint32_t what, uint32_t arg, uint8_t root[32], co
     // exchange would otherwise hold this rank for ever); on expiry the communicator is aborted and the rank returns DST_ERR_COMM
     const int rw = ok ? ctx_sync(c, what == SH_TRACE_TREE ? "the root of the trace tree" : what == SH_CONSTRAINT_TREE ? "the root of the constraint tree" : "the root of a FRI tree") : DST_ERR_HIP;
     ok = ok && rw == DST_OK && hipGetLastError() == hipSuccess;
-    c->shard_ms[1] += wall_ms_shard() - t_wait;
+    c->shard_ms[1] += wall_ms() - t_wait;
     if (!ok) { const int code = rw ? rw : DST_ERR_HIP; S.fail(code, rw ? c->err : std::string("tree_exchange: root read-back failed")); S.agreed = S.agreed ? S.agreed : code; return; }
     tree_exchange_finish(S, what, arg, host, payload_out, first_bad);
     if (root) memcpy(root, host + G * sizeof(TreeRec), 32);
@@ -880,7 +796,7 @@ void tree_exchange_finish(Sharded& S, uint32_t what, uint32_t arg, const uint8_t
     if (S.agreed) return;
     if (what == SH_TRACE_TREE) memcpy(c->trace_root, root, 32);
     else if (what == SH_CONSTRAINT_TREE) memcpy(c->constraint_root, root, 32);
-    else { if (c->fri_roots.size() <= arg) c->fri_roots.resize(arg + 1); c->fri_roots[arg].assign(root, root + 32); }
+    else step::fri_file_root(c, (int)arg, root);
 }
 
 // steps 1-2 up to the rank-local tree levels.  Interpolation is split by COLUMNS: rank g interpolates the registers r = g (mod G); the
@@ -968,17 +884,17 @@ int dst_prove_sharded(dst_ctx* c, dst_comm* comm, const dst_public* pub, uint8_t
     struct WaitScope { dst_ctx* c; ~WaitScope() { c->wait_comm = nullptr; } } wait_scope{c};
     c->wait_comm = comm;
     const size_t G = comm->world;
-    double t0 = wall_ms_shard();
+    double t0 = wall_ms();
     c->shard_ms[0] = c->shard_ms[1] = 0; c->shard_trees = 0;
     for (double& x : c->exchange_ms) x = 0;
     c->coll_used = 0;
-    auto mark = [&](int i) { const double t = wall_ms_shard(); c->phase_ms[i] = t - t0; t0 = t; };
+    auto mark = [&](int i) { const double t = wall_ms(); c->phase_ms[i] = t - t0; t0 = t; };
     // Phase boundaries are events on the stream (the reference's nine timings, prover.rs:28,36,66,74,87,103,112,134,167): the host only
     // ENQUEUES between two waits, so its own clock says nothing about where the device's time went.  sh_ev: 0 start, 1 end of the
     // extension, 2 / 3 around the constraint evaluation, 4 end of the combination.
     bool timed = true;
     for (int i = 0; i < 5 && timed; i++) if (!c->sh_ev[i] && hipEventCreate(&c->sh_ev[i]) != hipSuccess) { (void)hipGetLastError(); c->sh_ev[i] = nullptr; timed = false; }
-    auto ev_ms = [&](int a, int b) -> double { float ms = 0; if (timed && hipEventElapsedTime(&ms, c->sh_ev[a], c->sh_ev[b]) == hipSuccess) return ms; (void)hipGetLastError(); return -1.0; };
+    auto ev_ms = [&](int a, int b) { return timed ? event_ms(c->sh_ev[a], c->sh_ev[b]) : -1.0; };
     // steps 1-2.  Nothing waits for the extension on the host (the tree exchange is queued behind it)
     timed = timed && hipEventRecord(c->sh_ev[0], c->stream) == hipSuccess;
     commit_trace_columns(S);                                    // records sh_ev[1] behind the last extension launch
@@ -1000,7 +916,7 @@ int dst_prove_sharded(dst_ctx* c, dst_comm* comm, const dst_public* pub, uint8_t
     {
         // phase 0 = interpolation + extension (the stream's own clock up to sh_ev[1]), phase 1 = leaves, tree levels, the exchange and the
         // host's share: the rest of the wall time up to the root
-        const double now = wall_ms_shard(), both = now - t_commit, dev_ms = S.rc == DST_OK ? ev_ms(0, 1) : -1.0;
+        const double now = wall_ms(), both = now - t_commit, dev_ms = S.rc == DST_OK ? ev_ms(0, 1) : -1.0;
         if (dev_ms >= 0 && dev_ms < both) { c->phase_ms[0] = dev_ms; c->phase_ms[1] = both - dev_ms; }
         else { c->phase_ms[0] = 0; c->phase_ms[1] = both; }
         t0 = now;
@@ -1012,7 +928,7 @@ int dst_prove_sharded(dst_ctx* c, dst_comm* comm, const dst_public* pub, uint8_t
     // constraint tree's exchange below instead of a host exchange and a wait of its own -- a trace that fails is reported one phase later
     const double t_eval = t0;
     if (timed) (void)hipEventRecord(c->sh_ev[2], c->stream);
-    S.local([&] { return shard_eval_constraints(c, pub, (const uint8_t*)coef.data(), nullptr, true); });
+    S.local([&] { return step::eval_constraints(c, pub, (const uint8_t*)coef.data(), nullptr, /*defer_check=*/true); });
     if (timed) (void)hipEventRecord(c->sh_ev[3], c->stream);
     // steps 4-5: the transition evaluations of all ranks, then combination (replicated) and the constraint tree
     {
@@ -1052,7 +968,7 @@ int dst_prove_sharded(dst_ctx* c, dst_comm* comm, const dst_public* pub, uint8_t
         // phases 2 (constraint evaluation), 3 (combination incl. the exchange of the evaluations), 4 (extension of the constraint polynomial,
         // its tree, the tree exchange): the host queued all three without a wait, so they are split at the stream's events; what the host spent
         // before the first and after the last event goes to the outer phases, as in dst_eval_constraints
-        const double now = wall_ms_shard(), total = now - t_eval;
+        const double now = wall_ms(), total = now - t_eval;
         const double e1 = S.rc == DST_OK ? ev_ms(2, 3) : -1.0, e2 = S.rc == DST_OK ? ev_ms(3, 4) : -1.0;
         if (e1 >= 0 && e2 >= 0 && e1 + e2 <= total) { c->phase_ms[2] = e1; c->phase_ms[3] = e2; c->phase_ms[4] = total - e1 - e2; }
         else { c->phase_ms[2] = 0; c->phase_ms[3] = 0; c->phase_ms[4] = total; }
@@ -1078,10 +994,7 @@ int dst_prove_sharded(dst_ctx* c, dst_comm* comm, const dst_public* pub, uint8_t
     for (int d = 0; d < rep_from; d++) {
         S.local([&]() -> int {
             if (!c->composed || d != c->fri_committed || d != c->fri_folded) { c->err = "dst_prove_sharded: FRI layer out of order"; return DST_ERR_STATE; }
-            const size_t nd = fri_nd(c, d), nb = nd / 4;
-            k_fri_leaves_cm(c, c->fri_e[d], c->fri_leaves[d], nd);
-            k_merkle_levels_to(c, c->fri_leaves[d], c->fri_nodes[d], nb * c->Bc, nb);
-            c->fri_committed = d + 1;
+            step::fri_shard_layer(c, d);
             return DST_OK;
         });
         uint8_t root[32];
@@ -1090,8 +1003,7 @@ int dst_prove_sharded(dst_ctx* c, dst_comm* comm, const dst_public* pub, uint8_t
         if (chained) {
             S.local([&]() -> int {
                 k_fri_draw_at(c, c->fri_upper[d], d_alpha + d, d_roots + d);
-                k_fri_fold_cm(c, c->fri_e[d], c->fri_e[d + 1], fri_nd(c, d), d, fe_zero(), d_alpha + d);
-                c->fri_folded = d + 1;
+                step::fri_shard_fold(c, d, fe_zero(), d_alpha + d);
                 return DST_OK;
             });
         } else {
@@ -1113,9 +1025,9 @@ int dst_prove_sharded(dst_ctx* c, dst_comm* comm, const dst_public* pub, uint8_t
     if (chained && rep_from > 0) {
         // the deferred records of the sharded layers: everything queued has completed once the stream is idle (a rank that failed locally
         // did not run the tail's own wait)
-        const double t_wait = wall_ms_shard();
+        const double t_wait = wall_ms();
         { const int rw = ctx_sync(c, "the FRI layers"); if (rw) { S.fail(rw, c->err); if (rw == DST_ERR_COMM) return rw; } }
-        c->shard_ms[1] += wall_ms_shard() - t_wait;
+        c->shard_ms[1] += wall_ms() - t_wait;
         for (int d = 0; d < rep_from && !S.agreed; d++) tree_exchange_finish(S, SH_FRI_TREE, (uint32_t)d, slot_of(d), nullptr, nullptr);
         if (S.agreed) return S.agreed;
     }
@@ -1123,16 +1035,7 @@ int dst_prove_sharded(dst_ctx* c, dst_comm* comm, const dst_public* pub, uint8_t
     // step 8 (replicated: every rank grinds the same seed and finds the same first nonce)
     uint64_t nonce = 0;
     std::vector<uint64_t> positions;
-    S.local([&]() -> int {
-        std::vector<uint8_t> roots;
-        for (int d = 0; d < c->num_fri_layers; d++) roots.insert(roots.end(), c->fri_roots[d].begin(), c->fri_roots[d].end());
-        uint8_t seed0[32], seed1[32];
-        if (!blake3_short(roots.data(), roots.size(), seed0)) { c->err = "too many FRI roots"; return DST_ERR_ARG; }
-        int r = dst_pow_grind(c, seed0, c->prm.grinding_factor, seed1, &nonce);
-        if (r) return r;
-        if (query_positions(seed1, c->N, (uint32_t)c->B, c->prm.num_queries, positions)) { c->err = "could not generate enough query positions"; return DST_ERR_ARG; }
-        return DST_OK;
-    });
+    S.local([&] { return step::query_seed(c, &nonce, positions); });
     mark(7);
     // step 9: the lengths of the ranks' opening blobs travel with their status
     std::vector<uint64_t> lens(G, 0);
@@ -1194,4 +1097,3 @@ int dst_prove_sharded_local(dst_ctx** ctxs, uint32_t world, const dst_public* pu
     return DST_OK;
 }
 
-}  // extern "C"

@@ -387,3 +387,7 @@ int k_field_op(dst_ctx* c, int op, const uint8_t* a, const uint8_t* b, uint8_t* 
 // Rescue digests / trees (kernels_hash.hip, rescue_dev.h): no context, the caller's stream; -1 when a launch fails; *bad = 1 for an input element >= p
 int k_rescue_digests(hipStream_t stream, const fe* in /* 4 per digest */, fe* out /* 2 per digest */, size_t count, uint32_t* bad);
 int k_rescue_tree(hipStream_t stream, fe* nodes /* 2 elements per node, leaf level in place */, size_t leaves, uint32_t* bad);
+// dirty parents only: level l (2^l parents) recomputes the cnt[l] node positions at lists[off[l] ..); cnt[l] == 2^l: the whole level, no list
+int k_rescue_tree_update(hipStream_t stream, fe* nodes, uint32_t log_leaves, const uint32_t* lists /* device */, const size_t* off, const size_t* cnt);
+int k_rescue_tree_scatter(hipStream_t stream, fe* nodes, const uint32_t* pos /* device */, const fe* vals /* 2 per node */, size_t count);   // nodes[pos[i]] = vals[i]
+int k_rescue_tree_gather(hipStream_t stream, const fe* nodes, const uint32_t* pos /* device */, fe* out /* 2 per node */, size_t count);       // out[i] = nodes[pos[i]]

@@ -57,7 +57,7 @@ EXPORTS = ["dst_ctx_create", "dst_ctx_destroy", "dst_last_error", "dst_phase_ms"
            "dst_comm_describe", "dst_comm_trace", "dst_test_hooks", "dst_comm_set_timeout", "dst_comm_abort", "dst_shard_exchange_ms", "dst_bench_clock",
            "dst_verify", "dst_proof_info",
            "dst_rescue_digest_many", "dst_rtree_build", "dst_rtree_root", "dst_rtree_path", "dst_rtree_tapes", "dst_rtree_read_nodes", "dst_rtree_build_ms",
-           "dst_rtree_destroy", "dst_rtree_last_error"]
+           "dst_rtree_destroy", "dst_rtree_last_error", "dst_rtree_update", "dst_rtree_update_ms", "dst_rtree_paths", "dst_rtree_tapes_many"]
 
 
 class DistaffError(RuntimeError):
@@ -330,6 +330,50 @@ class RescueTree:
         b = np.zeros((max(n.value, 1), 2), dtype=np.uint64)
         self._check(self.lib.dst_rtree_tapes(self._h, ctypes.c_uint64(index), ctypes.c_uint32(what), _ptr(a), _ptr(b), ctypes.c_size_t(n.value), ctypes.byref(n)))
         return arr_to_ints(a[:n.value]), arr_to_ints(b[:n.value])
+
+    @staticmethod
+    def _indices(indices):
+        idx = np.ascontiguousarray(np.array([int(i) for i in indices], dtype=np.uint64))
+        return idx, (_ptr(idx) if idx.size else None)
+
+    def update(self, indices, leaves):
+        """replaces the leaves at the distinct leaf indices `indices` (any order) by `leaves` (as many pairs of ints, or uint64 words
+        [count, 2, 2]) and recomputes their ancestors: the tree then equals one built from the modified leaves (dst_rtree_update).  A repeated
+        index, an index past the end or an element not below p raises DistaffError(DST_ERR_ARG) and leaves the tree as it was."""
+        idx, ip = self._indices(indices)
+        a = _elements(leaves, 2)
+        if a.shape[0] != idx.size:
+            raise DistaffError(DST_ERR_ARG, "as many leaves as indices")
+        self._check(self.lib.dst_rtree_update(self._h, ip, _ptr(a) if idx.size else None, ctypes.c_size_t(idx.size)))
+
+    @property
+    def update_ms(self):
+        """device milliseconds of the level launches of the last update (0 for a host tree)"""
+        ms = ctypes.c_double(0)
+        self._check(self.lib.dst_rtree_update_ms(self._h, ctypes.byref(ms)))
+        return ms.value
+
+    def paths(self, indices):
+        """authentication paths of the leaves `indices` (repeats allowed) in one call (dst_rtree_paths): a list with one path(i) per index, i.e.
+        count x (log_leaves + 1) x 2 elements"""
+        idx, ip = self._indices(indices)
+        n = self.log_leaves + 1
+        out = np.zeros((max(idx.size, 1) * n, 2, 2), dtype=np.uint64)
+        self._check(self.lib.dst_rtree_paths(self._h, ip, ctypes.c_size_t(idx.size), _ptr(out)))
+        v = arr_to_ints(out[:idx.size * n])
+        return [[(v[2 * (i * n + k)], v[2 * (i * n + k) + 1]) for k in range(n)] for i in range(idx.size)]
+
+    def tapes_many(self, indices, what=3):
+        """tapes(i, what) for every i of `indices` in one call (dst_rtree_tapes_many): a list of (A, B)"""
+        idx, ip = self._indices(indices)
+        n = ctypes.c_size_t(0)
+        self._check(self.lib.dst_rtree_tapes_many(self._h, ip, ctypes.c_size_t(idx.size), ctypes.c_uint32(what), None, None, ctypes.c_size_t(0), ctypes.byref(n)))
+        each = n.value
+        a = np.zeros((max(idx.size * each, 1), 2), dtype=np.uint64)
+        b = np.zeros((max(idx.size * each, 1), 2), dtype=np.uint64)
+        self._check(self.lib.dst_rtree_tapes_many(self._h, ip, ctypes.c_size_t(idx.size), ctypes.c_uint32(what), _ptr(a), _ptr(b), ctypes.c_size_t(each), ctypes.byref(n)))
+        va, vb = arr_to_ints(a[:idx.size * each]), arr_to_ints(b[:idx.size * each])
+        return [(va[i * each:(i + 1) * each], vb[i * each:(i + 1) * each]) for i in range(idx.size)]
 
     def nodes(self, first, count):
         """`count` nodes of the node array from `first` as uint64 words [count, 2, 2]: index 1 = root, [2^log_leaves, 2^(log_leaves+1)) = the leaves"""

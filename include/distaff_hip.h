@@ -170,6 +170,22 @@ DST_API int dst_rtree_read_nodes(const dst_rtree* t, uint64_t first, uint64_t co
  * around the launches -- without the allocation and the upload of the leaves, which a caller's clock around dst_rtree_build includes -- can only be
  * recorded here; tools/rescue_tree_time.py reports this figure, as dst_phase_ms does for the prover's steps. */
 DST_API int dst_rtree_build_ms(const dst_rtree* t, double* device_ms);
+/* A tree is not frozen.  dst_rtree_update replaces the leaves at `indices` (count distinct leaf indices, any order) by `leaves` (count * 32 bytes)
+ * and recomputes exactly the ancestors of those leaves -- the nodes compute_merkle_root (merkle.rs:112-145) visits from any of them -- level by
+ * level, at most count nodes per level; afterwards every node equals that of a tree built from the modified leaf array.  DST_ERR_ARG: a null
+ * pointer with count > 0, an index past the end, a repeated index, a leaf element not below p; all of it is checked on the host before anything
+ * is queued, so the tree is unchanged after DST_ERR_ARG.  count = 0: DST_OK, nothing happens.  A HIP error during the update leaves the tree
+ * unusable: dst_rtree_last_error says so, and every later call on it except dst_rtree_destroy and dst_rtree_last_error returns DST_ERR_STATE. */
+DST_API int dst_rtree_update(dst_rtree* t, const uint64_t* indices, const uint8_t* leaves, size_t count);
+/* device milliseconds of the level launches of the last dst_rtree_update (events on the library's stream, as dst_rtree_build_ms; 0 for a host tree) */
+DST_API int dst_rtree_update_ms(const dst_rtree* t, double* device_ms);
+/* authentication paths of `count` leaves, (log_leaves + 1) * 32 bytes each, in the order of `indices` (repeats allowed); the layout of each is
+ * dst_rtree_path's (merkle.rs:98-145).  On a device tree: one upload of the node positions, one gather launch, one copy back, whatever count is. */
+DST_API int dst_rtree_paths(const dst_rtree* t, const uint64_t* indices, size_t count, uint8_t* paths);
+/* dst_rtree_tapes (generate_program_inputs, merkle.rs:63-94) for `count` leaves: tape_a / tape_b receive count blocks of *elems_each elements,
+ * block i for indices[i]; cap_elems_each >= *elems_each; tape_a = tape_b = NULL: size query */
+DST_API int dst_rtree_tapes_many(const dst_rtree* t, const uint64_t* indices, size_t count, uint32_t what,
+                                 uint8_t* tape_a, uint8_t* tape_b, size_t cap_elems_each, size_t* elems_each);
 DST_API void dst_rtree_destroy(dst_rtree* t);
 DST_API const char* dst_rtree_last_error(const dst_rtree* t);     /* t may be NULL: the error of the calling thread's last failed dst_rtree_build / dst_rescue_digest_many */
 

@@ -2,6 +2,7 @@
 """Device time of Rescue Merkle trees (dst_rtree_build: events around the level launches), the host path on one core, and the bound the
 device's own modular-multiplication rate sets.
     python tools/rescue_tree_time.py [--host-log 12] [--lib path/to/another/build.so] [log_leaves ...]        (default 12 16 20)
+    python tools/rescue_tree_time.py --update        updates in place and batched openings on the 2^20 tree instead (dst_rtree_update_ms)
 One digest is counted as 9 180 field multiplications, the reference's own count per hasher::digest: ten rounds of 6 x 2 for the cubes, 6 x 139
 for x^INV_ALPHA by the addition chain (127 squarings + 12 multiplications) and 2 x 36 for the two MDS products."""
 import argparse
@@ -20,6 +21,7 @@ ap = argparse.ArgumentParser()
 ap.add_argument("--host-log", type=int, default=12, help="size of the host-path tree (one core); 0: skip")
 ap.add_argument("--lib", default=None, help="another build of the library (a different RESCUE_SPREAD_MAX)")
 ap.add_argument("--runs", type=int, default=5)
+ap.add_argument("--update", action="store_true", help="time dst_rtree_update (k = 1, 256, 65 536 leaves) and dst_rtree_paths on the 2^20 tree instead of builds")
 ap.add_argument("sizes", nargs="*", type=int)
 args = ap.parse_args()
 lib = D.lib._open(os.path.abspath(args.lib)) if args.lib else None       # through the binding: one HIP runtime per process
@@ -49,6 +51,46 @@ mul_rate = lanes * iters * 4 / (mul_ms * 1e-3)                       # four mult
 bound = mul_rate / MULS_PER_DIGEST
 print("dst_bench_mulmod: %.3e modular multiplications/s (%d lanes x %d iterations x 4 chains in %.3f ms) -> at most %.3e digests/s at %d multiplications per digest"
       % (mul_rate, lanes, iters, mul_ms, bound, MULS_PER_DIGEST))
+if args.update:
+    import ctypes
+    UPDATE_SEED, log_leaves = 2020, 20
+    a = leaves(log_leaves)
+    D.RescueTree(a, device=0, lib=lib).close()      # warm-up
+    t = D.RescueTree(a, device=0, lib=lib)
+    print("2^%d leaves: built in %.3f ms on the device (dst_rtree_build_ms of the tree the updates below run on)" % (log_leaves, t.build_ms))
+    rng = np.random.default_rng(UPDATE_SEED)
+    for k in (1, 256, 65536):
+        ms = []
+        for _ in range(1 + args.runs):              # the first is the warm-up: stream, staging buffer, code
+            idx = rng.permutation(1 << log_leaves)[:k].astype(np.uint64)
+            new = rng.integers(0, 1 << 64, size=(k, 2, 2), dtype=np.uint64)
+            new[..., 1] >>= np.uint64(1)
+            t.update(idx, new)
+            ms.append(t.update_ms)
+        ms = ms[1:]
+        root = t.root
+        print("update of %d leaves: %.3f ms on the device (min of %d after one warm-up; all: %s), %.1f x faster than the build, root %032x %032x"
+              % (k, min(ms), args.runs, " ".join("%.3f" % v for v in ms), t.build_ms / min(ms), root[0], root[1]))
+    count, n = 4096, log_leaves + 1
+    idx = rng.integers(0, 1 << log_leaves, size=count).astype(np.uint64)
+    t.paths(idx[:16])                               # warm-up
+    t0 = time.perf_counter(); many = t.paths(idx); s_many = time.perf_counter() - t0
+    t0 = time.perf_counter(); single = [t.path(int(i)) for i in idx]; s_single = time.perf_counter() - t0
+    assert many == single
+    print("paths() of %d indices: %.2f ms wall; %d calls of path(): %.2f ms wall (both with the binding's conversion to Python ints)" % (count, s_many * 1e3, count, s_single * 1e3))
+    out = np.zeros((count * n, 2, 2), dtype=np.uint64)   # the C calls alone
+    h, L = t._h, t.lib
+    t0 = time.perf_counter(); r = L.dst_rtree_paths(h, idx.ctypes.data_as(ctypes.c_void_p), ctypes.c_size_t(count), out.ctypes.data_as(ctypes.c_void_p)); c_many = time.perf_counter() - t0
+    one = np.zeros((n, 2, 2), dtype=np.uint64)
+    po = one.ctypes.data_as(ctypes.c_void_p)
+    t0 = time.perf_counter()
+    for i in idx.tolist():
+        r |= L.dst_rtree_path(h, ctypes.c_uint64(i), po)
+    c_single = time.perf_counter() - t0
+    assert r == 0 and np.array_equal(out[-n:], one)
+    print("dst_rtree_paths of %d indices: %.3f ms wall; %d calls of dst_rtree_path: %.2f ms wall (ctypes, no conversion): %.0f x" % (count, c_many * 1e3, count, c_single * 1e3, c_single / c_many))
+    t.close()
+    sys.exit(0)
 for log_leaves in args.sizes or [12, 16, 20]:
     a = leaves(log_leaves)
     D.RescueTree(a, device=0, lib=lib).close()      # warm-up

@@ -1,4 +1,5 @@
-// C-ABI of libdistaff_hip.so (include/distaff_hip.h): context, tables, the prover phases and proof assembly.
+// C-ABI of libdistaff_hip.so (include/distaff_hip.h): context, tables, the prover phases and proof assembly.  The verifier (verify/), the
+// shared prover steps (host/steps_impl.h) and the Rescue trees (host/rtree_impl.h) are host code compiled with this unit.
 // The phase order and every Fiat-Shamir dependency follow stark::prove (/root/reference/src/stark/prover.rs:17-168).
 #include <algorithm>
 #include <cstdio>
@@ -8,7 +9,6 @@
 #include "host_proof.h"
 #include "host_util.h"
 #include "host_vm.h"
-#include "host_rescue.h"
 #include "verify/host_verify.h"
 
 using namespace dsth;
@@ -725,344 +725,8 @@ int dst_proof_info(const uint8_t* proof, size_t len, dst_proof_info_t* info) {
     return DST_OK;
 }
 
-// ---- Rescue digests and Rescue Merkle trees (kernels_hash.hip / rescue_dev.h on the device, host_rescue.h on the host): no context ---------
-struct dst_rtree {
-    int device = -1;                      // < 0: the nodes live in `host`
-    uint32_t log_leaves = 0;
-    fe* dev = nullptr;                    // node array on the device: 2 elements per node, nodes[1] = root, nodes[leaves ..) = the leaves
-    std::vector<u128> host;
-    double device_ms = 0;                 // events around the level launches of the build
-    double update_ms = 0;                 // ... and of the last dst_rtree_update
-    bool broken = false;                  // a HIP error inside dst_rtree_update: the nodes are in an unknown state, only destroy / last_error remain
-    hipStream_t stream = nullptr;         // what updates and batched openings run on: stream, events and the staging buffer are created by the
-    hipEvent_t ev[2] = {nullptr, nullptr};        // first call that needs them and live as long as the tree
-    uint8_t* stage = nullptr; size_t stage_bytes = 0;
-    std::string err;
-};
-#define RT_LIVE(t) do { if ((t)->broken) return DST_ERR_STATE; } while (0)
-static thread_local std::string g_rtree_error;         // error of the calling thread's last failed call without a tree (dst_rtree_last_error(NULL))
-#define RT_HIP(errstr, expr, cleanup)                                                                \
-    do {                                                                                            \
-        hipError_t _e = (expr);                                                                     \
-        if (_e != hipSuccess) { (errstr) = std::string(#expr) + ": " + hipGetErrorString(_e); cleanup; return DST_ERR_HIP; } \
-    } while (0)
-static bool all_below_p(const uint8_t* p, size_t elems) {
-    for (size_t i = 0; i < elems; i++) { u128 v; memcpy(&v, p + 16 * i, 16); if (v >= FIELD_P) return false; }
-    return true;
-}
-
-// utils::hasher::digest (src/utils/hasher.rs:12)
-int dst_rescue_digest_many(int device, const uint8_t* in, size_t count, uint8_t* out) {
-    if ((!in || !out) && count) return DST_ERR_ARG;
-    if (count == 0) return DST_OK;
-    if (count > ((size_t)1 << 32)) return DST_ERR_ARG;
-    if (device < 0) {
-        if (!all_below_p(in, 4 * count)) { g_rtree_error = "an input element is not below the modulus"; return DST_ERR_ARG; }
-        try {
-            std::vector<u128> v(4 * count), d(2 * count);                  // the caller's buffers need only byte alignment
-            memcpy(v.data(), in, 64 * count);
-            rescue_digest_many_host(v.data(), count, d.data());
-            memcpy(out, d.data(), 32 * count);
-        } catch (const std::bad_alloc&) { g_rtree_error = "out of host memory"; return DST_ERR_HIP; }
-        return DST_OK;
-    }
-    fe *d_in = nullptr, *d_out = nullptr; uint32_t* d_bad = nullptr; hipStream_t st = nullptr;
-    auto cleanup = [&]() { if (d_in) hipFree(d_in); if (d_out) hipFree(d_out); if (d_bad) hipFree(d_bad); if (st) hipStreamDestroy(st); };
-    RT_HIP(g_rtree_error, hipSetDevice(device), cleanup());
-    RT_HIP(g_rtree_error, hipStreamCreateWithFlags(&st, hipStreamNonBlocking), cleanup());
-    RT_HIP(g_rtree_error, hipMalloc((void**)&d_in, count * 64), cleanup());
-    RT_HIP(g_rtree_error, hipMalloc((void**)&d_out, count * 32), cleanup());
-    RT_HIP(g_rtree_error, hipMalloc((void**)&d_bad, 4), cleanup());
-    RT_HIP(g_rtree_error, hipMemsetAsync(d_bad, 0, 4, st), cleanup());
-    RT_HIP(g_rtree_error, hipMemcpyAsync(d_in, in, count * 64, hipMemcpyHostToDevice, st), cleanup());
-    if (k_rescue_digests(st, d_in, d_out, count, d_bad)) { g_rtree_error = "rescue_digest_kernel: launch failed"; cleanup(); return DST_ERR_HIP; }
-    uint32_t bad = 0;
-    RT_HIP(g_rtree_error, hipMemcpyAsync(&bad, d_bad, 4, hipMemcpyDeviceToHost, st), cleanup());
-    RT_HIP(g_rtree_error, hipMemcpyAsync(out, d_out, count * 32, hipMemcpyDeviceToHost, st), cleanup());
-    RT_HIP(g_rtree_error, hipStreamSynchronize(st), cleanup());
-    cleanup();
-    if (bad) { g_rtree_error = "an input element is not below the modulus"; return DST_ERR_ARG; }
-    return DST_OK;
-}
-
-// the tree whose paths smpath / pmpath authenticate: parent = digest(l0, l1, r0, r1) (src/examples/merkle.rs:112-145)
-int dst_rtree_build(int device, const uint8_t* leaves, uint32_t log_leaves, dst_rtree** out) {
-    if (out) *out = nullptr;
-    if (!leaves || !out || log_leaves < 1 || log_leaves > 26) { g_rtree_error = "invalid argument (1 <= log_leaves <= 26)"; return DST_ERR_ARG; }
-    const size_t n = (size_t)1 << log_leaves;
-    dst_rtree* t = new (std::nothrow) dst_rtree;
-    if (!t) { g_rtree_error = "out of host memory"; return DST_ERR_HIP; }
-    t->device = device < 0 ? -1 : device; t->log_leaves = log_leaves;
-    if (device < 0) {
-        if (!all_below_p(leaves, 2 * n)) { g_rtree_error = "a leaf element is not below the modulus"; delete t; return DST_ERR_ARG; }
-        try { t->host.assign(4 * n, 0); } catch (const std::bad_alloc&) { g_rtree_error = "out of host memory"; delete t; return DST_ERR_HIP; }
-        memcpy(t->host.data() + 2 * n, leaves, 32 * n);
-        rescue_tree_host(t->host.data(), n);
-        *out = t;
-        return DST_OK;
-    }
-    uint32_t* d_bad = nullptr; hipStream_t st = nullptr; hipEvent_t e0 = nullptr, e1 = nullptr;
-    auto cleanup = [&]() { if (d_bad) hipFree(d_bad); if (st) hipStreamDestroy(st); if (e0) hipEventDestroy(e0); if (e1) hipEventDestroy(e1); };
-    auto fail = [&]() { cleanup(); if (t->dev) hipFree(t->dev); delete t; };
-    RT_HIP(g_rtree_error, hipSetDevice(device), fail());
-    RT_HIP(g_rtree_error, hipStreamCreateWithFlags(&st, hipStreamNonBlocking), fail());
-    RT_HIP(g_rtree_error, hipEventCreate(&e0), fail());
-    RT_HIP(g_rtree_error, hipEventCreate(&e1), fail());
-    RT_HIP(g_rtree_error, hipMalloc((void**)&t->dev, 64 * n), fail());
-    RT_HIP(g_rtree_error, hipMalloc((void**)&d_bad, 4), fail());
-    RT_HIP(g_rtree_error, hipMemsetAsync(d_bad, 0, 4, st), fail());
-    RT_HIP(g_rtree_error, hipMemsetAsync(t->dev, 0, 32, st), fail());                       // nodes[0] is not part of the tree
-    RT_HIP(g_rtree_error, hipMemcpyAsync(t->dev + 2 * n, leaves, 32 * n, hipMemcpyHostToDevice, st), fail());
-    RT_HIP(g_rtree_error, hipEventRecord(e0, st), fail());
-    if (k_rescue_tree(st, t->dev, n, d_bad)) { g_rtree_error = "rescue_tree_level_kernel: launch failed"; fail(); return DST_ERR_HIP; }
-    RT_HIP(g_rtree_error, hipEventRecord(e1, st), fail());
-    uint32_t bad = 0;
-    RT_HIP(g_rtree_error, hipMemcpyAsync(&bad, d_bad, 4, hipMemcpyDeviceToHost, st), fail());
-    RT_HIP(g_rtree_error, hipStreamSynchronize(st), fail());
-    float ms = 0;
-    RT_HIP(g_rtree_error, hipEventElapsedTime(&ms, e0, e1), fail());
-    t->device_ms = ms;
-    if (bad) { g_rtree_error = "a leaf element is not below the modulus"; fail(); return DST_ERR_ARG; }
-    cleanup();
-    *out = t;
-    return DST_OK;
-}
-void dst_rtree_destroy(dst_rtree* t) {
-    if (!t) return;
-    if (t->dev) {
-        (void)hipSetDevice(t->device); hipFree(t->dev);
-        if (t->stage) hipFree(t->stage);
-        if (t->ev[0]) hipEventDestroy(t->ev[0]);
-        if (t->ev[1]) hipEventDestroy(t->ev[1]);
-        if (t->stream) hipStreamDestroy(t->stream);
-    }
-    delete t;
-}
-const char* dst_rtree_last_error(const dst_rtree* t) { return t ? t->err.c_str() : g_rtree_error.c_str(); }
-int dst_rtree_build_ms(const dst_rtree* t, double* device_ms) {
-    if (!t) return DST_ERR_ARG;
-    RT_LIVE(t);
-    if (!device_ms) { const_cast<dst_rtree*>(t)->err = "null pointer"; return DST_ERR_ARG; }
-    *device_ms = t->device_ms;
-    return DST_OK;
-}
-// `count` nodes at the node-array positions pos[] -> out (32 bytes each)
-static int rtree_gather(const dst_rtree* ct, const uint64_t* pos, size_t count, uint8_t* out) {
-    dst_rtree* t = const_cast<dst_rtree*>(ct);
-    if (t->device < 0) { for (size_t k = 0; k < count; k++) memcpy(out + 32 * k, t->host.data() + 2 * pos[k], 32); return DST_OK; }
-    RT_HIP(t->err, hipSetDevice(t->device), (void)0);
-    for (size_t k = 0; k < count; k++) RT_HIP(t->err, hipMemcpy(out + 32 * k, t->dev + 2 * pos[k], 32, hipMemcpyDeviceToHost), (void)0);
-    return DST_OK;
-}
-int dst_rtree_read_nodes(const dst_rtree* t, uint64_t first, uint64_t count, uint8_t* out) {
-    if (!t) return DST_ERR_ARG;
-    RT_LIVE(t);
-    if (!out && count) { const_cast<dst_rtree*>(t)->err = "null pointer"; return DST_ERR_ARG; }
-    const uint64_t total = (uint64_t)2 << t->log_leaves;
-    if (first > total || count > total - first) { const_cast<dst_rtree*>(t)->err = "node range past the end of the node array"; return DST_ERR_ARG; }
-    if (count == 0) return DST_OK;
-    if (t->device < 0) { memcpy(out, t->host.data() + 2 * first, 32 * count); return DST_OK; }
-    RT_HIP(const_cast<dst_rtree*>(t)->err, hipSetDevice(t->device), (void)0);
-    RT_HIP(const_cast<dst_rtree*>(t)->err, hipMemcpy(out, t->dev + 2 * first, 32 * count, hipMemcpyDeviceToHost), (void)0);
-    return DST_OK;
-}
-int dst_rtree_root(const dst_rtree* t, uint8_t root[32]) {
-    if (!t) return DST_ERR_ARG;
-    RT_LIVE(t);
-    if (!root) { const_cast<dst_rtree*>(t)->err = "null pointer"; return DST_ERR_ARG; }
-    return dst_rtree_read_nodes(t, 1, 1, root);
-}
-int dst_rtree_path(const dst_rtree* t, uint64_t index, uint8_t* path) {
-    if (!t) return DST_ERR_ARG;
-    RT_LIVE(t);
-    if (!path) { const_cast<dst_rtree*>(t)->err = "null pointer"; return DST_ERR_ARG; }
-    if (index >> t->log_leaves) { const_cast<dst_rtree*>(t)->err = "leaf index past the end"; return DST_ERR_ARG; }
-    uint64_t pos[27];
-    rescue_path_positions(t->log_leaves, index, pos);
-    return rtree_gather(t, pos, t->log_leaves + 1, path);
-}
-// generate_program_inputs (src/examples/merkle.rs:63-94)
-int dst_rtree_tapes(const dst_rtree* t, uint64_t index, uint32_t what, uint8_t* tape_a, uint8_t* tape_b, size_t cap_elems, size_t* elems) {
-    if (!t) return DST_ERR_ARG;
-    RT_LIVE(t);
-    if (!elems || what < 1 || what > 3) { const_cast<dst_rtree*>(t)->err = "elems missing, or what outside 1..3"; return DST_ERR_ARG; }
-    const size_t n = t->log_leaves + 1;
-    *elems = ((what & 1u) ? 2 * n - 1 : 0) + ((what & 2u) ? n - 1 : 0);
-    if (!tape_a && !tape_b) {                                                              // size query
-        if (index >> t->log_leaves) { const_cast<dst_rtree*>(t)->err = "leaf index past the end"; return DST_ERR_ARG; }
-        return DST_OK;
-    }
-    if (!tape_a || !tape_b || cap_elems < *elems) { const_cast<dst_rtree*>(t)->err = "tape buffers missing or too small"; return DST_ERR_ARG; }
-    u128 path[2 * 27];
-    int r = dst_rtree_path(t, index, (uint8_t*)path);
-    if (r != DST_OK) return r;
-    try {
-        std::vector<u128> a, b;
-        rescue_tapes(path, n, index, what, a, b);
-        memcpy(tape_a, a.data(), 16 * a.size()); memcpy(tape_b, b.data(), 16 * b.size());
-    } catch (const std::bad_alloc&) { const_cast<dst_rtree*>(t)->err = "out of host memory"; return DST_ERR_HIP; }
-    return DST_OK;
-}
-
-// stream, events and at least `bytes` of device staging for an update or a batched opening
-static int rtree_stage(dst_rtree* t, size_t bytes) {
-    RT_HIP(t->err, hipSetDevice(t->device), (void)0);
-    if (!t->stream) RT_HIP(t->err, hipStreamCreateWithFlags(&t->stream, hipStreamNonBlocking), (void)0);
-    if (!t->ev[0]) RT_HIP(t->err, hipEventCreate(&t->ev[0]), (void)0);
-    if (!t->ev[1]) RT_HIP(t->err, hipEventCreate(&t->ev[1]), (void)0);
-    if (bytes > t->stage_bytes) {
-        if (t->stage) { hipFree(t->stage); t->stage = nullptr; t->stage_bytes = 0; }
-        RT_HIP(t->err, hipMalloc((void**)&t->stage, bytes), (void)0);
-        t->stage_bytes = bytes;
-    }
-    return DST_OK;
-}
-// a tree is not frozen: replaces leaves and recomputes their ancestors, the nodes that src/examples/merkle.rs:98-145 would read on the
-// way from any of these leaves to the root
-int dst_rtree_update(dst_rtree* t, const uint64_t* indices, const uint8_t* leaves, size_t count) {
-    if (!t) return DST_ERR_ARG;
-    RT_LIVE(t);
-    if (count == 0) return DST_OK;
-    if (!indices || !leaves) { t->err = "null pointer"; return DST_ERR_ARG; }
-    const uint32_t L = t->log_leaves;
-    const size_t n = (size_t)1 << L;
-    if (count > n) { t->err = "a leaf index is repeated"; return DST_ERR_ARG; }
-    try {
-        // everything is checked here, before the first node changes: O(count log count)
-        std::vector<uint32_t> cur(count);
-        for (size_t i = 0; i < count; i++) {
-            if (indices[i] >> L) { t->err = "leaf index past the end"; return DST_ERR_ARG; }
-            cur[i] = (uint32_t)indices[i];
-        }
-        std::sort(cur.begin(), cur.end());
-        if (std::adjacent_find(cur.begin(), cur.end()) != cur.end()) { t->err = "a leaf index is repeated"; return DST_ERR_ARG; }
-        if (!all_below_p(leaves, 2 * count)) { t->err = "a leaf element is not below the modulus"; return DST_ERR_ARG; }
-        if (t->device < 0) {
-            u128* nodes = t->host.data();
-            for (size_t i = 0; i < count; i++) memcpy(nodes + 2 * (n + indices[i]), leaves + 32 * i, 32);
-            for (uint32_t l = L; l-- > 0;) {                      // dirty parents of level l = unique(index >> (L - l)), sorted
-                for (auto& v : cur) v >>= 1;
-                cur.erase(std::unique(cur.begin(), cur.end()), cur.end());
-                const size_t base = (size_t)1 << l, m = cur.size();
-                u128 in[2][4], out[2][2];
-                size_t i = 0;
-                for (; i + 2 <= m; i += 2) {
-                    const size_t p0 = base + cur[i], p1 = base + cur[i + 1];
-                    memcpy(in[0], nodes + 4 * p0, 64); memcpy(in[1], nodes + 4 * p1, 64);
-                    rescue_digests_host<2>(in, out);
-                    memcpy(nodes + 2 * p0, out[0], 32); memcpy(nodes + 2 * p1, out[1], 32);
-                }
-                if (i < m) {
-                    const size_t p0 = base + cur[i];
-                    memcpy(in[0], nodes + 4 * p0, 64);
-                    rescue_digests_host<1>(in, out);
-                    memcpy(nodes + 2 * p0, out[0], 32);
-                }
-            }
-            return DST_OK;
-        }
-        // staging: the new leaves as given, their node positions, then the dirty lists of all levels -- one upload
-        size_t off[27] = {0}, cnt[27] = {0};
-        std::vector<uint32_t> words(count);
-        for (size_t i = 0; i < count; i++) words[i] = (uint32_t)(n + indices[i]);
-        for (uint32_t l = L; l-- > 0;) {
-            for (auto& v : cur) v >>= 1;
-            cur.erase(std::unique(cur.begin(), cur.end()), cur.end());
-            cnt[l] = cur.size();
-            if (cnt[l] == ((size_t)1 << l)) continue;            // the whole level (and every level above it): dense launch, no list
-            off[l] = words.size() - count;
-            for (uint32_t v : cur) words.push_back(((uint32_t)1 << l) + v);
-        }
-        const size_t total = 32 * count + 4 * words.size();
-        std::vector<uint8_t> up(total);
-        memcpy(up.data(), leaves, 32 * count);
-        memcpy(up.data() + 32 * count, words.data(), 4 * words.size());
-        auto dead = [&]() { t->broken = true; t->err += "; the update did not complete, the tree is unusable"; };
-        if (rtree_stage(t, total) != DST_OK) { dead(); return DST_ERR_HIP; }
-        const uint32_t* d_words = reinterpret_cast<const uint32_t*>(t->stage + 32 * count);
-        RT_HIP(t->err, hipMemcpyAsync(t->stage, up.data(), total, hipMemcpyHostToDevice, t->stream), dead());
-        if (k_rescue_tree_scatter(t->stream, t->dev, d_words, reinterpret_cast<const fe*>(t->stage), count)) { t->err = "rescue_tree_scatter_kernel: launch failed"; dead(); return DST_ERR_HIP; }
-        RT_HIP(t->err, hipEventRecord(t->ev[0], t->stream), dead());
-        if (k_rescue_tree_update(t->stream, t->dev, L, d_words + count, off, cnt)) { t->err = "rescue_tree_update_kernel: launch failed"; dead(); return DST_ERR_HIP; }
-        RT_HIP(t->err, hipEventRecord(t->ev[1], t->stream), dead());
-        RT_HIP(t->err, hipStreamSynchronize(t->stream), dead());
-        float ms = 0;
-        RT_HIP(t->err, hipEventElapsedTime(&ms, t->ev[0], t->ev[1]), dead());
-        t->update_ms = ms;
-    } catch (const std::bad_alloc&) { t->err = "out of host memory"; return DST_ERR_HIP; }      // thrown before anything was queued
-    return DST_OK;
-}
-int dst_rtree_update_ms(const dst_rtree* t, double* device_ms) {
-    if (!t) return DST_ERR_ARG;
-    RT_LIVE(t);
-    if (!device_ms) { const_cast<dst_rtree*>(t)->err = "null pointer"; return DST_ERR_ARG; }
-    *device_ms = t->update_ms;
-    return DST_OK;
-}
-// the paths of `count` leaves, (log_leaves + 1) nodes each -> out: on a device tree one upload of the positions, one gather launch, one copy back
-static int rtree_paths(const dst_rtree* ct, const uint64_t* indices, size_t count, uint8_t* out) {
-    dst_rtree* t = const_cast<dst_rtree*>(ct);
-    const size_t n = t->log_leaves + 1;
-    if (count > ((size_t)1 << 40)) { t->err = "too many indices"; return DST_ERR_ARG; }
-    for (size_t i = 0; i < count; i++) if (indices[i] >> t->log_leaves) { t->err = "leaf index past the end"; return DST_ERR_ARG; }
-    if (count == 0) return DST_OK;
-    uint64_t pos[27];
-    if (t->device < 0) {
-        for (size_t i = 0; i < count; i++) {
-            rescue_path_positions(t->log_leaves, indices[i], pos);
-            for (size_t k = 0; k < n; k++) memcpy(out + 32 * (i * n + k), t->host.data() + 2 * pos[k], 32);
-        }
-        return DST_OK;
-    }
-    const size_t m = count * n;
-    try {
-        std::vector<uint32_t> where(m);
-        for (size_t i = 0; i < count; i++) {
-            rescue_path_positions(t->log_leaves, indices[i], pos);
-            for (size_t k = 0; k < n; k++) where[i * n + k] = (uint32_t)pos[k];
-        }
-        int r = rtree_stage(t, 36 * m);                           // [m nodes][m positions]
-        if (r != DST_OK) return r;
-        uint32_t* d_where = reinterpret_cast<uint32_t*>(t->stage + 32 * m);
-        RT_HIP(t->err, hipMemcpyAsync(d_where, where.data(), 4 * m, hipMemcpyHostToDevice, t->stream), (void)0);
-        if (k_rescue_tree_gather(t->stream, t->dev, d_where, reinterpret_cast<fe*>(t->stage), m)) { t->err = "rescue_tree_gather_kernel: launch failed"; return DST_ERR_HIP; }
-        RT_HIP(t->err, hipMemcpyAsync(out, t->stage, 32 * m, hipMemcpyDeviceToHost, t->stream), (void)0);
-        RT_HIP(t->err, hipStreamSynchronize(t->stream), (void)0);
-    } catch (const std::bad_alloc&) { t->err = "out of host memory"; return DST_ERR_HIP; }
-    return DST_OK;
-}
-int dst_rtree_paths(const dst_rtree* t, const uint64_t* indices, size_t count, uint8_t* paths) {
-    if (!t) return DST_ERR_ARG;
-    RT_LIVE(t);
-    if ((!indices || !paths) && count) { const_cast<dst_rtree*>(t)->err = "null pointer"; return DST_ERR_ARG; }
-    return rtree_paths(t, indices, count, paths);
-}
-// generate_program_inputs (src/examples/merkle.rs:63-94) for many leaves
-int dst_rtree_tapes_many(const dst_rtree* t, const uint64_t* indices, size_t count, uint32_t what, uint8_t* tape_a, uint8_t* tape_b, size_t cap_elems_each, size_t* elems_each) {
-    if (!t) return DST_ERR_ARG;
-    RT_LIVE(t);
-    if (!elems_each || what < 1 || what > 3) { const_cast<dst_rtree*>(t)->err = "elems_each missing, or what outside 1..3"; return DST_ERR_ARG; }
-    if (!indices && count) { const_cast<dst_rtree*>(t)->err = "null pointer"; return DST_ERR_ARG; }
-    const size_t n = t->log_leaves + 1;
-    const size_t each = ((what & 1u) ? 2 * n - 1 : 0) + ((what & 2u) ? n - 1 : 0);
-    *elems_each = each;
-    if (!tape_a && !tape_b) {                                                              // size query
-        for (size_t i = 0; i < count; i++) if (indices[i] >> t->log_leaves) { const_cast<dst_rtree*>(t)->err = "leaf index past the end"; return DST_ERR_ARG; }
-        return DST_OK;
-    }
-    if (!tape_a || !tape_b || cap_elems_each < each) { const_cast<dst_rtree*>(t)->err = "tape buffers missing or too small"; return DST_ERR_ARG; }
-    try {
-        std::vector<u128> paths(2 * n * count);
-        int r = rtree_paths(t, indices, count, (uint8_t*)paths.data());
-        if (r != DST_OK) return r;
-        std::vector<u128> a, b;
-        for (size_t i = 0; i < count; i++) {
-            rescue_tapes(paths.data() + 2 * n * i, n, indices[i], what, a, b);
-            memcpy(tape_a + 16 * each * i, a.data(), 16 * each); memcpy(tape_b + 16 * each * i, b.data(), 16 * each);
-        }
-    } catch (const std::bad_alloc&) { const_cast<dst_rtree*>(t)->err = "out of host memory"; return DST_ERR_HIP; }
-    return DST_OK;
-}
+// ---- Rescue digests and Rescue Merkle trees (dst_rescue_digest_many, dst_rtree_*): no context, compiled with this unit ---------------------
+#include "host/rtree_impl.h"
 
 // ---- inspection --------------------------------------------------------------------------------------------------------------------
 int dst_read_buffer(dst_ctx* c, uint32_t what, uint32_t arg, uint8_t* out, size_t cap, size_t* len) {

@@ -1,0 +1,307 @@
+// Rescue digests and Rescue Merkle trees behind dst_rescue_digest_many / dst_rtree_* (kernels_hash.hip and rescue_dev.h on the device,
+// host_rescue.h on the host): the implementation, included by api.hip alone.  Host code, and no prover context: a device tree owns its stream.
+#pragma once
+#include <algorithm>
+#include <memory>
+#include "../ctx.h"
+#include "../host_rescue.h"
+
+struct dst_rtree {
+    int device = -1;                      // < 0: the nodes live in `host`
+    uint32_t log_leaves = 0;
+    fe* dev = nullptr;                    // node array on the device: 2 elements per node, nodes[1] = root, nodes[leaves ..) = the leaves
+    std::vector<u128> host;
+    double device_ms = 0;                 // events around the level launches of the build
+    double update_ms = 0;                 // ... and of the last dst_rtree_update
+    bool broken = false;                  // a HIP error inside dst_rtree_update: the nodes are in an unknown state, only destroy / last_error remain
+    // what the build, the updates and the openings of a device tree run on: rtree_stage creates the stream and the events with the build and
+    // grows the staging buffer as calls need it (openings of a const tree too, hence mutable); they live as long as the tree
+    mutable hipStream_t stream = nullptr;
+    mutable hipEvent_t ev[2] = {nullptr, nullptr};
+    mutable uint8_t* stage = nullptr; mutable size_t stage_bytes = 0;
+    mutable std::string err;
+    ~dst_rtree() {
+        if (device < 0) return;
+        (void)hipSetDevice(device);
+        if (dev) hipFree(dev);
+        if (stage) hipFree(stage);
+        for (hipEvent_t e : ev) if (e) hipEventDestroy(e);
+        if (stream) hipStreamDestroy(stream);
+    }
+};
+static thread_local std::string g_rtree_error;         // error of the calling thread's last failed call without a tree (dst_rtree_last_error(NULL))
+#define RT_HIP(errstr, expr)                                                                                              \
+    do {                                                                                                                   \
+        hipError_t _e = (expr);                                                                                            \
+        if (_e != hipSuccess) { (errstr) = std::string(#expr) + ": " + hipGetErrorString(_e); return DST_ERR_HIP; }       \
+    } while (0)
+// how every call on a tree begins, and how it files an error
+static int rt_enter(const dst_rtree* t) { return !t ? DST_ERR_ARG : t->broken ? DST_ERR_STATE : DST_OK; }
+static int rt_fail(const dst_rtree* t, int code, const char* why) { t->err = why; return code; }
+static bool all_below_p(const uint8_t* p, size_t elems) {
+    for (size_t i = 0; i < elems; i++) { u128 v; memcpy(&v, p + 16 * i, 16); if (v >= FIELD_P) return false; }
+    return true;
+}
+static bool all_leaf_indices(const dst_rtree* t, const uint64_t* indices, size_t count) {
+    for (size_t i = 0; i < count; i++) if (indices[i] >> t->log_leaves) return false;
+    return true;
+}
+struct rt_scratch {                                    // the stream and the device buffer of a call without a tree
+    hipStream_t s = nullptr; uint8_t* p = nullptr;
+    ~rt_scratch() { if (p) hipFree(p); if (s) hipStreamDestroy(s); }
+};
+
+// utils::hasher::digest (src/utils/hasher.rs:12)
+int dst_rescue_digest_many(int device, const uint8_t* in, size_t count, uint8_t* out) {
+    if ((!in || !out) && count) return DST_ERR_ARG;
+    if (count == 0) return DST_OK;
+    if (count > ((size_t)1 << 32)) return DST_ERR_ARG;
+    if (device < 0) {
+        if (!all_below_p(in, 4 * count)) { g_rtree_error = "an input element is not below the modulus"; return DST_ERR_ARG; }
+        try {
+            std::vector<u128> v(4 * count), d(2 * count);                  // the caller's buffers need only byte alignment
+            memcpy(v.data(), in, 64 * count);
+            rescue_digest_many_host(v.data(), count, d.data());
+            memcpy(out, d.data(), 32 * count);
+        } catch (const std::bad_alloc&) { g_rtree_error = "out of host memory"; return DST_ERR_HIP; }
+        return DST_OK;
+    }
+    rt_scratch h;                                                          // p = [count inputs][count digests][bad]
+    RT_HIP(g_rtree_error, hipSetDevice(device));
+    RT_HIP(g_rtree_error, hipStreamCreateWithFlags(&h.s, hipStreamNonBlocking));
+    RT_HIP(g_rtree_error, hipMalloc((void**)&h.p, count * 96 + 4));
+    fe *d_in = reinterpret_cast<fe*>(h.p), *d_out = d_in + 4 * count;
+    uint32_t *d_bad = reinterpret_cast<uint32_t*>(h.p + count * 96), bad = 0;
+    RT_HIP(g_rtree_error, hipMemsetAsync(d_bad, 0, 4, h.s));
+    RT_HIP(g_rtree_error, hipMemcpyAsync(d_in, in, count * 64, hipMemcpyHostToDevice, h.s));
+    if (k_rescue_digests(h.s, d_in, d_out, count, d_bad)) { g_rtree_error = "rescue_digest_kernel: launch failed"; return DST_ERR_HIP; }
+    RT_HIP(g_rtree_error, hipMemcpyAsync(&bad, d_bad, 4, hipMemcpyDeviceToHost, h.s));
+    RT_HIP(g_rtree_error, hipMemcpyAsync(out, d_out, count * 32, hipMemcpyDeviceToHost, h.s));
+    RT_HIP(g_rtree_error, hipStreamSynchronize(h.s));
+    if (bad) { g_rtree_error = "an input element is not below the modulus"; return DST_ERR_ARG; }
+    return DST_OK;
+}
+
+// selects the tree's device; its stream and events on the first call, and at least `bytes` of device staging
+static int rtree_stage(const dst_rtree* t, size_t bytes) {
+    RT_HIP(t->err, hipSetDevice(t->device));
+    if (!t->stream) RT_HIP(t->err, hipStreamCreateWithFlags(&t->stream, hipStreamNonBlocking));
+    if (!t->ev[0]) RT_HIP(t->err, hipEventCreate(&t->ev[0]));
+    if (!t->ev[1]) RT_HIP(t->err, hipEventCreate(&t->ev[1]));
+    if (bytes > t->stage_bytes) {
+        if (t->stage) { hipFree(t->stage); t->stage = nullptr; t->stage_bytes = 0; }
+        RT_HIP(t->err, hipMalloc((void**)&t->stage, bytes));
+        t->stage_bytes = bytes;
+    }
+    return DST_OK;
+}
+// ev[0] .. ev[1] of the stream, which has been synchronised
+static int rtree_elapsed(const dst_rtree* t, double* ms) {
+    float f = 0;
+    RT_HIP(t->err, hipEventElapsedTime(&f, t->ev[0], t->ev[1]));
+    *ms = f;
+    return DST_OK;
+}
+
+static int rtree_build_device(dst_rtree* t, const uint8_t* leaves) {
+    const size_t n = (size_t)1 << t->log_leaves;
+    if (int r = rtree_stage(t, 4)) return r;                                                // the flag of a leaf element >= p
+    uint32_t *d_bad = reinterpret_cast<uint32_t*>(t->stage), bad = 0;
+    RT_HIP(t->err, hipMalloc((void**)&t->dev, 64 * n));
+    RT_HIP(t->err, hipMemsetAsync(d_bad, 0, 4, t->stream));
+    RT_HIP(t->err, hipMemsetAsync(t->dev, 0, 32, t->stream));                               // nodes[0] is not part of the tree
+    RT_HIP(t->err, hipMemcpyAsync(t->dev + 2 * n, leaves, 32 * n, hipMemcpyHostToDevice, t->stream));
+    RT_HIP(t->err, hipEventRecord(t->ev[0], t->stream));
+    if (k_rescue_tree(t->stream, t->dev, n, d_bad)) return rt_fail(t, DST_ERR_HIP, "rescue_tree_level_kernel: launch failed");
+    RT_HIP(t->err, hipEventRecord(t->ev[1], t->stream));
+    RT_HIP(t->err, hipMemcpyAsync(&bad, d_bad, 4, hipMemcpyDeviceToHost, t->stream));
+    RT_HIP(t->err, hipStreamSynchronize(t->stream));
+    if (int r = rtree_elapsed(t, &t->device_ms)) return r;
+    return bad ? rt_fail(t, DST_ERR_ARG, "a leaf element is not below the modulus") : DST_OK;
+}
+// the tree whose paths smpath / pmpath authenticate: parent = digest(l0, l1, r0, r1) (src/examples/merkle.rs:112-145)
+int dst_rtree_build(int device, const uint8_t* leaves, uint32_t log_leaves, dst_rtree** out) {
+    if (out) *out = nullptr;
+    if (!leaves || !out || log_leaves < 1 || log_leaves > 26) { g_rtree_error = "invalid argument (1 <= log_leaves <= 26)"; return DST_ERR_ARG; }
+    const size_t n = (size_t)1 << log_leaves;
+    std::unique_ptr<dst_rtree> t(new (std::nothrow) dst_rtree);
+    if (!t) { g_rtree_error = "out of host memory"; return DST_ERR_HIP; }
+    t->device = device < 0 ? -1 : device; t->log_leaves = log_leaves;
+    int r = DST_OK;
+    if (device >= 0) r = rtree_build_device(t.get(), leaves);
+    else if (!all_below_p(leaves, 2 * n)) r = rt_fail(t.get(), DST_ERR_ARG, "a leaf element is not below the modulus");
+    else {
+        try { t->host.assign(4 * n, 0); } catch (const std::bad_alloc&) { g_rtree_error = "out of host memory"; return DST_ERR_HIP; }
+        memcpy(t->host.data() + 2 * n, leaves, 32 * n);
+        rescue_tree_host(t->host.data(), n);
+    }
+    if (r != DST_OK) { g_rtree_error = t->err; return r; }
+    *out = t.release();
+    return DST_OK;
+}
+void dst_rtree_destroy(dst_rtree* t) { delete t; }
+const char* dst_rtree_last_error(const dst_rtree* t) { return t ? t->err.c_str() : g_rtree_error.c_str(); }
+int dst_rtree_build_ms(const dst_rtree* t, double* device_ms) {
+    if (int r = rt_enter(t)) return r;
+    if (!device_ms) return rt_fail(t, DST_ERR_ARG, "null pointer");
+    *device_ms = t->device_ms;
+    return DST_OK;
+}
+int dst_rtree_update_ms(const dst_rtree* t, double* device_ms) {
+    if (int r = rt_enter(t)) return r;
+    if (!device_ms) return rt_fail(t, DST_ERR_ARG, "null pointer");
+    *device_ms = t->update_ms;
+    return DST_OK;
+}
+int dst_rtree_read_nodes(const dst_rtree* t, uint64_t first, uint64_t count, uint8_t* out) {
+    if (int r = rt_enter(t)) return r;
+    if (!out && count) return rt_fail(t, DST_ERR_ARG, "null pointer");
+    const uint64_t total = (uint64_t)2 << t->log_leaves;
+    if (first > total || count > total - first) return rt_fail(t, DST_ERR_ARG, "node range past the end of the node array");
+    if (count == 0) return DST_OK;
+    if (t->device < 0) { memcpy(out, t->host.data() + 2 * first, 32 * count); return DST_OK; }
+    RT_HIP(t->err, hipSetDevice(t->device));
+    RT_HIP(t->err, hipMemcpy(out, t->dev + 2 * first, 32 * count, hipMemcpyDeviceToHost));
+    return DST_OK;
+}
+int dst_rtree_root(const dst_rtree* t, uint8_t root[32]) {
+    if (int r = rt_enter(t)) return r;
+    if (!root) return rt_fail(t, DST_ERR_ARG, "null pointer");
+    return dst_rtree_read_nodes(t, 1, 1, root);
+}
+
+// ---- updates in place ------------------------------------------------------------------------------------------------------------------
+// the dirty parents of an update, in the form k_rescue_tree_update and rescue_tree_update_host take: level l (2^l parents, l < log_leaves)
+// has cnt[l] of them, their node-array positions sorted at lists[off[l] ..); a level that is dirty as a whole (and so every level above it)
+// has cnt[l] == 2^l and no list
+struct rtree_dirty {
+    std::vector<uint32_t> lists;
+    size_t off[27] = {0}, cnt[27] = {0};
+};
+static rtree_dirty rtree_dirty_levels(std::vector<uint32_t> cur /* the leaf indices: sorted, distinct */, uint32_t log_leaves) {
+    rtree_dirty d;
+    for (uint32_t l = log_leaves; l-- > 0;) {                    // dirty parents of level l = unique(index >> (log_leaves - l))
+        for (auto& v : cur) v >>= 1;
+        cur.erase(std::unique(cur.begin(), cur.end()), cur.end());
+        d.cnt[l] = cur.size();
+        if (d.cnt[l] == ((size_t)1 << l)) continue;
+        d.off[l] = d.lists.size();
+        for (uint32_t v : cur) d.lists.push_back(((uint32_t)1 << l) + v);
+    }
+    return d;
+}
+// staging: the new leaves as given, their node positions, then the dirty lists -- `up`, one upload; nothing here allocates host memory
+static int rtree_update_device(dst_rtree* t, const std::vector<uint8_t>& up, size_t count, const rtree_dirty& d) {
+    if (int r = rtree_stage(t, up.size())) return r;
+    const uint32_t* d_words = reinterpret_cast<const uint32_t*>(t->stage + 32 * count);
+    RT_HIP(t->err, hipMemcpyAsync(t->stage, up.data(), up.size(), hipMemcpyHostToDevice, t->stream));
+    if (k_rescue_tree_scatter(t->stream, t->dev, d_words, reinterpret_cast<const fe*>(t->stage), count)) return rt_fail(t, DST_ERR_HIP, "rescue_tree_scatter_kernel: launch failed");
+    RT_HIP(t->err, hipEventRecord(t->ev[0], t->stream));
+    if (k_rescue_tree_update(t->stream, t->dev, t->log_leaves, d_words + count, d.off, d.cnt)) return rt_fail(t, DST_ERR_HIP, "rescue_tree_update_kernel: launch failed");
+    RT_HIP(t->err, hipEventRecord(t->ev[1], t->stream));
+    RT_HIP(t->err, hipStreamSynchronize(t->stream));
+    return rtree_elapsed(t, &t->update_ms);
+}
+// a tree is not frozen: replaces leaves and recomputes their ancestors, the nodes that src/examples/merkle.rs:98-145 would read on the
+// way from any of these leaves to the root
+int dst_rtree_update(dst_rtree* t, const uint64_t* indices, const uint8_t* leaves, size_t count) {
+    if (int r = rt_enter(t)) return r;
+    if (count == 0) return DST_OK;
+    if (!indices || !leaves) return rt_fail(t, DST_ERR_ARG, "null pointer");
+    const size_t n = (size_t)1 << t->log_leaves;
+    if (count > n) return rt_fail(t, DST_ERR_ARG, "a leaf index is repeated");
+    if (!all_leaf_indices(t, indices, count)) return rt_fail(t, DST_ERR_ARG, "leaf index past the end");
+    try {
+        // everything is checked and every host buffer allocated here, before the first node changes: O(count log count)
+        std::vector<uint32_t> sorted(indices, indices + count);
+        std::sort(sorted.begin(), sorted.end());
+        if (std::adjacent_find(sorted.begin(), sorted.end()) != sorted.end()) return rt_fail(t, DST_ERR_ARG, "a leaf index is repeated");
+        if (!all_below_p(leaves, 2 * count)) return rt_fail(t, DST_ERR_ARG, "a leaf element is not below the modulus");
+        const rtree_dirty d = rtree_dirty_levels(std::move(sorted), t->log_leaves);
+        if (t->device < 0) {
+            std::vector<u128> scratch(6 * count);                  // no level has more dirty parents than there are new leaves
+            for (size_t i = 0; i < count; i++) memcpy(t->host.data() + 2 * (n + indices[i]), leaves + 32 * i, 32);
+            rescue_tree_update_host(t->host.data(), t->log_leaves, d.lists.data(), d.off, d.cnt, scratch.data());
+            return DST_OK;
+        }
+        std::vector<uint32_t> where(count);
+        for (size_t i = 0; i < count; i++) where[i] = (uint32_t)(n + indices[i]);
+        std::vector<uint8_t> up(36 * count + 4 * d.lists.size());
+        memcpy(up.data(), leaves, 32 * count);
+        memcpy(up.data() + 32 * count, where.data(), 4 * count);
+        memcpy(up.data() + 36 * count, d.lists.data(), 4 * d.lists.size());
+        const int r = rtree_update_device(t, up, count, d);
+        if (r != DST_OK) { t->broken = true; t->err += "; the update did not complete, the tree is unusable"; }
+        return r;
+    } catch (const std::bad_alloc&) { return rt_fail(t, DST_ERR_HIP, "out of host memory"); }      // thrown before anything was queued
+}
+
+// ---- openings --------------------------------------------------------------------------------------------------------------------------
+// the paths of `count` leaves, (log_leaves + 1) nodes each -> out: on a device tree one upload of the positions, one gather launch, one copy back
+static int rtree_paths(const dst_rtree* t, const uint64_t* indices, size_t count, uint8_t* out) {
+    const size_t n = t->log_leaves + 1, m = count * n;
+    if (count > ((size_t)1 << 40)) return rt_fail(t, DST_ERR_ARG, "too many indices");
+    if (!all_leaf_indices(t, indices, count)) return rt_fail(t, DST_ERR_ARG, "leaf index past the end");
+    if (count == 0) return DST_OK;
+    uint64_t pos[27];
+    if (t->device < 0) {
+        for (size_t i = 0; i < count; i++) {
+            rescue_path_positions(t->log_leaves, indices[i], pos);
+            for (size_t k = 0; k < n; k++) memcpy(out + 32 * (i * n + k), t->host.data() + 2 * pos[k], 32);
+        }
+        return DST_OK;
+    }
+    try {
+        std::vector<uint32_t> where(m);
+        for (size_t i = 0; i < count; i++) {
+            rescue_path_positions(t->log_leaves, indices[i], pos);
+            for (size_t k = 0; k < n; k++) where[i * n + k] = (uint32_t)pos[k];
+        }
+        if (int r = rtree_stage(t, 36 * m)) return r;                 // [m nodes][m positions]
+        uint32_t* d_where = reinterpret_cast<uint32_t*>(t->stage + 32 * m);
+        RT_HIP(t->err, hipMemcpyAsync(d_where, where.data(), 4 * m, hipMemcpyHostToDevice, t->stream));
+        if (k_rescue_tree_gather(t->stream, t->dev, d_where, reinterpret_cast<fe*>(t->stage), m)) return rt_fail(t, DST_ERR_HIP, "rescue_tree_gather_kernel: launch failed");
+        RT_HIP(t->err, hipMemcpyAsync(out, t->stage, 32 * m, hipMemcpyDeviceToHost, t->stream));
+        RT_HIP(t->err, hipStreamSynchronize(t->stream));
+    } catch (const std::bad_alloc&) { return rt_fail(t, DST_ERR_HIP, "out of host memory"); }
+    return DST_OK;
+}
+int dst_rtree_paths(const dst_rtree* t, const uint64_t* indices, size_t count, uint8_t* paths) {
+    if (int r = rt_enter(t)) return r;
+    if ((!indices || !paths) && count) return rt_fail(t, DST_ERR_ARG, "null pointer");
+    return rtree_paths(t, indices, count, paths);
+}
+int dst_rtree_path(const dst_rtree* t, uint64_t index, uint8_t* path) {
+    if (int r = rt_enter(t)) return r;
+    if (!path) return rt_fail(t, DST_ERR_ARG, "null pointer");
+    return rtree_paths(t, &index, 1, path);
+}
+// generate_program_inputs (src/examples/merkle.rs:63-94) for `count` leaves; `size_name`: what the entry calls its size output
+static int rtree_tapes(const dst_rtree* t, const uint64_t* indices, size_t count, uint32_t what, uint8_t* tape_a, uint8_t* tape_b, size_t cap_each, size_t* each_out,
+                       const char* size_name) {
+    if (int r = rt_enter(t)) return r;
+    if (!each_out || what < 1 || what > 3) { t->err = std::string(size_name) + " missing, or what outside 1..3"; return DST_ERR_ARG; }
+    if (!indices && count) return rt_fail(t, DST_ERR_ARG, "null pointer");
+    const size_t n = t->log_leaves + 1;
+    const size_t each = ((what & 1u) ? 2 * n - 1 : 0) + ((what & 2u) ? n - 1 : 0);
+    *each_out = each;
+    if (!tape_a && !tape_b)                                                                // size query
+        return all_leaf_indices(t, indices, count) ? DST_OK : rt_fail(t, DST_ERR_ARG, "leaf index past the end");
+    if (!tape_a || !tape_b || cap_each < each) return rt_fail(t, DST_ERR_ARG, "tape buffers missing or too small");
+    try {
+        std::vector<u128> paths(2 * n * count);
+        if (int r = rtree_paths(t, indices, count, (uint8_t*)paths.data())) return r;
+        std::vector<u128> a, b;
+        for (size_t i = 0; i < count; i++) {
+            rescue_tapes(paths.data() + 2 * n * i, n, indices[i], what, a, b);
+            memcpy(tape_a + 16 * each * i, a.data(), 16 * each); memcpy(tape_b + 16 * each * i, b.data(), 16 * each);
+        }
+    } catch (const std::bad_alloc&) { return rt_fail(t, DST_ERR_HIP, "out of host memory"); }
+    return DST_OK;
+}
+int dst_rtree_tapes(const dst_rtree* t, uint64_t index, uint32_t what, uint8_t* tape_a, uint8_t* tape_b, size_t cap_elems, size_t* elems) {
+    return rtree_tapes(t, &index, 1, what, tape_a, tape_b, cap_elems, elems, "elems");
+}
+int dst_rtree_tapes_many(const dst_rtree* t, const uint64_t* indices, size_t count, uint32_t what, uint8_t* tape_a, uint8_t* tape_b, size_t cap_elems_each, size_t* elems_each) {
+    return rtree_tapes(t, indices, count, what, tape_a, tape_b, cap_elems_each, elems_each, "elems_each");
+}

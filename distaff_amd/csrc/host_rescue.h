@@ -46,6 +46,20 @@ inline void rescue_digest_many_host(const u128* in, size_t count, u128* out) {
 inline void rescue_tree_host(u128* nodes, size_t leaves) {
     for (size_t count = leaves >> 1; count >= 1; count >>= 1) rescue_digest_many_host(nodes + 4 * count, count, nodes + 2 * count);      // level by level: parents count .. 2 count
 }
+// the dirty parents of an update, level by level from the level of leaves / 2 parents (level log_leaves - 1) to the root (level 0): level l has
+// cnt[l] of them, their node-array positions at lists[off[l] ..), or no list when the whole level is dirty (cnt[l] == 2^l).  scratch: 6 elements
+// per parent of the longest list
+inline void rescue_tree_update_host(u128* nodes, uint32_t log_leaves, const uint32_t* lists, const size_t* off, const size_t* cnt, u128* scratch) {
+    for (uint32_t l = log_leaves; l-- > 0;) {
+        const size_t m = cnt[l];
+        if (m == ((size_t)1 << l)) { rescue_digest_many_host(nodes + 4 * m, m, nodes + 2 * m); continue; }
+        const uint32_t* list = lists + off[l];
+        u128 *in = scratch, *out = scratch + 4 * m;
+        for (size_t i = 0; i < m; i++) memcpy(in + 4 * i, nodes + 4 * (size_t)list[i], 64);
+        rescue_digest_many_host(in, m, out);
+        for (size_t i = 0; i < m; i++) memcpy(nodes + 2 * (size_t)list[i], out + 2 * i, 32);
+    }
+}
 
 // node-array positions of the authentication path of leaf `index`: [leaf, sibling, uncle, ...], log_leaves + 1 of them (merkle.rs:98-145)
 inline void rescue_path_positions(uint32_t log_leaves, uint64_t index, uint64_t* pos) {

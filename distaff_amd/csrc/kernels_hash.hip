@@ -387,25 +387,19 @@ __global__ void __launch_bounds__(RESCUE_THREADS) rescue_digest_kernel(const fe*
     rescue_digest4(v0, v1, v2, v3, d0, d1);
     out[2 * i] = d0; out[2 * i + 1] = d1;
 }
-// one level, one lane per parent: nodes[count + i] = digest(nodes[2 (count + i)], nodes[2 (count + i) + 1]); check: the children are leaves
-__global__ void __launch_bounds__(RESCUE_THREADS) rescue_tree_level_kernel(fe* nodes, size_t count, uint32_t check, uint32_t* __restrict__ bad) {
-    const size_t i = (size_t)blockIdx.x * RESCUE_THREADS + threadIdx.x;
-    if (i >= count) return;
-    const size_t p = count + i;
+// the parent at node-array position p on one lane: nodes[p] = digest(nodes[2 p], nodes[2 p + 1]); check: the children are leaves
+__device__ __forceinline__ void rescue_parent(fe* nodes, size_t p, uint32_t check, uint32_t* bad) {
     const fe v0 = nodes[4 * p], v1 = nodes[4 * p + 1], v2 = nodes[4 * p + 2], v3 = nodes[4 * p + 3];
     if (check && !(rescue_canonical(v0) && rescue_canonical(v1) && rescue_canonical(v2) && rescue_canonical(v3))) *bad = 1u;
     fe d0, d1;
     rescue_digest4(v0, v1, v2, v3, d0, d1);
     nodes[2 * p] = d0; nodes[2 * p + 1] = d1;
 }
-// the same level with one parent per group of eight lanes (six of them working, one state element each): the narrow levels, where a launch
-// lasts one wavefront's dependent chain whatever its width -- the chain per lane is a sixth as long
-__global__ void __launch_bounds__(RESCUE_THREADS) rescue_tree_level_spread_kernel(fe* nodes, size_t count, uint32_t check, uint32_t* __restrict__ bad) {
-    __shared__ fe xch[RESCUE_THREADS];
+// the same parent on a group of eight lanes (six of them working, one state element each): the narrow levels, where a launch lasts one
+// wavefront's dependent chain whatever its width -- the chain per lane is a sixth as long.  A group past the end (!live) is given a
+// valid p, keeps the barriers and stores nothing.
+__device__ __forceinline__ void rescue_parent_spread(fe* nodes, size_t p, bool live, uint32_t check, uint32_t* bad, fe* xch) {
     const uint32_t e = threadIdx.x & 7u;
-    const size_t i = (size_t)blockIdx.x * (RESCUE_THREADS / 8u) + (threadIdx.x >> 3);
-    const bool live = i < count;                                       // lanes past the end keep the barriers and store nothing
-    const size_t p = count + (live ? i : 0);
     fe v = fe_zero();                                                  // state after hasher.rs:18: (0, 0, r1, r0, l1, l0)
     if (e >= 2u && e < 6u) {
         v = nodes[4 * p + (5u - e)];
@@ -414,34 +408,33 @@ __global__ void __launch_bounds__(RESCUE_THREADS) rescue_tree_level_spread_kerne
     rescue_permute_lane(v, e, xch + (threadIdx.x & ~7u));
     if (live && (e == 5u || e == 4u)) nodes[2 * p + (5u - e)] = v;
 }
+// one whole level of `count` parents, p = count + i, in either form
+__global__ void __launch_bounds__(RESCUE_THREADS) rescue_tree_level_kernel(fe* nodes, size_t count, uint32_t check, uint32_t* __restrict__ bad) {
+    const size_t i = (size_t)blockIdx.x * RESCUE_THREADS + threadIdx.x;
+    if (i >= count) return;
+    rescue_parent(nodes, count + i, check, bad);
+}
+__global__ void __launch_bounds__(RESCUE_THREADS) rescue_tree_level_spread_kernel(fe* nodes, size_t count, uint32_t check, uint32_t* __restrict__ bad) {
+    __shared__ fe xch[RESCUE_THREADS];
+    const size_t i = (size_t)blockIdx.x * (RESCUE_THREADS / 8u) + (threadIdx.x >> 3);
+    rescue_parent_spread(nodes, count + (i < count ? i : 0), i < count, check, bad, xch);
+}
+// updates in place (dst_rtree_update): the dirty parents of a level, p = list[g] a node-array position.  The host has validated the new
+// leaves and every inner node is a digest, so nothing is checked here.
+__global__ void __launch_bounds__(RESCUE_THREADS) rescue_tree_update_kernel(fe* nodes, const uint32_t* __restrict__ list, size_t count) {
+    const size_t g = (size_t)blockIdx.x * RESCUE_THREADS + threadIdx.x;
+    if (g >= count) return;
+    rescue_parent(nodes, list[g], 0u, nullptr);
+}
+__global__ void __launch_bounds__(RESCUE_THREADS) rescue_tree_update_spread_kernel(fe* nodes, const uint32_t* __restrict__ list, size_t count) {
+    __shared__ fe xch[RESCUE_THREADS];
+    const size_t g = (size_t)blockIdx.x * (RESCUE_THREADS / 8u) + (threadIdx.x >> 3);
+    rescue_parent_spread(nodes, list[g < count ? g : 0], g < count, 0u, nullptr, xch);
+}
 // compile-time knob (profiles/rescue_tree.md): levels of at most this many parents use the spread form
 #ifndef RESCUE_SPREAD_MAX
 #define RESCUE_SPREAD_MAX ((size_t)1 << 15)
 #endif
-
-// ---- updates in place (dst_rtree_update): the same two level forms over a LIST of dirty parents, list[g] = a node-array position:
-//      nodes[list[g]] = digest(nodes[2 list[g]], nodes[2 list[g] + 1]).  The host has validated the new leaves and every inner node is a
-//      digest, so nothing is checked here. ------------------------------------------------------------------------------------------------
-__global__ void __launch_bounds__(RESCUE_THREADS) rescue_tree_update_kernel(fe* nodes, const uint32_t* __restrict__ list, size_t count) {
-    const size_t g = (size_t)blockIdx.x * RESCUE_THREADS + threadIdx.x;
-    if (g >= count) return;
-    const size_t p = list[g];
-    const fe v0 = nodes[4 * p], v1 = nodes[4 * p + 1], v2 = nodes[4 * p + 2], v3 = nodes[4 * p + 3];
-    fe d0, d1;
-    rescue_digest4(v0, v1, v2, v3, d0, d1);
-    nodes[2 * p] = d0; nodes[2 * p + 1] = d1;
-}
-__global__ void __launch_bounds__(RESCUE_THREADS) rescue_tree_update_spread_kernel(fe* nodes, const uint32_t* __restrict__ list, size_t count) {
-    __shared__ fe xch[RESCUE_THREADS];
-    const uint32_t e = threadIdx.x & 7u;
-    const size_t g = (size_t)blockIdx.x * (RESCUE_THREADS / 8u) + (threadIdx.x >> 3);
-    const bool live = g < count;                                       // lanes past the end keep the barriers and store nothing
-    const size_t p = list[live ? g : 0];
-    fe v = fe_zero();
-    if (e >= 2u && e < 6u) v = nodes[4 * p + (5u - e)];
-    rescue_permute_lane(v, e, xch + (threadIdx.x & ~7u));
-    if (live && (e == 5u || e == 4u)) nodes[2 * p + (5u - e)] = v;
-}
 // nodes[pos[i]] = vals[i] (the new leaves of an update) and out[i] = nodes[pos[i]] (batched openings): one lane per element, two per node
 __global__ void rescue_tree_scatter_kernel(fe* __restrict__ nodes, const uint32_t* __restrict__ pos, const fe* __restrict__ vals, size_t count) {
     const size_t t = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
@@ -458,33 +451,28 @@ int k_rescue_digests(hipStream_t stream, const fe* in, fe* out, size_t count, ui
     hipLaunchKernelGGL(rescue_digest_kernel, dim3((unsigned)((count + RESCUE_THREADS - 1) / RESCUE_THREADS)), dim3(RESCUE_THREADS), 0, stream, in, out, count, bad);
     return hipGetLastError() == hipSuccess ? 0 : -1;
 }
-// one whole level of `count` parents
-static int rescue_level(hipStream_t stream, fe* nodes, size_t count, uint32_t check, uint32_t* bad) {
-    if (count <= RESCUE_SPREAD_MAX)
-        hipLaunchKernelGGL(rescue_tree_level_spread_kernel, dim3((unsigned)((count + RESCUE_THREADS / 8 - 1) / (RESCUE_THREADS / 8))), dim3(RESCUE_THREADS), 0, stream, nodes, count, check, bad);
-    else
-        hipLaunchKernelGGL(rescue_tree_level_kernel, dim3((unsigned)((count + RESCUE_THREADS - 1) / RESCUE_THREADS)), dim3(RESCUE_THREADS), 0, stream, nodes, count, check, bad);
+// one level of `count` parents: the whole level of that width (list == nullptr), or the parents at the positions list[0 .. count) (device)
+static int rescue_level(hipStream_t stream, fe* nodes, size_t count, const uint32_t* list, uint32_t check, uint32_t* bad) {
+    const bool spread = count <= RESCUE_SPREAD_MAX;
+    const size_t per_block = spread ? RESCUE_THREADS / 8 : RESCUE_THREADS;
+    const dim3 grid((unsigned)((count + per_block - 1) / per_block)), block(RESCUE_THREADS);
+    if (list && spread) hipLaunchKernelGGL(rescue_tree_update_spread_kernel, grid, block, 0, stream, nodes, list, count);
+    else if (list) hipLaunchKernelGGL(rescue_tree_update_kernel, grid, block, 0, stream, nodes, list, count);
+    else if (spread) hipLaunchKernelGGL(rescue_tree_level_spread_kernel, grid, block, 0, stream, nodes, count, check, bad);
+    else hipLaunchKernelGGL(rescue_tree_level_kernel, grid, block, 0, stream, nodes, count, check, bad);
     return hipGetLastError() == hipSuccess ? 0 : -1;
 }
 // fills nodes[1 .. leaves) of a node array whose leaf level nodes[leaves .. 2 leaves) is in place
 int k_rescue_tree(hipStream_t stream, fe* nodes, size_t leaves, uint32_t* bad) {
     for (size_t count = leaves >> 1; count >= 1; count >>= 1)
-        if (rescue_level(stream, nodes, count, count == (leaves >> 1) ? 1u : 0u, bad)) return -1;
+        if (rescue_level(stream, nodes, count, nullptr, count == (leaves >> 1) ? 1u : 0u, bad)) return -1;
     return 0;
 }
 // recomputes the dirty parents level by level, from the level of leaves / 2 parents (level log_leaves - 1) to the root (level 0): level l has
-// cnt[l] dirty parents, their positions sorted at lists[off[l] ..); a level that is dirty as a whole (cnt[l] == 2^l) has no list and runs
-// through the dense level kernels
+// cnt[l] dirty parents, their positions sorted at lists[off[l] ..); a level that is dirty as a whole (cnt[l] == 2^l) has no list
 int k_rescue_tree_update(hipStream_t stream, fe* nodes, uint32_t log_leaves, const uint32_t* lists, const size_t* off, const size_t* cnt) {
-    for (uint32_t l = log_leaves; l-- > 0;) {
-        const size_t count = cnt[l];
-        if (count == ((size_t)1 << l)) { if (rescue_level(stream, nodes, count, 0u, nullptr)) return -1; continue; }
-        if (count <= RESCUE_SPREAD_MAX)
-            hipLaunchKernelGGL(rescue_tree_update_spread_kernel, dim3((unsigned)((count + RESCUE_THREADS / 8 - 1) / (RESCUE_THREADS / 8))), dim3(RESCUE_THREADS), 0, stream, nodes, lists + off[l], count);
-        else
-            hipLaunchKernelGGL(rescue_tree_update_kernel, dim3((unsigned)((count + RESCUE_THREADS - 1) / RESCUE_THREADS)), dim3(RESCUE_THREADS), 0, stream, nodes, lists + off[l], count);
-        if (hipGetLastError() != hipSuccess) return -1;
-    }
+    for (uint32_t l = log_leaves; l-- > 0;)
+        if (rescue_level(stream, nodes, cnt[l], cnt[l] == ((size_t)1 << l) ? nullptr : lists + off[l], 0u, nullptr)) return -1;
     return 0;
 }
 int k_rescue_tree_scatter(hipStream_t stream, fe* nodes, const uint32_t* pos, const fe* vals, size_t count) {

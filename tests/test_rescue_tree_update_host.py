@@ -1,6 +1,7 @@
 """Updates in place and batched openings of Rescue Merkle trees (dst_rtree_update, dst_rtree_paths, dst_rtree_tapes_many) on the host path
 (device = -1) of the PRODUCT library.  No GPU.  The yardstick of an update is dst_rtree_build over the modified leaves -- code that
-tests/test_rescue_tree_host.py holds against the oracle -- and the yardstick of a batched opening is the single-index call.  The helpers take
+tests/test_rescue_tree_host.py holds against the oracle.  The single-index calls may share their code with the batched openings, so these have
+two yardsticks that share none: the node array as dst_rtree_read_nodes copies it, at positions computed here, and tapes_from_path.  The helpers take
 the tree's constructor, so tests/test_rescue_tree_update_gpu.py and tests/test_rescue_tree_update_emulated.py run the same cases on device trees."""
 import ctypes
 import random
@@ -8,7 +9,7 @@ import random
 import numpy as np
 import pytest
 
-from test_rescue_tree_host import P, _product, random_leaves
+from test_rescue_tree_host import P, _product, random_leaves, tapes_from_path
 
 
 def host_tree(leaves):
@@ -79,11 +80,23 @@ def check_rejections(make_tree, log_leaves):
 
 
 def check_batched_openings(tree, indices):
-    """paths / tapes_many equal the concatenation of the single-index calls; an index past the end is an argument error"""
+    """paths / tapes_many equal the concatenation of the single-index calls, the nodes of the node array at the path's positions (leaf
+    2^L + i, then p ^ 1 while p >>= 1) and the tapes restated from those paths; an index past the end is an argument error"""
     import distaff_amd as D
-    assert tree.paths(indices) == [tree.path(i) for i in indices]
+    paths = tree.paths(indices)
+    assert paths == [tree.path(i) for i in indices]
+    v = D.arr_to_ints(tree.nodes(0, 2 << tree.log_leaves))
+    node = [(v[2 * k], v[2 * k + 1]) for k in range(2 << tree.log_leaves)]
+    for i, path in zip(indices, paths):
+        p = (1 << tree.log_leaves) + i
+        want = [node[p]]
+        while p > 1:
+            want.append(node[p ^ 1])
+            p >>= 1
+        assert path == want, i
     for what in (1, 2, 3):
         assert tree.tapes_many(indices, what) == [tree.tapes(i, what) for i in indices], what
+    assert tree.tapes_many(indices, 3) == [tapes_from_path(path, i) for i, path in zip(indices, paths)]
     assert tree.paths([]) == [] and tree.tapes_many([]) == []
     for call in (tree.paths, tree.tapes_many):
         with pytest.raises(D.DistaffError) as e:

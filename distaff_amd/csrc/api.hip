@@ -409,7 +409,7 @@ int dst_commit_trace(dst_ctx* c, uint8_t trace_root[32]) {
     for (int i = 0; i < 3; i++) HIP_TRY(c, hipMemcpyAsync(&last[i], c->trace + (size_t)i * c->trace_stride + (c->n - 1), 16, hipMemcpyDeviceToHost, c->stream));
     HIP_TRY(c, hipStreamSynchronize(c->stream));
     HIP_TRY(c, hipGetLastError());
-    c->op_count = (uint64_t)fe_to_u128(last[0]);
+    c->op_count = (uint64_t)fe_to_u128(last[0]); c->op_counter = last[0];
     c->program_hash[0] = last[1]; c->program_hash[1] = last[2];
     memcpy(trace_root, c->trace_root, 32);
     {

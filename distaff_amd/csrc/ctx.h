@@ -238,7 +238,8 @@ struct dst_ctx {
     std::vector<uint8_t> deep_z1, deep_z2;
     bool deep_pending = false;          // the DEEP values of the last composition are still in the page-locked staging area
     std::vector<std::vector<uint8_t>> fri_roots;
-    uint64_t op_count = 0;
+    uint64_t op_count = 0;              // op counter of the last trace row as the proof header carries it
+    fe op_counter{};                    // the same register as the field element it is (an arbitrary table may hold any value below p): what the last-step boundary constraint subtracts
     fe program_hash[2] = {};
     bool have_trace = false, committed = false, constraints_done = false, composed = false;
     // asynchronous upload (dst_trace_upload_async): column group g is complete when upload_done[g] has fired on upload_stream

@@ -72,7 +72,7 @@ int step::boundary_polys(dst_ctx* c, const fe* draws344, fe* ip, fe* fp, fe* o0,
                 if (constant != 0) g[pass * 2 + adj] = hf_add(g[pass * 2 + adj], hf_mul(k, constant));
             }
         };
-        term(0, pass ? (u128)c->op_count : 0, 0);
+        term(0, pass ? fe_to_u128(c->op_counter) : 0, 0);
         if (pass == 0) { for (int i = 0; i < 4; i++) term(1 + i, 0, 2 + 2 * i); }
         else { for (int i = 0; i < 2; i++) term(1 + i, fe_to_u128(c->program_hash[i]), 2 + 2 * i); }
         for (int i = 0; i < 3; i++) term(5 + i, pass ? one : 0, 10 + 2 * i);

@@ -52,7 +52,7 @@ int k_eval_constraints(dst_ctx* c, const fe* coeffs_dev, const fe* tc_dev, int64
     a.num_inputs = c->pub.num_inputs; a.num_outputs = c->pub.num_outputs;
     memcpy(a.inputs, c->pub.inputs, sizeof(a.inputs)); memcpy(a.outputs, c->pub.outputs, sizeof(a.outputs));
     memcpy(a.program_hash, c->program_hash, sizeof(a.program_hash));
-    a.op_count = fe_from_u64(c->op_count);
+    a.op_count = c->op_counter;
     HIP_TRY(c, hipMemsetAsync(c->d_u64, 0xFF, 8, c->stream));          // ~0 = no failing step yet
     const uint32_t cd = c->prm.ctx_depth, lp = c->prm.loop_depth, sd = (uint32_t)c->stack_depth;
     a.cl = cd > 1 ? cd : 1; a.ll = lp > 1 ? lp : 1; a.sl = sd > 8 ? sd : 8;

@@ -100,7 +100,7 @@ int dst_shard_commit_trace(dst_ctx* c) {
     for (int i = 0; i < 3; i++) HIP_TRY(c, hipMemcpyAsync(&last[i], c->trace + (size_t)i * c->trace_stride + (c->n - 1), 16, hipMemcpyDeviceToHost, c->stream));
     HIP_TRY(c, hipStreamSynchronize(c->stream));
     HIP_TRY(c, hipGetLastError());
-    c->op_count = (uint64_t)fe_to_u128(last[0]);
+    c->op_count = (uint64_t)fe_to_u128(last[0]); c->op_counter = last[0];
     c->program_hash[0] = last[1]; c->program_hash[1] = last[2];
     c->committed = true; c->constraints_done = c->composed = false;
     return DST_OK;
@@ -909,7 +909,7 @@ int dst_prove_sharded(dst_ctx* c, dst_comm* comm, const dst_public* pub, uint8_t
         fe last[3];
         tree_exchange(S, SH_TRACE_TREE, 0, trace_root, from, last);
         if (S.agreed) return S.agreed;
-        c->op_count = (uint64_t)fe_to_u128(last[0]);
+        c->op_count = (uint64_t)fe_to_u128(last[0]); c->op_counter = last[0];
         c->program_hash[0] = last[1]; c->program_hash[1] = last[2];
         c->committed = true; c->constraints_done = c->composed = false;
     }

@@ -101,12 +101,28 @@ def _run(emulated_library, args, timeout=900):
                           cwd=ROOT, env=env, stdout=subprocess.PIPE, stderr=subprocess.STDOUT, timeout=timeout)
 
 
+def _run_has_xdist():
+    import importlib.util
+    return importlib.util.find_spec("xdist") is not None and (os.cpu_count() or 1) >= 8
+
+
 def test_parity_selection_on_the_emulated_build(emulated_library):
     ids = ["tests/test_gpu_parity.py::" + t for t in SELECTION]
     r = _run(emulated_library, ids)
     out = r.stdout.decode()
     assert r.returncode == 0, out[-4000:]
     assert "%d passed" % len(SELECTION) in out, out[-2000:]
+
+
+def test_arbitrary_rows_and_the_widest_trace_on_the_emulated_build(emulated_library):
+    """tests/test_air_arbitrary_rows.py as a whole (uniform rows through every constraint instance up to 16 + 8 + 32 registers, valid prefixes
+    with arbitrary rows behind them) and the widest valid trace at its default instance (1024 rows of 70 and of 62 registers through every
+    phase).  The oracle's share of a case is 0.3 s and 1 s; the rest is the emulated launches."""
+    ids = ["tests/test_air_arbitrary_rows.py"] + ["tests/test_gpu_parity.py::test_widest_valid_trace_through_every_phase[%s-]" % s for s in ("loops", "blocks")]
+    r = _run(emulated_library, ids + (["-n", "4"] if _run_has_xdist() else []))
+    out = r.stdout.decode()
+    assert r.returncode == 0, out[-4000:]
+    assert "33 passed" in out, out[-2000:]                               # 23 uniform cases + 8 prefix cases + 2
 
 
 def test_whole_domain_parity_on_the_emulated_build(emulated_library):

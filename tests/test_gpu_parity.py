@@ -90,6 +90,7 @@ def _check_all_phases(O, D, trace, num_outputs=1, log_blowup=5, num_queries=50, 
     ctx.upload(trace.columns)
     assert ctx.prove(trace.public_inputs, op.outputs) == proof
     ctx.close()
+    return proof
 
 
 @pytest.mark.parametrize("log_n", [7, 10, 12])
@@ -245,6 +246,75 @@ def test_deep_stacks_and_nested_blocks(oracle, monkeypatch, instance):
         monkeypatch.setenv("DISTAFF_AIR", instance)
     for src, inputs, num_outputs in DEEP_PROGRAMS:
         _check_all_phases(oracle, D, oracle.Trace(src, inputs), num_outputs=num_outputs)
+
+
+def _nested_program(blocks, loops, pushes=27):
+    """`pushes` pushes on top of the public inputs, then `blocks` nested blocks around `loops` nested `while` loops (each entered once: the
+    secret tape feeds a 1 to every `read while.true` and a 0 to every `read end`) around `dup mul`, then the pushed items dropped again"""
+    return ("begin " + " ".join("push.%d" % (3 + i) for i in range(pushes)) + " " + "block noop " * blocks + "read while.true " * loops + "dup mul "
+            + "read end " * loops + "end " * blocks + "drop " * (pushes - 2) + "end")
+
+
+# name -> (blocks, loops, secret tape, (rows, context depth, loop depth, stack depth))
+WIDEST_SHAPES = {"loops": (7, 8, [1] * 8 + [0] * 16, (1024, 15, 8, 32)),        # W = 70
+                 "blocks": (15, 0, [], (1024, 15, 0, 32))}                        # W = 62: the context axis without a loop register
+_widest_traces = {}
+
+
+def _widest_trace(O, shape):
+    if shape not in _widest_traces:
+        blocks, loops, tape, dims = WIDEST_SHAPES[shape]
+        t = O.Trace(_nested_program(blocks, loops), [1, 2, 3, 4], tape)
+        assert (t.length, t.ctx_depth, t.loop_depth, t.stack_depth) == dims
+        _widest_traces[shape] = t
+    return _widest_traces[shape]
+
+
+@pytest.mark.parametrize("instance", ["", "generic"])
+@pytest.mark.parametrize("shape", ["loops", "blocks"])
+def test_widest_valid_trace_through_every_phase(oracle, monkeypatch, shape, instance):
+    """The largest shape a program can reach, through every phase against the oracle: 1024 rows of 70 registers (context depth 15, loop depth
+    8, stack depth 32; rows of 1120 bytes span two BLAKE3 chunks), and 15 nested blocks without a loop (62 registers) -- the slot loop of the
+    deep instance up to slot 31 with its left shifts at the end of the slice, 15 + 8 context / loop constraints and their coefficients, the
+    DEEP values of 70 registers, opened rows longer than a chunk; by the default instance and by the per-operation formulation.
+
+    Context depth 16, which `dst_ctx_create` accepts, is out of every program's reach: the VM's depth counter starts at 1 (decoder/mod.rs:39
+    sets it to the length of a one-register stack) and the 16th nested block then exceeds MAX_CONTEXT_DEPTH -- `block`s, `if`s and `while`s
+    alike (16 of any of them: "context stack overflow").  tests/test_air_arbitrary_rows.py runs that shape on arbitrary rows.
+
+    No register of either trace is constant (asserted; the list of constant registers is empty), so every DEEP coefficient and every
+    boundary coefficient multiplies a non-trivial extension."""
+    import distaff_amd as D
+    t = _widest_trace(oracle, shape)
+    assert [i for i in range(t.width) if (t.columns[i] == t.columns[i, 0]).all()] == []
+    if instance:
+        monkeypatch.setenv("DISTAFF_AIR", instance)
+    _check_all_phases(oracle, D, t, num_outputs=1, grinding=8)
+
+
+def test_widest_valid_trace_verifies_and_shards(oracle):
+    """the 70-register proof: dst_verify accepts it and rejects it after one opened trace value was flipped (a 1120-byte row no longer
+    hashes to its leaf); two thread-ranks of dst_prove_sharded_local return the same bytes"""
+    import distaff_amd as D
+    from test_verify_gpu import _first_trace_value_offset
+    t = _widest_trace(oracle, "loops")
+    outputs = oracle.Prover.from_trace(t, 1).outputs
+    ctx = _ctx(D, t, grinding=8)
+    ctx.upload(t.columns)
+    proof = ctx.prove(t.public_inputs, outputs)
+    ctx.close()
+    assert D.proof_info(proof)["register_count"] == 70
+    assert D.verify(proof, t.program_hash, t.public_inputs, outputs) == (True, "")
+    bad = bytearray(proof); bad[_first_trace_value_offset(proof)] ^= 1
+    assert D.verify(bytes(bad), t.program_hash, t.public_inputs, outputs) == (False, "verification of trace Merkle proof failed")
+    ctxs = []
+    for r in range(2):
+        c = D.Context(10, t.width, t.ctx_depth, t.loop_depth, rank=r, world=2, grinding=8)
+        c.upload(t.columns)
+        ctxs.append(c)
+    assert D.prove_sharded_local(ctxs, t.public_inputs, outputs) == proof
+    for c in ctxs:
+        c.close()
 
 
 def _pad_ops(ops, n):

@@ -5,6 +5,7 @@
 #include <cstdio>
 #include <cstdlib>
 #include "ctx.h"
+#include "host/ctx_tables.h"     // root powers and uploads, shared with k_ntt_init (kernels_ntt.hip)
 #include "host/steps.h"
 #include "host_proof.h"
 #include "host_util.h"
@@ -17,41 +18,6 @@ using step::wall_ms;
 using step::event_ms;
 
 static std::string g_create_error;
-
-// ---- small host field helpers on limbs (fe.h compiles for the host too) ---------------------------------------------------------
-static fe h_root_of_unity(uint32_t log_order) {               // field.rs:228: G^(2^(40 - log_order))
-    const u128 G = (((u128)0x120532E7B364080Aull) << 64) | 0x86B8723E1920F4AAull;      // field.rs:14
-    u128 r = G;
-    for (uint32_t i = log_order; i < 40; i++) r = hf_mul(r, r);
-    return fe_from_u128(r);
-}
-static std::vector<fe> h_powers(fe base, size_t count) {
-    std::vector<fe> v(count);
-    u128 b = fe_to_u128(base), cur = 1;
-    for (size_t i = 0; i < count; i++) { v[i] = fe_from_u128(cur); cur = hf_mul(cur, b); }
-    return v;
-}
-static std::vector<fe_tw> h_powers_tw(fe base, size_t count) {     // table pairs (w, w * 2^64 mod p) of the powers
-    std::vector<fe_tw> v(count);
-    u128 b = fe_to_u128(base), cur = 1;
-    for (size_t i = 0; i < count; i++) { v[i] = fe_tw_make(fe_from_u128(cur)); cur = hf_mul(cur, b); }
-    return v;
-}
-static fe h_inv(fe a) { return fe_from_u128(hf_pow(fe_to_u128(a), FIELD_P - 2)); }
-static fe h_pow(fe a, u128 e) { return fe_from_u128(hf_pow(fe_to_u128(a), e)); }
-
-template <class T>
-static int dev_alloc(dst_ctx* c, T** p, size_t count) {
-    HIP_TRY(c, hipMalloc((void**)p, count * sizeof(T) > 0 ? count * sizeof(T) : 16));
-    return DST_OK;
-}
-template <class T>
-static int dev_upload(dst_ctx* c, T** p, const std::vector<T>& v) {
-    int r = dev_alloc(c, p, v.size());
-    if (r) return r;
-    HIP_TRY(c, hipMemcpy(*p, v.data(), v.size() * sizeof(T), hipMemcpyHostToDevice));
-    return DST_OK;
-}
 
 // periodic constants of the AIR over a cycle of 16*8 steps: interpolate each 16-entry row, evaluate at w_128^s
 // (constraints/utils.rs:87-113; decoder/mod.rs:95-100,219-223; stack/mod.rs:67-70)
@@ -83,9 +49,11 @@ static std::vector<fe> build_periodic_table() {
 }
 
 static void free_all(dst_ctx* c) {
-    void* ptrs[] = {c->tw_lo, c->tw_hi, c->itw_lo, c->itw_hi, c->w1f, c->w2f, c->w1i, c->w2i, c->w1pf, c->w1pi, c->w2pf, c->w2pi, c->prescale, c->dit_last, c->tw4_lde, c->tw4_fwd, c->tw4_inv, c->tw4_row_fwd, c->tw4_row_inv, c->w3f, c->w3i, c->tmp2, c->periodic, c->trace == c->lde ? nullptr : c->trace, c->polys, c->lde, c->tmp,
+    void* ptrs[] = {c->tw_lo, c->tw_hi, c->itw_lo, c->itw_hi, c->prescale, c->dit_last, c->tw4_lde, c->tw4_fwd, c->tw4_inv, c->tw4_row_fwd, c->tw4_row_inv, c->tmp2, c->periodic, c->trace == c->lde ? nullptr : c->trace, c->polys, c->lde, c->tmp,
                     c->trace_leaves, c->trace_nodes, c->air_consts, c->ceval, c->cwork, c->cpoly, c->cevals, c->cnodes, c->comp_poly, c->comp, c->scratch, c->d_u64, c->d_stage, c->d_fri_chain};
     for (void* p : ptrs) if (p) hipFree(p);
+    for (auto& pass : c->ntt_stage_tw) for (fe_tw* p : pass) if (p) hipFree(p);
+    for (auto& pass : c->ntt_pre_tw) for (fe_tw* p : pass) if (p) hipFree(p);
     for (auto& e : c->kpending) { hipEventDestroy(e.e0); hipEventDestroy(e.e1); }
     for (hipEvent_t e : c->event_pool) hipEventDestroy(e);
     if (c->gather_buf) hipFree(c->gather_buf);
@@ -134,47 +102,6 @@ static int ctx_init(dst_ctx* c) {
     HIP_TRY(c, hipHostMalloc((void**)&c->h_stage, HS_TOTAL, hipHostMallocDefault));
     for (hipEvent_t& e : c->ph_ev) HIP_TRY(c, hipEventCreate(&e));
 
-    // NTT plan: n = n1 * n2 in two HBM passes, tiles bounded by 64 KiB of LDS; from n = 2^21 (measured cross-over) three passes n = n1 * nm * n3 with
-    // 16-column tiles (256-byte HBM segments) instead of 4096-point tiles that hold one or two columns
-    NttPlan& pl = c->plan;
-    const char* force = c->sw("DISTAFF_NTT");
-    // n = 2^21, 2^22: still two passes -- their 2048-point factors run as a register pre-stage + 1024-point LDS tiles (NttArgs::pre);
-    // DISTAFF_NTT=pre forces the pre-stages onto smaller transforms (tests), DISTAFF_NTT=3pass keeps the three-pass plan from 2^21 on
-    const bool force_3 = force && !strcmp(force, "3pass"), force_pre = force && !strcmp(force, "pre") && c->log_n >= 10 && c->log_n <= 22;
-    const bool pre_plan = force_pre || ((c->log_n == 21 || c->log_n == 22) && !force);
-    const bool three = !pre_plan && ((c->log_n >= 21 && !(force && (!strcmp(force, "reg") || !strcmp(force, "lds")))) || (force_3 && c->log_n >= 12));
-    pl.log_n = c->log_n;
-    if (three) {
-        // shape n1 * nm * n3 with n1 >= nm >= n3 as balanced as possible, at most 2^8 each; DISTAFF_NTT_SHAPE=a,b overrides n1, nm (tests)
-        uint32_t a = (c->log_n + 2) / 3, b = (c->log_n - a + 1) / 2;
-        if (a > 8) { a = 8; b = 8; }
-        if (const char* sh = c->sw("DISTAFF_NTT_SHAPE")) { unsigned x = 0, y = 0; if (sscanf(sh, "%u,%u", &x, &y) == 2 && x >= 4 && y >= 4 && x <= 8 && y <= 8 && x + y + 4 <= c->log_n && c->log_n - x - y <= 8) { a = x; b = y; } }
-        pl.log_n1 = a; pl.log_n2 = c->log_n - a; pl.log_n3 = c->log_n - a - b;
-    }
-    else { pl.log_n1 = (c->log_n + 1) / 2; pl.log_n2 = c->log_n / 2; pl.log_n3 = 0; }
-    if (pre_plan) { pl.pre_a = (force_pre || pl.log_n1 > 10) ? 1u : 0u; pl.pre_b = (force_pre || pl.log_n2 > 10) ? 1u : 0u; }
-    auto tile_for = [](uint32_t log_len, uint32_t other_len_log, uint32_t cap) {
-        uint32_t t = cap;
-        while (t > 1 && (((size_t)1 << log_len) * t * sizeof(fe) > 65536 || t > (1u << other_len_log))) t >>= 1;
-        return t;
-    };
-    pl.tile_a = tile_for(pl.log_n1 - pl.pre_a, pl.log_n2, three ? 16 : 4);
-    pl.tile_b = three ? tile_for(pl.log_n3, pl.log_n1, 16) : tile_for(pl.log_n2 - pl.pre_b, pl.log_n1, 4);
-    pl.tile_m = three ? tile_for(pl.log_n2 - pl.log_n3, pl.log_n3, 16) : 1;
-    // kernel choice per pass (measured): the LDS radix-2 kernels win while a tile holds >= 2 columns in 64 KiB of LDS; the
-    // register-radix kernels take over for 4096-point tiles.  DISTAFF_NTT=reg|lds forces one two-pass family (tests run both).
-    {
-        const bool reg_ok = !three && !pre_plan && pl.log_n2 >= 6 && pl.log_n1 <= 12;
-        pl.reg_a = reg_ok && pl.log_n1 >= 12; pl.reg_b = reg_ok && pl.log_n2 >= 12;      // 4096-point tiles: the LDS family is down to one column (16-byte segments)
-        if (force && !strcmp(force, "reg") && reg_ok) pl.reg_a = pl.reg_b = true;
-        if (force && !strcmp(force, "lds")) { pl.reg_a = pl.reg_a && pl.log_n1 >= 12; pl.reg_b = pl.reg_b && pl.log_n2 >= 12; }   // a 4096-point coset DIT (64 KiB tile + 128 KiB of twiddle pairs) does not fit LDS
-    }
-    {
-        fe w16 = h_root_of_unity(4), w16i = h_inv(w16);
-        std::vector<fe> f = h_powers(w16, 8), b = h_powers(w16i, 8);
-        for (int j = 0; j < 8; j++) { c->c16f[j] = f[j]; c->c16i[j] = b[j]; }
-    }
-
     // twiddle tables
     fe wN = h_root_of_unity(c->log_N), wN_inv = h_inv(wN);
     c->tw_lo_bits = (c->log_N + 1) / 2;
@@ -184,42 +111,7 @@ static int ctx_init(dst_ctx* c) {
     if ((r = dev_upload(c, &c->tw_hi, h_powers(h_pow(wN, (u128)1 << c->tw_lo_bits), (size_t)1 << hi_bits)))) return r;
     if ((r = dev_upload(c, &c->itw_lo, h_powers(wN_inv, (size_t)1 << c->tw_lo_bits)))) return r;
     if ((r = dev_upload(c, &c->itw_hi, h_powers(h_pow(wN_inv, (u128)1 << c->tw_lo_bits), (size_t)1 << hi_bits)))) return r;
-    const uint32_t log_second = pl.log_n3 ? pl.log_n2 - pl.log_n3 : pl.log_n2 - pl.pre_b;        // three-pass: w2* serve the middle pass
-    const uint32_t log_first = pl.log_n1 - pl.pre_a;                                             // length of the first pass's LDS transform
-    fe w1 = h_root_of_unity(log_first), w2 = h_root_of_unity(log_second);
-    if ((r = dev_upload(c, &c->w1f, h_powers_tw(w1, (size_t)1 << (log_first - 1))))) return r;
-    if ((r = dev_upload(c, &c->w2f, h_powers_tw(w2, (size_t)1 << (log_second - 1))))) return r;
-    if ((r = dev_upload(c, &c->w1i, h_powers_tw(h_inv(w1), (size_t)1 << (log_first - 1))))) return r;
-    if ((r = dev_upload(c, &c->w2i, h_powers_tw(h_inv(w2), (size_t)1 << (log_second - 1))))) return r;
-    if (pl.pre_a) {
-        fe wp = h_root_of_unity(pl.log_n1);
-        if ((r = dev_upload(c, &c->w1pf, h_powers_tw(wp, (size_t)1 << (pl.log_n1 - 1))))) return r;
-        if ((r = dev_upload(c, &c->w1pi, h_powers_tw(h_inv(wp), (size_t)1 << (pl.log_n1 - 1))))) return r;
-    }
-    if (pl.pre_b) {
-        fe wp = h_root_of_unity(pl.log_n2);
-        if ((r = dev_upload(c, &c->w2pf, h_powers_tw(wp, (size_t)1 << (pl.log_n2 - 1))))) return r;
-        if ((r = dev_upload(c, &c->w2pi, h_powers_tw(h_inv(wp), (size_t)1 << (pl.log_n2 - 1))))) return r;
-    }
-    if (pl.log_n3) {
-        fe w3 = h_root_of_unity(pl.log_n3);
-        if ((r = dev_upload(c, &c->w3f, h_powers_tw(w3, (size_t)1 << (pl.log_n3 - 1))))) return r;
-        if ((r = dev_upload(c, &c->w3i, h_powers_tw(h_inv(w3), (size_t)1 << (pl.log_n3 - 1))))) return r;
-        if ((r = dev_alloc(c, &c->tw4_row_fwd, (size_t)1 << pl.log_n2))) return r;
-        if ((r = dev_alloc(c, &c->tw4_row_inv, (size_t)1 << pl.log_n2))) return r;
-    }
-    {
-        const std::vector<fe_tw> pre = h_powers_tw(h_root_of_unity(c->log_b + pl.log_n1), (size_t)1 << (c->log_b + pl.log_n1));
-        if ((r = dev_upload(c, &c->prescale, pre))) return r;
-        // last-stage twiddles of the (half-length, with a pre-stage) coset DITs: [B][R][len / 2] entries pre[j + B * (h + R * k)]
-        const size_t R = (size_t)1 << pl.pre_a, half = (size_t)1 << (pl.log_n1 - pl.pre_a - 1);
-        std::vector<fe_tw> last(c->B * R * half);
-        for (size_t j = 0; j < c->B; j++) for (size_t h = 0; h < R; h++) for (size_t k = 0; k < half; k++) last[(j * R + h) * half + k] = pre[j + c->B * (h + R * k)];
-        if ((r = dev_upload(c, &c->dit_last, last))) return r;
-    }
-    if ((r = dev_alloc(c, &c->tw4_lde, c->Bc * c->n))) return r;
-    if ((r = dev_alloc(c, &c->tw4_fwd, c->n))) return r;
-    if ((r = dev_alloc(c, &c->tw4_inv, c->n))) return r;
+    if ((r = k_ntt_init(c))) return r;                   // transform plan, its tables and LDS limits (kernels_ntt.hip)
     if ((r = dev_upload(c, &c->periodic, build_periodic_table()))) return r;
     c->n_inv = fe_from_u128(hf_pow((u128)c->n, FIELD_P - 2));
     c->n_inv_tw = fe_tw_make(c->n_inv);
@@ -245,10 +137,10 @@ static int ctx_init(dst_ctx* c) {
     size_t stage_cap = (size_t)12 << 30;
     { size_t free_b = 0, total_b = 0; if (hipMemGetInfo(&free_b, &total_b) == hipSuccess && free_b / 4 < stage_cap) stage_cap = free_b / 4; }
     c->tmp_regs = 4;
-    while (c->tmp_regs < c->W && (c->tmp_regs + 1) * (pl.log_n3 ? 2 : 1) * c->Bc * n * sizeof(fe) <= stage_cap) c->tmp_regs++;
+    while (c->tmp_regs < c->W && (c->tmp_regs + 1) * (c->plan.count == 3 ? 2 : 1) * c->Bc * n * sizeof(fe) <= stage_cap) c->tmp_regs++;
     if (const char* e = c->sw("DISTAFF_TMP_REGS")) { const long k = atol(e); if (k >= 4 && k <= (long)c->W) c->tmp_regs = (size_t)k; }
     if ((r = dev_alloc(c, &c->tmp, c->Bc * c->tmp_regs * n))) return r;
-    if (pl.log_n3 && (r = dev_alloc(c, &c->tmp2, c->Bc * c->tmp_regs * n))) return r;
+    if (c->plan.count == 3 && (r = dev_alloc(c, &c->tmp2, c->Bc * c->tmp_regs * n))) return r;
     if ((r = dev_alloc(c, &c->trace_leaves, Nl))) return r;
     if ((r = dev_alloc(c, &c->trace_nodes, Nl))) return r;
     if ((r = dev_alloc(c, &c->ceval, 3 * 8 * n))) return r;
@@ -278,7 +170,7 @@ static int ctx_init(dst_ctx* c) {
         sz /= 4;
     }
     c->num_fri_layers = d + 1;
-    return k_build_twiddle_tables(c);
+    return DST_OK;
 }
 
 static const fe* as_fe(const uint8_t* p) { return reinterpret_cast<const fe*>(p); }
@@ -761,7 +653,7 @@ int dst_read_buffer(dst_ctx* c, uint32_t what, uint32_t arg, uint8_t* out, size_
     if (coset_major) {
         fe* tmp = nullptr;
         HIP_TRY(c, hipMalloc((void**)&tmp, bytes));
-        k_coset_to_natural(c, coset_major, cosets, tmp);
+        k_coset_to_natural_len(c, coset_major, cosets, c->n, tmp);
         hipError_t e = hipMemcpyAsync(out, tmp, bytes, hipMemcpyDeviceToHost, c->stream);
         if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
         hipFree(tmp);

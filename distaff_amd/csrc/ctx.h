@@ -134,13 +134,29 @@ enum {
     DST_BUF_FRI_LEAVES = 14,  // arg = layer: hashed rows
 };
 
+// The transform plan of a context (kernels_ntt.hip: ntt_plan_derive, k_ntt_init): n = n1 * n2 in two HBM passes or n = n1 * nm * n3 in three, and
+// everything about each pass that is fixed when the context is created.  The launch adds only what depends on (cosets, columns).
+struct NttInstance;                                  // row of the table of compiled ntt_pass_a / ntt_pass_b instances
+struct NttRegInstance;                               // the same for ntt_reg_kernel<LOGL>
+enum NttKind : uint32_t { NTT_FIRST, NTT_MIDDLE, NTT_LAST };
+struct NttPass {
+    NttKind kind = NTT_FIRST;
+    uint32_t log_len = 0;                            // length of the tile transform (half of the pass's with a register pre-stage)
+    uint32_t log_tile = 0, pre = 0;                  // log2 of the columns per workgroup tile; register pre-stage 0 / 1 (see NttArgs)
+    uint32_t dit = 0;                                // first pass of an extension: 0 pre-scale + DIF, 1 coset DIT, 2 DIT with the last-stage twiddles in global memory
+    size_t lds = 0;                                  // dynamic LDS bytes: tile + stage twiddles
+    const NttInstance* inst = nullptr;               // LDS family: the instance that runs the pass
+    const NttRegInstance* reg = nullptr;             // register-radix family (tile lengths 2^6 .. 2^12) instead
+    // views of the context's tables, [0] forward [1] inverse (k_ntt_init): stage twiddles w_len^t, pre-stage twiddles w_{2 len}^m, four-step twiddles
+    const fe_tw* stage_tw[2] = {nullptr, nullptr}; const fe_tw* pre_tw[2] = {nullptr, nullptr}; const tw4_t* tw4[2] = {nullptr, nullptr};
+};
 struct NttPlan {
-    uint32_t log_n = 0, log_n1 = 0, log_n2 = 0;      // n = n1 * n2: first pass length, rest
+    uint32_t log_n1 = 0, log_n2 = 0;                 // n = n1 * n2: first pass length, rest
     uint32_t log_n3 = 0;                             // 0: two passes (second pass length n2); else three passes n = n1 * (n2/n3) * n3
-    uint32_t tile_a = 1, tile_b = 1;                 // columns per workgroup tile in pass A / pass B
-    uint32_t tile_m = 1;                             // three-pass plans: columns per tile of the middle pass
-    bool reg_a = false, reg_b = false;               // per pass: register-radix kernel (tile lengths 2^6 .. 2^12) instead of the LDS radix-2 one
-    uint32_t pre_a = 0, pre_b = 0;                   // two-pass plans: register pre-stage of the pass (its LDS tiles hold 2^(log_n1 - pre_a) / 2^(log_n2 - pre_b) points), see NttArgs
+    uint32_t count = 0;                              // 2 or 3
+    bool coset_slow = false; uint32_t debug = 0;     // DISTAFF_NTT_ORDER=0, DISTAFF_NTT_DEBUG
+    NttPass pass[3], first_lde;                      // first_lde: pass[0] as the first pass of an extension (its DIT mode, LDS bytes and instance differ)
+    const NttPass& at(uint32_t i, bool lde) const { return (i == 0 && lde) ? first_lde : pass[i]; }
 };
 
 struct dst_ctx {
@@ -179,8 +195,7 @@ struct dst_ctx {
     fe *itw_lo = nullptr, *itw_hi = nullptr;     // w_N^-t
     uint32_t tw_lo_bits = 0;
     // every twiddle of the LDS-family transforms is a table pair (w, w * 2^64 mod p), see fe_mul_tw (fe.h)
-    fe_tw *w1f = nullptr, *w2f = nullptr, *w1i = nullptr, *w2i = nullptr;   // stage twiddles w_{n1}^t, w_{n2}^t and inverses (of the LDS transform lengths)
-    fe_tw *w1pf = nullptr, *w1pi = nullptr, *w2pf = nullptr, *w2pi = nullptr;   // register pre-stages: w_{n1}^m, m < n1 / 2 (and inverse), the same for n2
+    fe_tw *ntt_stage_tw[3][2] = {}, *ntt_pre_tw[3][2] = {};   // per pass of the plan, forward and inverse: stage twiddles w_len^t, t < len / 2; register pre-stage w_{2 len}^m, m < len
     fe_tw *prescale = nullptr;                   // w_{B*n1}^t, t < B*n1
     fe_tw *dit_last = nullptr;                   // [B][R][len/2], len = n1 / R, R = 2^pre_a: last-stage twiddles of every coset's (half-length) DIT, w_{B*n1}^(j + B*(h + R*k)) (the pre-scale table regrouped)
     // four-step twiddles of pass A as full tables in output order [k1][m2] (one multiplication per element instead of a two-level
@@ -188,7 +203,6 @@ struct dst_ctx {
     tw4_t *tw4_lde = nullptr;                    // [Bc][n]: w_N^(m2 * (B*k1 + j)), local cosets j
     tw4_t *tw4_fwd = nullptr, *tw4_inv = nullptr;   // [n]: w_n^(m2*k1) and its inverse
     tw4_t *tw4_row_fwd = nullptr, *tw4_row_inv = nullptr;   // three-pass plans: [n2] twiddles w_{n2}^(k2*m3) of the middle pass and inverse
-    fe_tw *w3f = nullptr, *w3i = nullptr;        // three-pass plans: stage twiddles of the last pass (length n3)
     fe *tmp2 = nullptr;                          // three-pass plans: second staging buffer
     fe *periodic = nullptr;                      // [128][AIR_PERIODIC_STRIDE] extended Rescue round constants + cycle masks + cubes of six of them
     void *air_consts = nullptr;                  // AirConsts (Rescue MDS matrices) in device memory
@@ -324,13 +338,12 @@ inline bool fri_tail_starts_at(const dst_ctx* c, int d) {
 }
 // ---- kernel launchers (kernels_*.hip) ------------------------------------------------------------------------------------
 // NTT / LDE
-int k_build_twiddle_tables(dst_ctx* c);                                                 // fills tw4_lde / tw4_fwd / tw4_inv (context creation)
+int k_ntt_init(dst_ctx* c);                                                             // context creation: derives c->plan, builds every table of it, raises the LDS limits
 void k_intt_columns(dst_ctx* c, const fe* src, size_t src_stride, fe* dst, size_t ncols); // size-n inverse NTT of ncols columns src_stride apart -> contiguous columns
 void k_lde_columns(dst_ctx* c, const fe* polys, fe* lde, size_t ncols);                 // n coefficients -> coset-major [Bc][n] per column
 void k_lde_fold8(dst_ctx* c, const fe* poly8n, fe* out);                                // 8n coefficients -> coset-major [Bc][n]
 void k_intt8_cosets(dst_ctx* c, fe* vals /* [8][n] coset-major, in place scratch */, fe* out8n, fe* work);
-void k_coset_to_natural(dst_ctx* c, const fe* src, size_t cosets, fe* dst);             // [cosets][n] -> natural [n*cosets]
-void k_coset_to_natural_len(dst_ctx* c, const fe* src, size_t cosets, size_t len, fe* dst);
+void k_coset_to_natural_len(dst_ctx* c, const fe* src, size_t cosets, size_t len, fe* dst);   // [cosets][len] -> natural [len*cosets]
 void k_fri_leaves_at(dst_ctx* c, const fe* e, digest* leaves, size_t R);
 void k_fri_fold_at(dst_ctx* c, const fe* e, fe* out, size_t R, int layer, fe special_x, const fe* alpha_dev = nullptr);   // alpha_dev: x read from device memory instead
 // hashing

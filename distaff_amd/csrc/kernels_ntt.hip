@@ -18,7 +18,10 @@
 // extension is the trace itself and is copied.  HBM accesses are T*16-byte segments (T = 4 for 1024-point tiles, 16 for the
 // 256-point tiles of three-pass plans).  A second, register-radix kernel family (ntt_reg_kernel) is kept as an independent
 // implementation that the tests run at every tile length.
+// The host side is in this file too ("launch layer" below): the table of compiled instances, the plan of a context (ntt_plan_derive: passes, tile
+// shapes, kernel family and instance per pass), its tables (k_ntt_init, called by dst_ctx_create) and ONE function that launches a pass (ntt_run_pass).
 #include "ctx.h"
+#include "host/ctx_tables.h"     // k_ntt_init builds the tables of the plan
 #include <mutex>
 #include <type_traits>
 #include "ntt_lds.h"
@@ -167,7 +170,7 @@ extern __shared__ __attribute__((aligned(16))) unsigned char ntt_smem[];
 // tile's elements for the NEXT iteration are fetched from HBM into registers before the butterfly stages of the current one start, so
 // the HBM latency and most of the transfer overlap with the arithmetic (measured: a block of this occupancy that loads, computes and
 // stores in sequence pays HBM time + ALU time, not their maximum).  <1024, 8, false>: two workgroups of 1024 lanes per CU, 8 waves per
-// SIMD in 64 registers, no prefetch -- while one workgroup loads, the other one's 16 waves keep the SIMDs busy (ntt_launch picks it for
+// SIMD in 64 registers, no prefetch -- while one workgroup loads, the other one's 16 waves keep the SIMDs busy (ntt_select picks it for
 // 1024-point tiles).  The stage twiddles live in LDS behind the tile as table pairs (32 bytes each), so the stages issue no global loads
 // that would have to wait behind the prefetch.  A 1024-point coset DIT with its whole table in LDS needs 64 KiB of tile + 32 KiB of
 // twiddles: that instance runs as ONE workgroup of 1024 lanes per CU; everything that fits 80 KiB runs as two workgroups per CU.
@@ -531,50 +534,131 @@ __global__ void __launch_bounds__((1 << (LOGL + NttDigits<LOGL>::log_t)) / 16, (
     }
 }
 
-template <int LOGL>
-static void launch_ntt_reg(dst_ctx* c, const NttRegArgs& a, size_t tiles, size_t cosets, size_t cols, const char* name, double bytes) {
-    constexpr int NT = (1 << (LOGL + NttDigits<LOGL>::log_t)) / 16;
-    dim3 g((unsigned)(tiles >> NttDigits<LOGL>::log_t), (unsigned)cosets, (unsigned)cols);
-    KScope ks_(c, name, bytes, true);
-    hipLaunchKernelGGL(ntt_reg_kernel<LOGL>, g, dim3(NT), 0, c->stream, a);
-}
-static void dispatch_ntt_reg(dst_ctx* c, uint32_t log_len, const NttRegArgs& a, size_t tiles, size_t cosets, size_t cols, const char* name, double bytes) {
-    switch (log_len) {
-        case 6: launch_ntt_reg<6>(c, a, tiles, cosets, cols, name, bytes); break;
-        case 7: launch_ntt_reg<7>(c, a, tiles, cosets, cols, name, bytes); break;
-        case 8: launch_ntt_reg<8>(c, a, tiles, cosets, cols, name, bytes); break;
-        case 9: launch_ntt_reg<9>(c, a, tiles, cosets, cols, name, bytes); break;
-        case 10: launch_ntt_reg<10>(c, a, tiles, cosets, cols, name, bytes); break;
-        case 11: launch_ntt_reg<11>(c, a, tiles, cosets, cols, name, bytes); break;
-        default: launch_ntt_reg<12>(c, a, tiles, cosets, cols, name, bytes); break;
-    }
+// ---- launch layer: instance tables, the plan, one function per pass ---------------------------------------------------------------------
+// Every compiled instance of the two LDS passes and of the register-radix kernel is named HERE and nowhere else: the LDS-limit raise, the
+// selection, the launch, the occupancy report (DISTAFF_NTT_DEBUG) and dst_ntt_describe all work on a row of these tables.
+struct NttInstance { bool pass_b; int threads, wpe; bool prefetch; int log_len, log_t, pre; void (*kernel)(NttArgs, const fe*, fe*); };
+#define NTT_INSTANCE(PASS_B, KERNEL, ...) {PASS_B, __VA_ARGS__, KERNEL<__VA_ARGS__>}
+static const NttInstance NTT_INSTANCES[] = {
+    // any shape, from the arguments: 512 lanes + prefetch (two workgroups per CU), 1024 lanes for tiles whose twiddles exceed 80 KiB (one per CU),
+    // 1024 lanes at 8 waves per SIMD without prefetch for 1024-point tiles
+    NTT_INSTANCE(false, ntt_pass_a, 512, 4, true, 0, 0, 0),  NTT_INSTANCE(true, ntt_pass_b, 512, 4, true, 0, 0, 0),
+    NTT_INSTANCE(false, ntt_pass_a, 1024, 4, true, 0, 0, 0), NTT_INSTANCE(true, ntt_pass_b, 1024, 4, true, 0, 0, 0),
+    NTT_INSTANCE(false, ntt_pass_a, 1024, 8, false, 0, 0, 0), NTT_INSTANCE(true, ntt_pass_b, 1024, 8, false, 0, 0, 0),
+    // 1024 x 4 tiles (n = 2^20).  The second pass needs 44 registers: its 60-register form with the register prefetch still runs at 8 waves (9.03 ->
+    // 8.85 ms per proof); the first pass with the prefetch spills (12.0 -> 12.3 ms) and stays without
+    NTT_INSTANCE(false, ntt_pass_a, 1024, 8, false, 10, 2, 0), NTT_INSTANCE(true, ntt_pass_b, 1024, 8, true, 10, 2, 0),
+    // 256 x 16 tiles (n = 2^16, the first two passes of three-pass plans)
+    NTT_INSTANCE(false, ntt_pass_a, 1024, 8, false, 8, 4, 0), NTT_INSTANCE(true, ntt_pass_b, 1024, 8, false, 8, 4, 0),
+    NTT_INSTANCE(false, ntt_pass_a, 512, 4, true, 8, 4, 0),   NTT_INSTANCE(true, ntt_pass_b, 512, 4, true, 8, 4, 0),
+    // register pre-stage (NttArgs::pre): the 1024 x 4 shape of n = 2^21 / 2^22 compiled for the shape, any other shape (tests) from the arguments
+    NTT_INSTANCE(false, ntt_pass_a, 1024, 8, false, 10, 2, 1), NTT_INSTANCE(true, ntt_pass_b, 1024, 8, false, 10, 2, 1),
+    NTT_INSTANCE(false, ntt_pass_a, 512, 4, true, 0, 0, 1),   NTT_INSTANCE(true, ntt_pass_b, 512, 4, true, 0, 0, 1),
+};
+struct NttRegInstance { int log_len, log_t, threads; void (*kernel)(NttRegArgs); };
+#define NTT_REG_INSTANCE(L) {L, NttDigits<L>::log_t, (1 << (L + NttDigits<L>::log_t)) / 16, ntt_reg_kernel<L>}
+static const NttRegInstance NTT_REG_INSTANCES[] = {NTT_REG_INSTANCE(6), NTT_REG_INSTANCE(7), NTT_REG_INSTANCE(8), NTT_REG_INSTANCE(9), NTT_REG_INSTANCE(10), NTT_REG_INSTANCE(11), NTT_REG_INSTANCE(12)};
+
+// the DISTAFF_NTT_* switches (ctx.h DST_SWITCHES) as the plan reads them, parsed once
+struct NttSwitches {
+    enum Force { NONE, OTHER, PRE, THREE, REG, LDS } force = NONE;   // DISTAFF_NTT (OTHER: set to something else -- no plan family forced, but not the default either)
+    unsigned shape_a = 0, shape_b = 0;     // DISTAFF_NTT_SHAPE
+    int waves = 0;                         // DISTAFF_NTT_WAVES: 0 unset, else 4 / 8
+    int dif = -1;                          // DISTAFF_NTT_DIF: -1 unset, else the first-pass mode it forces
+    bool any_shape = false, coset_slow = false;   // DISTAFF_NTT_FIXED=0, DISTAFF_NTT_ORDER=0
+    uint32_t debug = 0;                    // DISTAFF_NTT_DEBUG
+};
+static NttSwitches ntt_switches(const dst_ctx* c) {
+    NttSwitches s;
+    if (const char* e = c->sw("DISTAFF_NTT")) s.force = !strcmp(e, "pre") ? s.PRE : !strcmp(e, "3pass") ? s.THREE : !strcmp(e, "reg") ? s.REG : !strcmp(e, "lds") ? s.LDS : s.OTHER;
+    if (const char* e = c->sw("DISTAFF_NTT_SHAPE")) if (sscanf(e, "%u,%u", &s.shape_a, &s.shape_b) != 2) s.shape_a = s.shape_b = 0;
+    if (const char* e = c->sw("DISTAFF_NTT_WAVES")) s.waves = e[0] == '8' ? 8 : 4;
+    if (const char* e = c->sw("DISTAFF_NTT_DIF")) s.dif = e[0] == '0' ? 1 : e[0] == '2' ? 2 : 0;
+    s.any_shape = c->sw_is("DISTAFF_NTT_FIXED", "0");
+    if (const char* e = c->sw("DISTAFF_NTT_ORDER")) s.coset_slow = e[0] == '0';
+    if (const char* e = c->sw("DISTAFF_NTT_DEBUG")) s.debug = (uint32_t)atoi(e);
+    return s;
 }
 
-static void launch_pass_reg(dst_ctx* c, bool pass_b, const fe* src, size_t src_col_stride, size_t src_coset_stride,
-                            fe* dst, size_t dst_col_stride, size_t dst_coset_stride, size_t cosets, size_t cols, bool inverse, bool lde, uint32_t skip) {
-    const NttPlan& p = c->plan;
-    const size_t n1 = (size_t)1 << p.log_n1, n2 = (size_t)1 << p.log_n2;
-    NttRegArgs a{};
-    a.log_N = c->log_N; a.log_b = c->log_b; a.lo_bits = c->tw_lo_bits;
-    a.j0 = lde ? (uint32_t)c->j0 + skip : 0u; a.coset_twiddle = lde ? 1u : 0u;
-    for (int j = 0; j < 8; j++) a.c16[j] = inverse ? c->c16i[j] : c->c16f[j];
-    a.src = src; a.src_col_stride = src_col_stride; a.src_coset_stride = src_coset_stride;
-    a.dst = dst; a.dst_col_stride = dst_col_stride; a.dst_coset_stride = dst_coset_stride;
-    a.scale = c->n_inv;
-    if (!pass_b) {      // n1-point transforms over the stride-n2 dimension
-        a.in_stride_m = n2; a.in_stride_t = 1; a.out_stride_k = n2;
-        a.stage_tw = inverse ? c->w1i : c->w1f;
-        a.tw_lo = inverse ? c->itw_lo : c->tw_lo; a.tw_hi = inverse ? c->itw_hi : c->tw_hi;
-        a.prescale = lde ? c->prescale : nullptr;
-        a.has_scale = 0;
-        dispatch_ntt_reg(c, p.log_n1, a, n2, cosets, cols, "ntt_pass_a", 16.0 * c->n * cols * (lde ? (1 + cosets) : 2 * cosets));
-    } else {            // n2-point transforms over the contiguous dimension, natural-order output
-        a.in_stride_m = 1; a.in_stride_t = n2; a.out_stride_k = n1;
-        a.stage_tw = inverse ? c->w2i : c->w2f;
-        a.tw_lo = nullptr; a.tw_hi = nullptr; a.prescale = nullptr;
-        a.has_scale = inverse ? 1u : 0u;
-        dispatch_ntt_reg(c, p.log_n2, a, n1, cosets, cols, "ntt_pass_b", 32.0 * c->n * cols * cosets);
+// two workgroups of 512 lanes per CU while tile + twiddles fit 80 KiB, else one of 1024 lanes (same waves per SIMD)
+#define NTT_LDS_TWO_PER_CU (80 * 1024)
+// The LDS-family instance of a pass.  1024-point tiles (five LDS rounds per tile): two workgroups of 1024 lanes = 8 waves per SIMD, 64 registers, no
+// register prefetch -- the other workgroup's rounds cover a workgroup's loads (measured 20.2 against 20.55 ms of extension per 2^20 proof, same box);
+// shorter tiles stay with 512 lanes + prefetch (2^16: 0.96 against 1.03 ms).  DISTAFF_NTT_WAVES=4|8 forces one (the tests run both).  A shape-compiled
+// instance where there is one for the lanes chosen, unless DISTAFF_NTT_FIXED=0; a pre-stage pass has its own instances and ignores the lanes.
+static const NttInstance* ntt_select(bool pass_b, uint32_t log_len, uint32_t log_tile, uint32_t pre, size_t lds, const NttSwitches& sw) {
+    const bool two = lds <= NTT_LDS_TWO_PER_CU, eight = two && (sw.waves ? sw.waves == 8 : log_len >= 10);
+    const bool fixed = log_len == 10 && log_tile == 2 && !sw.any_shape, fixed84 = log_len == 8 && log_tile == 4 && !sw.any_shape;
+    const bool wide8 = pre ? fixed : eight, shaped = pre ? fixed : two && ((eight && fixed) || fixed84);
+    const int threads = (wide8 || (!pre && !two)) ? 1024 : 512, wpe = wide8 ? 8 : 4, len = shaped ? (int)log_len : 0, t = shaped ? (int)log_tile : 0;
+    for (const NttInstance& r : NTT_INSTANCES)
+        if (r.pass_b == pass_b && r.threads == threads && r.wpe == wpe && r.log_len == len && r.log_t == t && r.pre == (int)pre) return &r;
+    return nullptr;
+}
+// First pass of an extension: coset DIT (the pre-scale costs nothing, but the workgroup holds n1 - 1 twiddle pairs of ITS coset) while
+// tile + pairs fit the 80 KiB that let two workgroups share a CU; otherwise pre-scale + DIF with the n1/2 shared stage twiddles (one
+// more multiplication per element, two workgroups per CU: measured 14.5 against 15.0 ms per proof for the 1024-point tiles of n = 2^20).
+// DISTAFF_NTT_DIF=1 / 0 forces one or the other (the tests run both).
+// returns 0: pre-scale + DIF, 1: coset DIT with the whole table in LDS, 2: coset DIT whose last-stage twiddles (half of the table) are read
+// from global memory (tile + the other half fit 80 KiB)
+static uint32_t ntt_first_pass_mode(const NttSwitches& sw, size_t n1, size_t tile) {
+    if (sw.dif >= 0) return (uint32_t)sw.dif;
+    if (n1 * tile * sizeof(fe) + n1 * sizeof(fe_tw) <= NTT_LDS_TWO_PER_CU) return 1;
+    if (n1 * tile * sizeof(fe) + (n1 / 2) * sizeof(fe_tw) <= NTT_LDS_TWO_PER_CU) return 2;
+    return 0;
+}
+
+// The plan, a pure function of the transform length and the switches.  n = n1 * n2 in two HBM passes, tiles bounded by 64 KiB of LDS; from n = 2^21
+// (measured cross-over) three passes n = n1 * nm * n3 with 16-column tiles (256-byte HBM segments) instead of 4096-point tiles that hold one or two
+// columns -- except n = 2^21, 2^22: still two passes, their 2048-point factors run as a register pre-stage + 1024-point LDS tiles (NttArgs::pre).
+// DISTAFF_NTT=pre forces the pre-stages onto smaller transforms (tests), DISTAFF_NTT=3pass the three-pass plan from 2^12 on.
+static NttPlan ntt_plan_derive(uint32_t log_n, const NttSwitches& sw) {
+    NttPlan pl;
+    const bool force_pre = sw.force == sw.PRE && log_n >= 10 && log_n <= 22;
+    const bool pre_plan = force_pre || ((log_n == 21 || log_n == 22) && sw.force == sw.NONE);
+    const bool three = !pre_plan && ((log_n >= 21 && sw.force != sw.REG && sw.force != sw.LDS) || (sw.force == sw.THREE && log_n >= 12));
+    uint32_t pre_a = 0, pre_b = 0;
+    if (three) {
+        // shape n1 * nm * n3 with n1 >= nm >= n3 as balanced as possible, at most 2^8 each; DISTAFF_NTT_SHAPE=a,b overrides n1, nm (tests)
+        uint32_t a = (log_n + 2) / 3, b = (log_n - a + 1) / 2;
+        if (a > 8) { a = 8; b = 8; }
+        const unsigned x = sw.shape_a, y = sw.shape_b;
+        if (x >= 4 && y >= 4 && x <= 8 && y <= 8 && x + y + 4 <= log_n && log_n - x - y <= 8) { a = x; b = y; }
+        pl.log_n1 = a; pl.log_n2 = log_n - a; pl.log_n3 = log_n - a - b;
     }
+    else { pl.log_n1 = (log_n + 1) / 2; pl.log_n2 = log_n / 2; }
+    if (pre_plan) { pre_a = (force_pre || pl.log_n1 > 10) ? 1u : 0u; pre_b = (force_pre || pl.log_n2 > 10) ? 1u : 0u; }
+    // kernel family per pass (measured): the LDS radix-2 kernels win while a tile holds >= 2 columns in 64 KiB of LDS; the
+    // register-radix kernels take over for 4096-point tiles.  DISTAFF_NTT=reg|lds forces one two-pass family (tests run both); a 4096-point
+    // coset DIT (64 KiB tile + 128 KiB of twiddle pairs) does not fit LDS, so `lds` leaves those to the register family
+    const bool reg_ok = !three && !pre_plan && pl.log_n2 >= 6 && pl.log_n1 <= 12, reg_all = reg_ok && sw.force == sw.REG;
+    const bool reg_a = reg_ok && (pl.log_n1 >= 12 || reg_all), reg_b = reg_ok && (pl.log_n2 >= 12 || reg_all);
+    // a pass: `cap` columns per tile while the tile fits 64 KiB and the other dimension has that many
+    auto pass = [&](NttKind kind, uint32_t log_len, uint32_t other_len_log, uint32_t cap, uint32_t pre, bool reg, bool lde) {
+        NttPass P;
+        uint32_t t = cap;
+        while (t > 1 && (((size_t)1 << log_len) * t * sizeof(fe) > 65536 || t > (1u << other_len_log))) t >>= 1;
+        P.kind = kind; P.log_len = log_len; P.log_tile = (uint32_t)__builtin_ctz(t); P.pre = pre;
+        const size_t len = (size_t)1 << log_len;
+        if (lde && !reg) { P.dit = ntt_first_pass_mode(sw, len, t); if (pre && P.dit == 0) P.dit = 2; }   // the pre-stage is written for the coset DIT (tiles of at most 1024 x 4: always fits)
+        P.lds = len * t * sizeof(fe) + (P.dit == 1 ? len : len / 2) * sizeof(fe_tw);
+        if (reg) { for (const NttRegInstance& r : NTT_REG_INSTANCES) if (r.log_len == (int)log_len) P.reg = &r; }
+        else P.inst = ntt_select(kind == NTT_LAST, log_len, P.log_tile, pre, P.lds, sw);
+        return P;
+    };
+    const uint32_t cap = three ? 16 : 4;
+    pl.pass[0] = pass(NTT_FIRST, pl.log_n1 - pre_a, pl.log_n2, cap, pre_a, reg_a, false);
+    pl.first_lde = pass(NTT_FIRST, pl.log_n1 - pre_a, pl.log_n2, cap, pre_a, reg_a, true);
+    if (three) pl.pass[1] = pass(NTT_MIDDLE, pl.log_n2 - pl.log_n3, pl.log_n3, cap, 0, false, false);
+    pl.pass[three ? 2 : 1] = three ? pass(NTT_LAST, pl.log_n3, pl.log_n1, cap, 0, false, false) : pass(NTT_LAST, pl.log_n2 - pre_b, pl.log_n1, cap, pre_b, reg_b, false);
+    pl.count = three ? 3 : 2; pl.coset_slow = sw.coset_slow; pl.debug = sw.debug;
+    return pl;
+}
+static int ntt_plan_set(dst_ctx* c) {                 // c->plan from the context's size and switches; every pass must have found its compiled instance
+    NttPlan& pl = c->plan = ntt_plan_derive(c->log_n, ntt_switches(c));
+    for (uint32_t i = 0; i < 2 * pl.count; i++)
+        if (!pl.at(i % pl.count, i >= pl.count).inst && !pl.at(i % pl.count, i >= pl.count).reg) { c->err = "transform plan: no compiled instance for pass " + std::to_string(i % pl.count); return DST_ERR_STATE; }
+    return DST_OK;
 }
 
 // tiles a workgroup walks through: as many as keep >= 2048 workgroups in the launch (8 per CU), at most 8
@@ -583,223 +667,121 @@ static uint32_t ntt_tiles_per_block(uint32_t tiles, size_t arrays) {
     while (k < 8 && tiles % (2 * k) == 0 && (size_t)(tiles / (2 * k)) * arrays >= 2048) k *= 2;
     return k;
 }
-// Block order of an extension's first pass (ntt_block): every (coset, register) of a tile group before the next group, so that the
-// coefficient tiles (the same for every coset) and the four-step twiddles (the same for every register) are re-read while they are still
-// in the XCD's L2: FETCH_SIZE of the 2^20 launches 1.29 against 1.57 GB, time unchanged.  DISTAFF_NTT_ORDER=0: coset-slow order (tests).
-static uint32_t ntt_coset_fast(const dst_ctx* c, size_t groups, size_t cosets) {
-    const char* e = c->sw("DISTAFF_NTT_ORDER");
-    return (cosets > 1 && groups % 8 == 0 && !(e && e[0] == '0')) ? 1u : 0u;
-}
-static void ntt_raise_lds_limit(dst_ctx* c) {                  // tile + stage twiddles exceed the 64 KiB default
-    // contexts of several ranks may run as threads of one process (dst_prove_sharded_local): the once-per-device marks are guarded
-    static std::mutex mu;
-    static bool raised[64] = {};
-    std::lock_guard<std::mutex> lock(mu);
-    if (c->device < 0 || c->device >= 64 || raised[c->device]) return;
-    (void)hipFuncSetAttribute((const void*)ntt_pass_a<512>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-    (void)hipFuncSetAttribute((const void*)ntt_pass_a<1024>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-    (void)hipFuncSetAttribute((const void*)ntt_pass_b<512>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-    (void)hipFuncSetAttribute((const void*)ntt_pass_b<1024>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-    (void)hipFuncSetAttribute((const void*)ntt_pass_a<1024, 8, false>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-    (void)hipFuncSetAttribute((const void*)ntt_pass_a<1024, 8, false, 10, 2>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-    (void)hipFuncSetAttribute((const void*)ntt_pass_a<1024, 8, false, 8, 4>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-    (void)hipFuncSetAttribute((const void*)ntt_pass_b<1024, 8, false, 8, 4>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-    (void)hipFuncSetAttribute((const void*)ntt_pass_a<512, 4, true, 8, 4>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-    (void)hipFuncSetAttribute((const void*)ntt_pass_b<512, 4, true, 8, 4>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-    (void)hipFuncSetAttribute((const void*)ntt_pass_b<1024, 8, true, 10, 2>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-    (void)hipFuncSetAttribute((const void*)ntt_pass_b<1024, 8, false>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-    (void)hipFuncSetAttribute((const void*)ntt_pass_a<1024, 8, false, 10, 2, 1>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-    (void)hipFuncSetAttribute((const void*)ntt_pass_b<1024, 8, false, 10, 2, 1>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-    (void)hipFuncSetAttribute((const void*)ntt_pass_a<512, 4, true, 0, 0, 1>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-    (void)hipFuncSetAttribute((const void*)ntt_pass_b<512, 4, true, 0, 0, 1>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-
-    raised[c->device] = true;
-}
-// DISTAFF_NTT_DEBUG=1 prints, once per distinct launch shape, how many workgroups of the instance are resident per CU
-static void ntt_report_occupancy(const char* name, bool pass_b, int threads, bool eight, size_t lds) {
+// DISTAFF_NTT_DEBUG=1 prints, once per distinct launch shape, how many workgroups of the instance that runs are resident per CU
+static void ntt_report_occupancy(const char* name, const NttInstance& I, size_t lds) {
     static std::mutex mu;
     static std::map<std::string, bool> seen;
-    char key[128]; snprintf(key, sizeof key, "%s/%d/%d/%zu", name, threads, (int)eight, lds);
+    char key[128]; snprintf(key, sizeof key, "%s/%d/%d/%d/%d/%d/%zu", name, I.threads, I.wpe, I.log_len, I.log_t, I.pre, lds);
     std::lock_guard<std::mutex> lock(mu);
     if (seen[key]) return; seen[key] = true;
     int nb = -1;
-    hipError_t e;
-    if (eight) e = pass_b ? hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, ntt_pass_b<1024, 8, false>, 1024, lds) : hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, ntt_pass_a<1024, 8, false>, 1024, lds);
-    else if (threads == 512) e = pass_b ? hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, ntt_pass_b<512>, 512, lds) : hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, ntt_pass_a<512>, 512, lds);
-    else e = pass_b ? hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, ntt_pass_b<1024>, 1024, lds) : hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, ntt_pass_a<1024>, 1024, lds);
-    fprintf(stderr, "[distaff] %s: %d lanes, %zu B LDS -> %d workgroups per CU (%s)\n", name, threads, lds, nb, hipGetErrorString(e));
+    const hipError_t e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, I.kernel, I.threads, lds);
+    fprintf(stderr, "[distaff] %s<%d,%d,%d,%d,%d,%d>: %d lanes, %zu B LDS -> %d workgroups per CU (%s)\n", name, I.threads, I.wpe, (int)I.prefetch, I.log_len, I.log_t, I.pre, I.threads, lds, nb, hipGetErrorString(e));
 }
-// two workgroups of 512 lanes per CU while tile + twiddles fit 80 KiB, else one of 1024 lanes (same waves per SIMD)
-#define NTT_LDS_TWO_PER_CU (80 * 1024)
-static void ntt_launch(dst_ctx* c, bool pass_b, NttArgs& a, size_t groups, size_t cosets, size_t cols, size_t lds, const char* name, double bytes) {
-    ntt_raise_lds_limit(c);
-    a.groups = (uint32_t)groups; a.cosets = (uint32_t)cosets; a.cols = (uint32_t)cols;
-    const dim3 grid((unsigned)(groups * cosets * cols));
-    // multiply-adds of the launch: 18 per table-pair multiplication (fe_mul_tw); multiplications per element: every DIT stage 1/2, DIF
-    // two-stage rounds 1 each except the last (1/4: the distance-1 stage has no twiddles), plus four-step twiddle / pre-scale / 1/n
-    const uint32_t stages = pass_b ? a.log_n2 : a.log_n1;
-    double mults = (!pass_b && a.dit) ? 0.5 * stages : ((stages & 1u) ? 0.5 * (stages - 1) : (stages >= 2 ? 0.5 * stages - 0.75 : 0.0));
-    if (!pass_b) mults += ((!a.dit && a.prescale != nullptr) ? 1.0 : 0.0) + (NTT_TW4_PAIRS ? 1.0 : 21.0 / 18.0); else if (a.has_scale) mults += 1.0;     // the four-step product: 18 or 21 mads
-    if (a.pre) mults += (!pass_b && a.dit) ? 1.0 : 0.5;        // register pre-stage: c * x[m + len] in both halves of a coset DIT, the twiddle of the odd half otherwise
-    const double elements = (double)groups * a.tiles_per_block * ((size_t)1 << a.tile) * ((size_t)1 << stages) * cosets * cols;
-    KScope ks_(c, name, bytes, true, 18.0 * mults * elements);
-    const char* wv = c->sw("DISTAFF_NTT_WAVES");
-    const bool two = lds <= NTT_LDS_TWO_PER_CU, eight = two && (wv ? wv[0] == '8' : stages >= 10);
-    const bool any_shape = c->sw_is("DISTAFF_NTT_FIXED", "0");
-    const bool fixed = stages == 10 && a.tile == 2 && !any_shape;      // 1024 x 4 tiles (n = 2^20) have their own instances,
-    const bool fixed84 = stages == 8 && a.tile == 4 && !any_shape;     // and so have 256 x 16 tiles (n = 2^16, the first two passes of three-pass plans)
-    if (a.debug & 1u) ntt_report_occupancy(name, pass_b, eight || !two ? 1024 : 512, eight, lds);
-    if (a.pre) {
-        // register pre-stage instances (NttArgs::pre): the 1024 x 4 shape of n = 2^21 / 2^22 compiled for the shape, any other shape (tests) from the arguments
-        if (pass_b && fixed) hipLaunchKernelGGL((ntt_pass_b<1024, 8, false, 10, 2, 1>), grid, dim3(1024), lds, c->stream, a, a.src, a.dst);
-        else if (!pass_b && fixed) hipLaunchKernelGGL((ntt_pass_a<1024, 8, false, 10, 2, 1>), grid, dim3(1024), lds, c->stream, a, a.src, a.dst);
-        else if (pass_b) hipLaunchKernelGGL((ntt_pass_b<512, 4, true, 0, 0, 1>), grid, dim3(512), lds, c->stream, a, a.src, a.dst);
-        else hipLaunchKernelGGL((ntt_pass_a<512, 4, true, 0, 0, 1>), grid, dim3(512), lds, c->stream, a, a.src, a.dst);
+
+struct NttIo { const fe* src; size_t src_col_stride, src_coset_stride; fe* dst; size_t dst_col_stride, dst_coset_stride; };   // strides in elements
+
+// One pass of a transform over `cosets` x `cols` arrays: the kernel arguments from the pass description, then the launch -- or, with `describe`, a
+// line about the launch instead of it (dst_ntt_describe).  Two-pass plans (n = n1 * n2): the first pass runs the n1-point transforms over the
+// stride-n2 dimension, the last the n2-point transforms over the contiguous one, natural-order output.  Three-pass plans (n = n1 * nm * n3):
+//   first  (shape n1 x n/n1): as in a two-pass plan (coset pre-scale, twiddle w_N^(m'*(B*k1+j)));
+//   middle (ntt_pass_a, shape nm x n3 on each of the cosets * n1 rows of n/n1 points): twiddle w_{n/n1}^(k2*m3);
+//   last   (n3 points, tile = adjacent k1, one batch per k2): natural-order store at k1 + n1*(k2 + nm*k3).
+static void ntt_run_pass(dst_ctx* c, const NttPass& P, const NttIo& io, size_t cosets, size_t cols, bool inverse, bool lde, uint32_t skip, std::string* describe) {
+    const NttPlan& p = c->plan;
+    const bool first = P.kind == NTT_FIRST, last = P.kind == NTT_LAST;
+    const size_t n = c->n, n1 = (size_t)1 << p.log_n1, nrow = (size_t)1 << p.log_n2;
+    const char* name = first ? "ntt_pass_a" : last ? "ntt_pass_b" : "ntt_pass_mid";
+    const double bytes = 16.0 * n * cols * ((first && lde) ? 1 + cosets : 2 * cosets);     // an extension reads its coefficients once for all cosets
+    const uint32_t j0 = lde ? (uint32_t)c->j0 + skip : 0u, has_scale = (last && inverse) ? 1u : 0u;   // 1/n leaves with the last pass
+    char line[384];
+    if (P.reg) {
+        const NttRegInstance& R = *P.reg;
+        NttRegArgs a{};
+        a.log_N = c->log_N; a.log_b = c->log_b; a.lo_bits = c->tw_lo_bits; a.j0 = j0; a.coset_twiddle = lde ? 1u : 0u;
+        for (int j = 0; j < 8; j++) a.c16[j] = inverse ? c->c16i[j] : c->c16f[j];
+        a.src = io.src; a.src_col_stride = io.src_col_stride; a.src_coset_stride = io.src_coset_stride;
+        a.dst = io.dst; a.dst_col_stride = io.dst_col_stride; a.dst_coset_stride = io.dst_coset_stride;
+        a.scale = c->n_inv; a.has_scale = has_scale; a.stage_tw = P.stage_tw[inverse];
+        if (first) {
+            a.in_stride_m = nrow; a.in_stride_t = 1; a.out_stride_k = nrow;
+            a.tw_lo = inverse ? c->itw_lo : c->tw_lo; a.tw_hi = inverse ? c->itw_hi : c->tw_hi;
+            a.prescale = lde ? c->prescale : nullptr;
+        } else { a.in_stride_m = 1; a.in_stride_t = nrow; a.out_stride_k = n1; }
+        const dim3 g((unsigned)((first ? nrow : n1) >> R.log_t), (unsigned)cosets, (unsigned)cols);
+        if (describe) {
+            snprintf(line, sizeof line, "%s reg LOGL=%d block=%d grid=%ux%ux%u lds=0 dit=0 pre=0 log_len=%d log_tile=%d tiles_per_block=1 coset_fast=0 has_scale=%u bytes=%.0f mads=0\n",
+                     name, R.log_len, R.threads, g.x, g.y, g.z, R.log_len, R.log_t, has_scale, bytes);
+            *describe += line; return;
+        }
+        KScope ks_(c, name, bytes, true);
+        hipLaunchKernelGGL(R.kernel, g, dim3(R.threads), 0, c->stream, a);
         return;
     }
-    if (two) {
-        // 1024-point tiles (five LDS rounds per tile): two workgroups of 1024 lanes = 8 waves per SIMD, 64 registers, no register prefetch -- the
-        // other workgroup's rounds cover a workgroup's loads (measured 20.2 against 20.55 ms of extension per 2^20 proof, same box); shorter
-        // tiles stay with 512 lanes + prefetch (2^16: 0.96 against 1.03 ms).  DISTAFF_NTT_WAVES=4|8 forces one (the tests run both).
-        // the fixed-shape second pass needs 44 registers: its 60-register form with the register prefetch still runs at 8 waves (9.03 -> 8.85 ms
-        // per proof); the first pass with the prefetch spills (12.0 -> 12.3 ms) and stays without
-        if (pass_b && eight && fixed) hipLaunchKernelGGL((ntt_pass_b<1024, 8, true, 10, 2>), grid, dim3(1024), lds, c->stream, a, a.src, a.dst);
-        else if (!pass_b && eight && fixed) hipLaunchKernelGGL((ntt_pass_a<1024, 8, false, 10, 2>), grid, dim3(1024), lds, c->stream, a, a.src, a.dst);
-        else if (pass_b && eight && fixed84) hipLaunchKernelGGL((ntt_pass_b<1024, 8, false, 8, 4>), grid, dim3(1024), lds, c->stream, a, a.src, a.dst);
-        else if (!pass_b && eight && fixed84) hipLaunchKernelGGL((ntt_pass_a<1024, 8, false, 8, 4>), grid, dim3(1024), lds, c->stream, a, a.src, a.dst);
-        else if (pass_b && fixed84) hipLaunchKernelGGL((ntt_pass_b<512, 4, true, 8, 4>), grid, dim3(512), lds, c->stream, a, a.src, a.dst);
-        else if (!pass_b && fixed84) hipLaunchKernelGGL((ntt_pass_a<512, 4, true, 8, 4>), grid, dim3(512), lds, c->stream, a, a.src, a.dst);
-        else if (pass_b && eight) hipLaunchKernelGGL((ntt_pass_b<1024, 8, false>), grid, dim3(1024), lds, c->stream, a, a.src, a.dst);
-        else if (pass_b) hipLaunchKernelGGL(ntt_pass_b<512>, grid, dim3(512), lds, c->stream, a, a.src, a.dst);
-        else if (eight) hipLaunchKernelGGL((ntt_pass_a<1024, 8, false>), grid, dim3(1024), lds, c->stream, a, a.src, a.dst);
-        else hipLaunchKernelGGL(ntt_pass_a<512>, grid, dim3(512), lds, c->stream, a, a.src, a.dst);
-    } else {
-        if (pass_b) hipLaunchKernelGGL(ntt_pass_b<1024>, grid, dim3(1024), lds, c->stream, a, a.src, a.dst);
-        else hipLaunchKernelGGL(ntt_pass_a<1024>, grid, dim3(1024), lds, c->stream, a, a.src, a.dst);
-    }
-}
-// First pass of an extension: coset DIT (the pre-scale costs nothing, but the workgroup holds n1 - 1 twiddle pairs of ITS coset) while
-// tile + pairs fit the 80 KiB that let two workgroups share a CU; otherwise pre-scale + DIF with the n1/2 shared stage twiddles (one
-// more multiplication per element, two workgroups per CU: measured 14.5 against 15.0 ms per proof for the 1024-point tiles of n = 2^20).
-// DISTAFF_NTT_DIF=1 / 0 forces one or the other (the tests run both).
-// returns 0: pre-scale + DIF, 1: coset DIT with the whole table in LDS, 2: coset DIT whose last-stage twiddles (half of the table) are read
-// from global memory (tile + the other half fit 80 KiB)
-static int ntt_first_pass_mode(const dst_ctx* c, size_t n1, size_t tile) {
-    if (const char* e = c->sw("DISTAFF_NTT_DIF")) return e[0] == '0' ? 1 : e[0] == '2' ? 2 : 0;
-    if (n1 * tile * sizeof(fe) + n1 * sizeof(fe_tw) <= NTT_LDS_TWO_PER_CU) return 1;
-    if (n1 * tile * sizeof(fe) + (n1 / 2) * sizeof(fe_tw) <= NTT_LDS_TWO_PER_CU) return 2;
-    return 0;
-}
-static NttArgs ntt_common_args(dst_ctx* c, bool inverse, bool lde, uint32_t skip) {
     NttArgs a{};
-    a.log_N = c->log_N; a.log_b = c->log_b;
-    a.j0 = lde ? (uint32_t)c->j0 + skip : 0u;
-    a.scale = c->n_inv_tw;
-    { const char* dbg = c->sw("DISTAFF_NTT_DEBUG"); a.debug = dbg ? (uint32_t)atoi(dbg) : 0u; }
-    (void)inverse;
-    return a;
-}
-static void launch_pass_lds(dst_ctx* c, bool pass_b, const fe* src, size_t src_col_stride, size_t src_coset_stride,
-                            fe* dst, size_t dst_col_stride, size_t dst_coset_stride, size_t cosets, size_t cols, bool inverse, bool lde, uint32_t skip) {
-    const NttPlan& p = c->plan;
-    NttArgs a = ntt_common_args(c, inverse, lde, skip);
+    a.log_N = c->log_N; a.log_b = c->log_b; a.scale = c->n_inv_tw; a.has_scale = has_scale; a.debug = p.debug;
+    a.src = io.src; a.src_col_stride = io.src_col_stride; a.src_coset_stride = io.src_coset_stride;
+    a.dst = io.dst; a.dst_col_stride = io.dst_col_stride; a.dst_coset_stride = io.dst_coset_stride;
+    a.stage_tw = P.stage_tw[inverse]; a.tile = P.log_tile; a.pre = P.pre; a.pre_tw = P.pre_tw[inverse];
     a.log_n1 = p.log_n1; a.log_n2 = p.log_n2;
-    a.prescale = lde ? c->prescale : nullptr;
-    a.has_scale = inverse ? 1u : 0u;
-    a.src = src; a.src_col_stride = src_col_stride; a.src_coset_stride = src_coset_stride;
-    a.dst = dst; a.dst_col_stride = dst_col_stride; a.dst_coset_stride = dst_coset_stride;
-    if (!pass_b) {
-        a.tw4 = lde ? c->tw4_lde + (size_t)skip * c->n : (inverse ? c->tw4_inv : c->tw4_fwd); a.tw4_coset_stride = lde ? c->n : 0;
-        a.stage_tw = inverse ? c->w1i : c->w1f; a.tile = (uint32_t)__builtin_ctz(p.tile_a);
-        a.pre = p.pre_a; a.pre_tw = inverse ? c->w1pi : c->w1pf;
-        a.log_n1 = p.log_n1 - p.pre_a;                                 // the kernel's LDS transform; with the pre-stage the pass covers twice that
-        const size_t n1 = (size_t)1 << a.log_n1;
-        int mode = lde ? ntt_first_pass_mode(c, n1, p.tile_a) : 0;
-        if (p.pre_a && lde && mode == 0) mode = 2;                     // the pre-stage is written for the coset DIT (tiles of at most 1024 x 4: always fits)
-        a.dit = mode ? 1u : 0u; a.dit_last = mode == 2 ? c->dit_last : nullptr;
-        const size_t lds_a = n1 * p.tile_a * sizeof(fe) + (mode == 1 ? n1 : n1 / 2) * sizeof(fe_tw);
-        const uint32_t tiles = (1u << p.log_n2) / p.tile_a;
-        a.tiles_per_block = ntt_tiles_per_block(tiles, (cosets * cols) << p.pre_a);
-        a.coset_fast = ntt_coset_fast(c, (size_t)(tiles / a.tiles_per_block) << p.pre_a, cosets);
-        ntt_launch(c, false, a, (size_t)(tiles / a.tiles_per_block) << p.pre_a, cosets, cols, lds_a, "ntt_pass_a", 16.0 * c->n * cols * (lde ? (1 + cosets) : 2 * cosets));
+    size_t units = cosets;             // what the coset dimension of the block index runs over
+    uint32_t tiles, batch_log = 0;     // tiles of an array; three-pass last pass: one batch of tile groups per middle frequency
+    if (first) {
+        a.log_n1 = P.log_len; a.j0 = j0;
+        a.prescale = lde ? c->prescale : nullptr;
+        a.dit = P.dit ? 1u : 0u; a.dit_last = P.dit == 2 ? c->dit_last : nullptr;
+        a.tw4 = !lde ? P.tw4[inverse] : describe ? nullptr : c->tw4_lde + (size_t)skip * n; a.tw4_coset_stride = lde ? n : 0;
+        tiles = (uint32_t)(nrow >> P.log_tile);
+    } else if (!last) {                // every (coset, k1) row of nrow points is an array of its own
+        a.log_n1 = P.log_len; a.log_n2 = p.log_n3; a.tw4 = P.tw4[inverse];
+        a.src_coset_stride = a.dst_coset_stride = nrow; units = cosets * n1;
+        tiles = (1u << p.log_n3) >> P.log_tile;
     } else {
-        a.stage_tw = inverse ? c->w2i : c->w2f; a.tile = (uint32_t)__builtin_ctz(p.tile_b);
-        a.pre = p.pre_b; a.pre_tw = inverse ? c->w2pi : c->w2pf;
-        a.log_n2 = p.log_n2 - p.pre_b;
-        a.src_row_stride = (size_t)1 << p.log_n2; a.dst_k_stride = (size_t)1 << p.log_n1; a.batch_log = 0; a.src_batch_stride = a.dst_batch_stride = 0;
-        const size_t n2 = (size_t)1 << a.log_n2;
-        const size_t lds_b = n2 * p.tile_b * sizeof(fe) + (n2 / 2) * sizeof(fe_tw);
-        const uint32_t tiles = (1u << p.log_n1) / p.tile_b;
-        a.tiles_per_block = ntt_tiles_per_block(tiles, (cosets * cols) << p.pre_b);
-        ntt_launch(c, true, a, (size_t)(tiles / a.tiles_per_block) << p.pre_b, cosets, cols, lds_b, "ntt_pass_b", 32.0 * c->n * cols * cosets);
+        a.log_n2 = P.log_len;
+        a.src_row_stride = nrow; a.dst_k_stride = n1;
+        if (p.log_n3) { batch_log = p.log_n2 - p.log_n3; a.src_batch_stride = (size_t)1 << p.log_n3; a.dst_k_stride = n1 << batch_log; a.dst_batch_stride = n1; }
+        a.batch_log = batch_log;
+        tiles = (uint32_t)(n1 >> P.log_tile);
     }
+    const uint32_t spread = P.pre + batch_log;         // a pre-stage pass has two tile groups per tile (one per half of the frequencies), a batched one a group per batch
+    a.tiles_per_block = ntt_tiles_per_block(tiles, (units * cols) << spread);
+    const size_t groups = (size_t)(tiles / a.tiles_per_block) << spread;
+    // Block order of a first pass over several cosets (ntt_block): every (coset, register) of a tile group before the next group, so that the
+    // coefficient tiles (the same for every coset) and the four-step twiddles (the same for every register) are re-read while they are still
+    // in the XCD's L2: FETCH_SIZE of the 2^20 launches 1.29 against 1.57 GB, time unchanged.  DISTAFF_NTT_ORDER=0: coset-slow order (tests).
+    a.coset_fast = (first && cosets > 1 && groups % 8 == 0 && !p.coset_slow) ? 1u : 0u;
+    a.groups = (uint32_t)groups; a.cosets = (uint32_t)units; a.cols = (uint32_t)cols;
+    // multiply-adds of the launch: 18 per table-pair multiplication (fe_mul_tw); multiplications per element: every DIT stage 1/2, DIF
+    // two-stage rounds 1 each except the last (1/4: the distance-1 stage has no twiddles), plus four-step twiddle / pre-scale / 1/n
+    const uint32_t stages = P.log_len;
+    double mults = a.dit ? 0.5 * stages : ((stages & 1u) ? 0.5 * (stages - 1) : (stages >= 2 ? 0.5 * stages - 0.75 : 0.0));
+    if (!last) mults += ((first && lde && !a.dit) ? 1.0 : 0.0) + (NTT_TW4_PAIRS ? 1.0 : 21.0 / 18.0); else if (has_scale) mults += 1.0;     // the four-step product: 18 or 21 mads
+    if (P.pre) mults += a.dit ? 1.0 : 0.5;             // register pre-stage: c * x[m + len] in both halves of a coset DIT, the twiddle of the odd half otherwise
+    const double elements = (double)groups * a.tiles_per_block * ((size_t)1 << a.tile) * ((size_t)1 << stages) * units * cols;
+    const NttInstance& I = *P.inst;
+    const unsigned grid = (unsigned)(groups * units * cols);
+    if (describe) {
+        snprintf(line, sizeof line, "%s lds %c<%d,%d,%d,%d,%d,%d> block=%d grid=%u lds=%zu dit=%u pre=%u log_len=%u log_tile=%u tiles_per_block=%u coset_fast=%u has_scale=%u bytes=%.0f mads=%.0f\n",
+                 name, I.pass_b ? 'b' : 'a', I.threads, I.wpe, (int)I.prefetch, I.log_len, I.log_t, I.pre, I.threads, grid, P.lds, P.dit, P.pre, P.log_len, P.log_tile,
+                 a.tiles_per_block, a.coset_fast, has_scale, bytes, 18.0 * mults * elements);
+        *describe += line; return;
+    }
+    KScope ks_(c, name, bytes, true, 18.0 * mults * elements);
+    if (a.debug & 1u) ntt_report_occupancy(name, I, P.lds);
+    hipLaunchKernelGGL(I.kernel, dim3(grid), dim3(I.threads), P.lds, c->stream, a, a.src, a.dst);
 }
 
-// n = n1 * nm * n3 (each <= 2^8) in three HBM passes with 16-column tiles, all on the LDS-family kernels:
-//   pass 1 (ntt_pass_a, shape n1 x n/n1): as the first pass of a two-pass plan (coset pre-scale, twiddle w_N^(m'*(B*k1+j)));
-//   pass 2 (ntt_pass_a, shape 2^8 x n3 on each of the cosets*2^8 rows of n/2^8 points): twiddle w_{n/2^8}^(k2*m3);
-//   pass 3 (ntt_pass_b, n3 points, tile = 16 adjacent k1, one batch per k2): natural-order store at k1 + 2^8*(k2 + 2^8*k3).
-static void launch_three_pass(dst_ctx* c, const fe* src, size_t src_col_stride, size_t src_coset_stride,
-                              fe* dst, size_t dst_col_stride, size_t dst_coset_stride,
-                              size_t cosets, size_t cols, bool inverse, bool lde, uint32_t skip) {
+// A whole transform: the plan's passes in turn, through the staging buffers [column][coset][n] between them.
+// skip: number of leading local cosets left out (their outputs are produced elsewhere); io.dst points at the first coset computed
+static void ntt_transform(dst_ctx* c, const NttIo& io, size_t cosets, size_t cols, bool inverse, bool lde, uint32_t skip = 0, std::string* describe = nullptr) {
     const NttPlan& p = c->plan;
-    const uint32_t log_mid = p.log_n2 - p.log_n3;                      // 8
-    const size_t n = c->n, nrow = (size_t)1 << p.log_n2, n3 = (size_t)1 << p.log_n3, n1 = (size_t)1 << p.log_n1;
-    NttArgs a = ntt_common_args(c, inverse, lde, skip);
-    // pass 1: src -> tmp
-    a.log_n1 = p.log_n1; a.log_n2 = p.log_n2; a.tile = (uint32_t)__builtin_ctz(p.tile_a);
-    a.prescale = lde ? c->prescale : nullptr; a.has_scale = 0;
-    a.tw4 = lde ? c->tw4_lde + (size_t)skip * n : (inverse ? c->tw4_inv : c->tw4_fwd); a.tw4_coset_stride = lde ? n : 0;
-    a.stage_tw = inverse ? c->w1i : c->w1f;
-    const int mode = lde ? ntt_first_pass_mode(c, n1, p.tile_a) : 0;
-    a.dit = mode ? 1u : 0u; a.dit_last = mode == 2 ? c->dit_last : nullptr;
-    a.src = src; a.src_col_stride = src_col_stride; a.src_coset_stride = src_coset_stride;
-    a.dst = c->tmp; a.dst_col_stride = n * cosets; a.dst_coset_stride = n;
-    {
-        const uint32_t tiles = (uint32_t)(nrow / p.tile_a);
-        a.tiles_per_block = ntt_tiles_per_block(tiles, cosets * cols);
-        a.coset_fast = ntt_coset_fast(c, tiles / a.tiles_per_block, cosets);
-        const size_t lds = n1 * p.tile_a * sizeof(fe) + (mode == 1 ? n1 : n1 / 2) * sizeof(fe_tw);
-        ntt_launch(c, false, a, tiles / a.tiles_per_block, cosets, cols, lds, "ntt_pass_a", 16.0 * n * cols * (lde ? (1 + cosets) : 2 * cosets));
+    fe* const stage[2] = {c->tmp, c->tmp2};
+    for (uint32_t i = 0; i < p.count; i++) {
+        NttIo s = io;
+        if (i > 0) { s.src = stage[i - 1]; s.src_col_stride = c->n * cosets; s.src_coset_stride = c->n; }
+        if (i + 1 < p.count) { s.dst = stage[i]; s.dst_col_stride = c->n * cosets; s.dst_coset_stride = c->n; }
+        ntt_run_pass(c, p.at(i, lde), s, cosets, cols, inverse, lde, skip, describe);
     }
-    // pass 2: tmp -> tmp2, every (coset, k1) row of nrow points is an array of shape 2^log_mid x n3
-    a.log_n1 = log_mid; a.log_n2 = p.log_n3; a.tile = (uint32_t)__builtin_ctz(p.tile_m);
-    a.j0 = 0; a.prescale = nullptr; a.dit = 0; a.coset_fast = 0;
-    a.tw4 = inverse ? c->tw4_row_inv : c->tw4_row_fwd; a.tw4_coset_stride = 0;
-    a.stage_tw = inverse ? c->w2i : c->w2f;
-    a.src = c->tmp; a.src_col_stride = n * cosets; a.src_coset_stride = nrow;
-    a.dst = c->tmp2; a.dst_col_stride = n * cosets; a.dst_coset_stride = nrow;
-    {
-        const uint32_t tiles = (uint32_t)(n3 / p.tile_m);
-        const size_t rows = cosets * n1;
-        a.tiles_per_block = ntt_tiles_per_block(tiles, rows * cols);
-        const size_t lds = ((size_t)1 << log_mid) * p.tile_m * sizeof(fe) + (((size_t)1 << log_mid) / 2) * sizeof(fe_tw);
-        ntt_launch(c, false, a, tiles / a.tiles_per_block, rows, cols, lds, "ntt_pass_mid", 32.0 * n * cols * cosets);
-    }
-    // pass 3: tmp2 -> dst
-    a.log_n1 = p.log_n1; a.log_n2 = p.log_n3; a.tile = (uint32_t)__builtin_ctz(p.tile_b);
-    a.tw4 = nullptr; a.has_scale = inverse ? 1u : 0u;
-    a.stage_tw = inverse ? c->w3i : c->w3f;
-    a.src = c->tmp2; a.src_col_stride = n * cosets; a.src_coset_stride = n;
-    a.dst = dst; a.dst_col_stride = dst_col_stride; a.dst_coset_stride = dst_coset_stride;
-    a.src_row_stride = nrow; a.src_batch_stride = n3; a.batch_log = log_mid;
-    a.dst_k_stride = n1 << log_mid; a.dst_batch_stride = n1;
-    {
-        const uint32_t tiles = (uint32_t)(n1 / p.tile_b);
-        a.tiles_per_block = ntt_tiles_per_block(tiles, ((size_t)cosets << log_mid) * cols);
-        const size_t lds = n3 * p.tile_b * sizeof(fe) + (n3 / 2) * sizeof(fe_tw);
-        ntt_launch(c, true, a, (size_t)(tiles / a.tiles_per_block) << log_mid, cosets, cols, lds, "ntt_pass_b", 32.0 * n * cols * cosets);
-    }
-}
-
-// skip: number of leading local cosets left out (their outputs are produced elsewhere); dst points at the first coset computed
-static void launch_two_pass(dst_ctx* c, const fe* src, size_t src_col_stride, size_t src_coset_stride,
-                            fe* dst, size_t dst_col_stride, size_t dst_coset_stride,
-                            size_t cosets, size_t cols, bool inverse, bool lde, uint32_t skip = 0) {
-    if (c->plan.log_n3) { launch_three_pass(c, src, src_col_stride, src_coset_stride, dst, dst_col_stride, dst_coset_stride, cosets, cols, inverse, lde, skip); return; }
-    // pass A: src -> tmp, pass B: tmp -> dst
-    (c->plan.reg_a ? launch_pass_reg : launch_pass_lds)(c, false, src, src_col_stride, src_coset_stride, c->tmp, c->n * cosets, c->n, cosets, cols, inverse, lde, skip);
-    (c->plan.reg_b ? launch_pass_reg : launch_pass_lds)(c, true, c->tmp, c->n * cosets, c->n, dst, dst_col_stride, dst_coset_stride, cosets, cols, inverse, lde, skip);
 }
 
 // ---- four-step twiddle tables -------------------------------------------------------------------------------------------------------
@@ -819,22 +801,85 @@ __global__ void twiddle_table_kernel(tw4_t* out, const fe* tw_lo, const fe* tw_h
     out[(size_t)blockIdx.y * n + i] = dom_pow(tw_lo, tw_hi, lo_bits, e);
 #endif
 }
-int k_build_twiddle_tables(dst_ctx* c) {
-    const NttPlan& p = c->plan;
-    dim3 g((unsigned)((c->n + 255) / 256), (unsigned)c->Bc);
-    hipLaunchKernelGGL(twiddle_table_kernel, g, dim3(256), 0, c->stream, c->tw4_lde, c->tw_lo, c->tw_hi, c->tw_lo_bits, p.log_n2, c->log_n, c->log_b, c->log_N, (uint32_t)c->j0, 1u);
-    g.y = 1;
-    hipLaunchKernelGGL(twiddle_table_kernel, g, dim3(256), 0, c->stream, c->tw4_fwd, c->tw_lo, c->tw_hi, c->tw_lo_bits, p.log_n2, c->log_n, c->log_b, c->log_N, 0u, 0u);
-    hipLaunchKernelGGL(twiddle_table_kernel, g, dim3(256), 0, c->stream, c->tw4_inv, c->itw_lo, c->itw_hi, c->tw_lo_bits, p.log_n2, c->log_n, c->log_b, c->log_N, 0u, 0u);
-    if (p.log_n3) {       // middle pass of a three-pass plan: rows of n' = n2 points, w_{n'}^(k2*m3) = w_N^(m3 * (k2 << (log_b + log_n1)))
-        dim3 gr((unsigned)((((size_t)1 << p.log_n2) + 255) / 256), 1u);
-        hipLaunchKernelGGL(twiddle_table_kernel, gr, dim3(256), 0, c->stream, c->tw4_row_fwd, c->tw_lo, c->tw_hi, c->tw_lo_bits, p.log_n3, p.log_n2, c->log_b + p.log_n1, c->log_N, 0u, 0u);
-        hipLaunchKernelGGL(twiddle_table_kernel, gr, dim3(256), 0, c->stream, c->tw4_row_inv, c->itw_lo, c->itw_hi, c->tw_lo_bits, p.log_n3, p.log_n2, c->log_b + p.log_n1, c->log_N, 0u, 0u);
+// Context creation: the plan, the LDS limits of its kernels and every table the passes read.  The tables stay the context's (ctx.h); the
+// pass descriptions hold views of them.
+int k_ntt_init(dst_ctx* c) {
+    int r = ntt_plan_set(c);
+    if (r) return r;
+    NttPlan& pl = c->plan;
+    {   // tile + stage twiddles exceed the 64 KiB default.  Contexts of several ranks may run as threads of one process
+        // (dst_prove_sharded_local): the once-per-device marks are guarded
+        static std::mutex mu;
+        static bool raised[64] = {};
+        std::lock_guard<std::mutex> lock(mu);
+        if (c->device >= 0 && c->device < 64 && !raised[c->device]) {
+            for (const NttInstance& I : NTT_INSTANCES) HIP_TRY(c, hipFuncSetAttribute((const void*)I.kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
+            raised[c->device] = true;
+        }
     }
+    {
+        const fe w16 = h_root_of_unity(4);
+        const std::vector<fe> f = h_powers(w16, 8), b = h_powers(h_inv(w16), 8);
+        for (int j = 0; j < 8; j++) { c->c16f[j] = f[j]; c->c16i[j] = b[j]; }
+    }
+    for (uint32_t i = 0; i < pl.count; i++) {
+        NttPass& P = pl.pass[i];
+        const fe w = h_root_of_unity(P.log_len), wp = h_root_of_unity(P.log_len + 1);
+        for (int inv = 0; inv < 2; inv++) {
+            if ((r = dev_upload(c, &c->ntt_stage_tw[i][inv], h_powers_tw(inv ? h_inv(w) : w, (size_t)1 << (P.log_len - 1))))) return r;
+            if (P.pre && (r = dev_upload(c, &c->ntt_pre_tw[i][inv], h_powers_tw(inv ? h_inv(wp) : wp, (size_t)1 << P.log_len)))) return r;
+            P.stage_tw[inv] = c->ntt_stage_tw[i][inv]; P.pre_tw[inv] = c->ntt_pre_tw[i][inv];
+        }
+    }
+    {
+        const std::vector<fe_tw> pre = h_powers_tw(h_root_of_unity(c->log_b + pl.log_n1), (size_t)1 << (c->log_b + pl.log_n1));
+        if ((r = dev_upload(c, &c->prescale, pre))) return r;
+        // last-stage twiddles of the (half-length, with a pre-stage) coset DITs: [B][R][len / 2] entries pre[j + B * (h + R * k)]
+        const size_t R = (size_t)1 << pl.pass[0].pre, half = (size_t)1 << (pl.pass[0].log_len - 1);
+        std::vector<fe_tw> last(c->B * R * half);
+        for (size_t j = 0; j < c->B; j++) for (size_t h = 0; h < R; h++) for (size_t k = 0; k < half; k++) last[(j * R + h) * half + k] = pre[j + c->B * (h + R * k)];
+        if ((r = dev_upload(c, &c->dit_last, last))) return r;
+    }
+    if ((r = dev_alloc(c, &c->tw4_lde, c->Bc * c->n))) return r;
+    if ((r = dev_alloc(c, &c->tw4_fwd, c->n))) return r;
+    if ((r = dev_alloc(c, &c->tw4_inv, c->n))) return r;
+    pl.pass[0].tw4[0] = c->tw4_fwd; pl.pass[0].tw4[1] = c->tw4_inv;
+    dim3 g((unsigned)((c->n + 255) / 256), (unsigned)c->Bc);
+    hipLaunchKernelGGL(twiddle_table_kernel, g, dim3(256), 0, c->stream, c->tw4_lde, c->tw_lo, c->tw_hi, c->tw_lo_bits, pl.log_n2, c->log_n, c->log_b, c->log_N, (uint32_t)c->j0, 1u);
+    g.y = 1;
+    hipLaunchKernelGGL(twiddle_table_kernel, g, dim3(256), 0, c->stream, c->tw4_fwd, c->tw_lo, c->tw_hi, c->tw_lo_bits, pl.log_n2, c->log_n, c->log_b, c->log_N, 0u, 0u);
+    hipLaunchKernelGGL(twiddle_table_kernel, g, dim3(256), 0, c->stream, c->tw4_inv, c->itw_lo, c->itw_hi, c->tw_lo_bits, pl.log_n2, c->log_n, c->log_b, c->log_N, 0u, 0u);
+    if (pl.count == 3) {  // middle pass of a three-pass plan: rows of n' = n2 points, w_{n'}^(k2*m3) = w_N^(m3 * (k2 << (log_b + log_n1)))
+        if ((r = dev_alloc(c, &c->tw4_row_fwd, (size_t)1 << pl.log_n2))) return r;
+        if ((r = dev_alloc(c, &c->tw4_row_inv, (size_t)1 << pl.log_n2))) return r;
+        pl.pass[1].tw4[0] = c->tw4_row_fwd; pl.pass[1].tw4[1] = c->tw4_row_inv;
+        dim3 gr((unsigned)((((size_t)1 << pl.log_n2) + 255) / 256), 1u);
+        hipLaunchKernelGGL(twiddle_table_kernel, gr, dim3(256), 0, c->stream, c->tw4_row_fwd, c->tw_lo, c->tw_hi, c->tw_lo_bits, pl.log_n3, pl.log_n2, c->log_b + pl.log_n1, c->log_N, 0u, 0u);
+        hipLaunchKernelGGL(twiddle_table_kernel, gr, dim3(256), 0, c->stream, c->tw4_row_inv, c->itw_lo, c->itw_hi, c->tw_lo_bits, pl.log_n3, pl.log_n2, c->log_b + pl.log_n1, c->log_N, 0u, 0u);
+    }
+    for (int inv = 0; inv < 2; inv++) { pl.first_lde.stage_tw[inv] = pl.pass[0].stage_tw[inv]; pl.first_lde.pre_tw[inv] = pl.pass[0].pre_tw[inv]; }   // its four-step table is tw4_lde
     HIP_TRY(c, hipStreamSynchronize(c->stream));
     HIP_TRY(c, hipGetLastError());
     return DST_OK;
 }
+
+#if DST_TEST_HOOKS
+// Test build only: the launches a transform of this size and shape would make under the current DISTAFF_NTT_* switches, one line each.  The plan comes
+// from ntt_plan_derive and the lines from ntt_run_pass itself with launching turned off; no device is touched and nothing is allocated.
+extern "C" __attribute__((visibility("default"))) int dst_ntt_describe(uint32_t log_n, uint32_t log_blowup, int inverse, int lde, uint32_t cosets, uint32_t cols, uint32_t skip, char* out, size_t cap) {
+    if (!out || log_n < 4 || log_n > 24 || log_blowup < 4 || log_blowup > 8 || !cosets || !cols) return DST_ERR_ARG;
+    dst_ctx c;
+    c.read_switches();
+    c.log_n = log_n; c.log_b = log_blowup; c.log_N = log_n + log_blowup;
+    c.n = (size_t)1 << log_n; c.B = c.Bc = (size_t)1 << log_blowup; c.N = c.n * c.B;
+    if (int r = ntt_plan_set(&c)) return r;
+    std::string text;
+    ntt_transform(&c, NttIo{}, cosets, cols, inverse != 0, lde != 0, skip, &text);
+    if (text.size() + 1 > cap) return DST_ERR_ARG;
+    memcpy(out, text.c_str(), text.size() + 1);
+    return DST_OK;
+}
+#endif
 
 // how many (coset x column) size-n arrays fit in c->tmp
 static size_t tmp_capacity_arrays(const dst_ctx* c) { return c->Bc * c->tmp_regs; }
@@ -843,7 +888,7 @@ void k_intt_columns(dst_ctx* c, const fe* src, size_t src_stride, fe* dst, size_
     size_t cap = tmp_capacity_arrays(c);
     for (size_t done = 0; done < ncols;) {
         size_t cols = ncols - done < cap ? ncols - done : cap;
-        launch_two_pass(c, src + done * src_stride, src_stride, 0, dst + done * c->n, c->n, 0, 1, cols, true, false);
+        ntt_transform(c, {src + done * src_stride, src_stride, 0, dst + done * c->n, c->n, 0}, 1, cols, true, false);
         done += cols;
     }
 }
@@ -862,7 +907,7 @@ void k_lde_columns(dst_ctx* c, const fe* polys, fe* lde, size_t ncols) {
         const size_t cols = ncols - done < bcols ? ncols - done : bcols;
         for (size_t s = skip; s < c->Bc;) {
             const size_t cc = c->Bc - s < bcos ? c->Bc - s : bcos;
-            launch_two_pass(c, polys + done * c->n, c->n, 0, lde + done * c->Bc * c->n + s * c->n, c->Bc * c->n, c->n, cc, cols, false, true, (uint32_t)s);
+            ntt_transform(c, {polys + done * c->n, c->n, 0, lde + done * c->Bc * c->n + s * c->n, c->Bc * c->n, c->n}, cc, cols, false, true, (uint32_t)s);
             s += cc;
         }
         done += cols;
@@ -959,7 +1004,7 @@ void k_lde_fold8(dst_ctx* c, const fe* poly8n, fe* out) {
     else if (all_cosets && c->B == 256) FOLD8_DFT(32)
     else { KScope ks_(c, "fold8_kernel", bytes); hipLaunchKernelGGL(fold8_kernel, g, dim3(256), c->Bc * 8 * sizeof(fe), c->stream, poly8n, out, c->tw_lo, c->tw_hi, c->tw_lo_bits, c->log_n, c->log_N, (uint32_t)c->j0, (uint32_t)c->Bc); }
 #undef FOLD8_DFT
-    launch_two_pass(c, out, 0, c->n, out, 0, c->n, c->Bc, 1, false, false);
+    ntt_transform(c, {out, 0, c->n, out, 0, c->n}, c->Bc, 1, false, false);
 }
 
 // ---- inverse transform of size 8n from coset-major input ------------------------------------------------------------------
@@ -1078,16 +1123,12 @@ void k_combine_fused(dst_ctx* c, const fe* work, const fe* q4, size_t q_stride, 
 
 // the two halves of k_intt8_cosets for the sharded prover: a rank inverts the size-n transforms of the evaluation cosets it owns BEFORE the
 // exchange (1/world of them instead of all eight on every rank), the 8-point step across cosets follows on the gathered arrays
-void k_intt_cosets_local(dst_ctx* c, fe* vals, fe* out, size_t cosets) { launch_two_pass(c, vals, 0, c->n, out, 0, c->n, cosets, 1, true, false); }
+void k_intt_cosets_local(dst_ctx* c, fe* vals, fe* out, size_t cosets) { ntt_transform(c, {vals, 0, c->n, out, 0, c->n}, cosets, 1, true, false); }
 void k_cross8(dst_ctx* c, const fe* work, fe* out8n) {
-    { KScope ks_(c, "cross8_kernel", 256.0 * c->n); hipLaunchKernelGGL(cross8_kernel, dim3((unsigned)((c->n + 255) / 256)), dim3(256), 0, c->stream, work, out8n,
-                       c->itw_lo, c->itw_hi, c->tw_lo_bits, c->log_n, c->log_N, c->log_b, c->eight_inv); }
+    KScope ks_(c, "cross8_kernel", 256.0 * c->n);
+    hipLaunchKernelGGL(cross8_kernel, dim3((unsigned)((c->n + 255) / 256)), dim3(256), 0, c->stream, work, out8n, c->itw_lo, c->itw_hi, c->tw_lo_bits, c->log_n, c->log_N, c->log_b, c->eight_inv);
 }
-void k_intt8_cosets(dst_ctx* c, fe* vals, fe* out8n, fe* work) {
-    launch_two_pass(c, vals, 0, c->n, work, 0, c->n, 8, 1, true, false);
-    { KScope ks_(c, "cross8_kernel", 256.0 * c->n); hipLaunchKernelGGL(cross8_kernel, dim3((unsigned)((c->n + 255) / 256)), dim3(256), 0, c->stream, (const fe*)work, out8n,
-                       c->itw_lo, c->itw_hi, c->tw_lo_bits, c->log_n, c->log_N, c->log_b, c->eight_inv); }
-}
+void k_intt8_cosets(dst_ctx* c, fe* vals, fe* out8n, fe* work) { k_intt_cosets_local(c, vals, work, 8); k_cross8(c, work, out8n); }
 
 // ---- layout conversion (inspection; replicated FRI tail of the sharded path) ------------------------------------------------------------------------------------
 __global__ void coset_to_natural_kernel(const fe* __restrict__ src, fe* __restrict__ dst, size_t n, size_t cosets) {
@@ -1100,4 +1141,3 @@ void k_coset_to_natural_len(dst_ctx* c, const fe* src, size_t cosets, size_t len
     size_t total = len * cosets;
     { KScope ks_(c, "coset_to_natural_kernel", 32.0 * total); hipLaunchKernelGGL(coset_to_natural_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, c->stream, src, dst, len, cosets); }
 }
-void k_coset_to_natural(dst_ctx* c, const fe* src, size_t cosets, fe* dst) { k_coset_to_natural_len(c, src, cosets, c->n, dst); }

@@ -144,6 +144,17 @@ def load_hooks():
     return _hooks_lib
 
 
+def ntt_describe(log_n, log_blowup, inverse, lde, cosets, cols, skip=0, lib=None):
+    """dst_ntt_describe (test build only): one line per kernel launch a transform of this size and shape would make under the DISTAFF_NTT_*
+    switches as the environment has them now -- instance, block, grid, LDS bytes, what the launch layer decided.  Touches no device."""
+    buf = ctypes.create_string_buffer(4096)
+    r = (lib or load_hooks()).dst_ntt_describe(ctypes.c_uint32(log_n), ctypes.c_uint32(log_blowup), ctypes.c_int(int(inverse)), ctypes.c_int(int(lde)),
+                                               ctypes.c_uint32(cosets), ctypes.c_uint32(cols), ctypes.c_uint32(skip), buf, ctypes.c_size_t(len(buf)))
+    if r != DST_OK:
+        raise DistaffError(r, "dst_ntt_describe(%d, %d) failed" % (log_n, log_blowup))
+    return buf.value.decode().splitlines()
+
+
 def _ptr(a):
     return a.ctypes.data_as(ctypes.c_void_p)
 

@@ -27,11 +27,13 @@ def _exports(path):
 
 
 def test_libraries_export_exactly_the_declared_entry_points():
-    """hidden visibility: no dst_internal_* hook, no helper leaves either library; every declaration of include/distaff_hip.h is defined"""
+    """hidden visibility: no dst_internal_* hook, no helper leaves either library; every declaration of include/distaff_hip.h is defined.
+    The test build adds exactly one entry point that the header does not declare: dst_ntt_describe (kernels_ntt.hip), the launch layer's
+    account of itself for tests/test_ntt_launch_plan.py."""
     declared = _declared()
-    assert len(declared) > 50
-    for name in ("libdistaff_hip.so", "libdistaff_hip_hooks.so"):
-        assert _exports(os.path.join(ROOT, "distaff_amd", name)) == declared, name
+    assert len(declared) > 50 and "dst_ntt_describe" not in declared
+    assert _exports(os.path.join(ROOT, "distaff_amd", "libdistaff_hip.so")) == declared
+    assert _exports(os.path.join(ROOT, "distaff_amd", "libdistaff_hip_hooks.so")) == declared | {"dst_ntt_describe"}
 
 
 def test_product_and_test_build_identify_themselves():

@@ -814,18 +814,24 @@ __global__ void field_op_kernel(int op, const fe* a, const fe* b, fe* out, size_
         case 3: r = fe_mul_portable(x, y); break;
         case 4: r = fe_inv(x); break;
         case 5: r = fe_pow(x, y); break;
-        case 6: {   // sum_{j<40} a[(i + j) % count] * b[(i + 7j) % count] + a[i], one reduction (fe_acc)
+        case 7: r = fe_mul_tw(x, y, fe_shift64(y)); break;      // x any 128-bit value, y canonical
+        case 8: r = fe_shift64(x); break;
+        case 9: case 10: { fe s, d; fe_addsub(x, y, s, d); r = op == 9 ? s : d; break; }
+        case 11: r = fe_mul_small(x, y.v[0]); break;
+        case 12: r = fe_sqr(x); break;
+        case 13: r = fe_cube(x); break;
+        default: {  // 6 (T = 40) and 256 + T: sum_{j<T} a[(i + j) % count] * b[(i + 7j) % count] + a[i], one reduction (fe_acc)
+            const size_t terms = op == 6 ? 40 : (size_t)(op - 256);
             fe_acc A; fe_acc_zero(A);
-            for (size_t j = 0; j < 40; j++) fe_acc_mac(A, a[(i + j) % count], b[(i + 7 * j) % count]);
+            for (size_t j = 0; j < terms; j++) fe_acc_mac(A, a[(i + j) % count], b[(i + 7 * j) % count]);
             fe_acc_add(A, x);
             r = fe_acc_reduce(A);
-            break;
         }
-        default: r = fe_zero();
     }
     out[i] = r;
 }
 int k_field_op(dst_ctx* c, int op, const uint8_t* a, const uint8_t* b, uint8_t* out, size_t count) {
+    if (!((op >= 0 && op <= 13) || (op > 256 && op <= 256 + 64))) { c->err = "dst_field_op: unknown operation (0 .. 13, 256 + T with T in 1 .. 64)"; return DST_ERR_ARG; }
     if (3 * count > c->scratch_elems - 2048) { c->err = "dst_field_op: too many elements"; return DST_ERR_ARG; }
     fe* da = c->scratch; fe* db = da + count; fe* dout = db + count;
     HIP_TRY(c, hipMemcpyAsync(da, a, count * 16, hipMemcpyHostToDevice, c->stream));

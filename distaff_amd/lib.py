@@ -847,7 +847,9 @@ class Context:
         return json.loads(buf.value.decode())
 
     def field_op(self, op, a, b):
-        ops = {"add": 0, "sub": 1, "mul": 2, "mul_portable": 3, "inv": 4, "pow": 5, "dot40": 6}
+        ops = {"add": 0, "sub": 1, "mul": 2, "mul_portable": 3, "inv": 4, "pow": 5, "dot40": 6, "mul_tw": 7, "shift64": 8, "addsub_sum": 9, "addsub_dif": 10,
+               "mul_small": 11, "sqr": 12, "cube": 13}
+        ops.update({"dot%d" % t: 256 + t for t in range(1, 65) if t != 40})        # dotT: the sum of dot40 over T terms
         a = np.ascontiguousarray(a, dtype=np.uint64); b = np.ascontiguousarray(b, dtype=np.uint64)
         out = np.zeros_like(a)
         self._check(self.lib.dst_field_op(self._h, ops[op], _ptr(a), _ptr(b), _ptr(out), ctypes.c_size_t(a.shape[0])))

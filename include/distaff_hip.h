@@ -262,7 +262,11 @@ DST_API int dst_bench_clock(dst_ctx* ctx, uint64_t lanes, uint32_t iters, double
  * their instruction-cache lines) -- whether that form would help on the device at hand.
  * (Test / bench build only: the product library returns DST_ERR_STATE.) */
 DST_API int dst_bench_code(dst_ctx* ctx, uint32_t code_kib, double* ms);
-/* element-wise device field arithmetic on caller data (tests): op 0 add, 1 sub, 2 mul, 3 mul (portable formulation), 4 inv(a), 5 a^b */
+/* element-wise device field arithmetic on caller data (tests): op 0 add, 1 sub, 2 mul, 3 mul (portable formulation), 4 inv(a), 5 a^b,
+ * 6 sum_{j<40} a[(i+j) % count] * b[(i+7j) % count] + a[i] with one reduction, 7 a * b as a multiplication by the table entry
+ * (b, b * 2^64) (a: any 128-bit value, b canonical), 8 a * 2^64, 9 / 10 the sum / the difference of one sum-and-difference pair,
+ * 11 a * (low 32 bits of b), 12 a^2, 13 a^3, 256 + T (T = 1 .. 64): the sum of op 6 over T terms instead of 40.  Every operation is one
+ * call of the device function on the operands as given (no check that they are canonical); any other op is DST_ERR_ARG. */
 DST_API int dst_field_op(dst_ctx* ctx, int op, const uint8_t* a, const uint8_t* b, uint8_t* out, size_t count);
 /* per-kernel timing with HIP events on the context's stream.  level 0: off; 1: every kernel launch is bracketed (costs ~5 % of a
  * proof: ~300 launches lose their back-to-back issue); 2: only the heavy kernels (NTT passes, constraint kernel, leaf hashing:

@@ -3,8 +3,10 @@
 libdistaff_emu.so is the library's own sources (distaff_amd/csrc/*.hip) compiled by g++ against a stand-in HIP header in which a
 kernel launch is executed on the host, one fiber per work-item (tests/emu/hip/hip_runtime.h).  It is test infrastructure: the
 package never picks it up by itself (it is selected here, in a subprocess, through DISTAFF_HIP_LIB), `bench.py`, `smoke()` and the
-`-m gpu` run use libdistaff_hip.so on the device, and the gfx950 formulation of the field arithmetic is NOT exercised by it (the
-host branch of fe.h is) -- that part is pinned on the GPU by test_device_field_arithmetic.  What it does pin, where there is no
+`-m gpu` run use libdistaff_hip.so on the device, and the gfx950 INSTRUCTIONS of the field arithmetic are NOT exercised by it (the
+plain-integer form of fe.h's carry primitives is, with the limb-level dataflow of the gfx950 formulations: -DFE_EMULATE_GFX950) --
+the device form is pinned on the GPU by tests/test_field_directed.py (every fe.h function on operands directed at the rare branches of
+its reductions; the same file runs here first, on the dataflow) and by test_device_field_arithmetic.  What it does pin, where there is no
 GPU: tile / twiddle / tree-level indexing of every kernel, the constraint instances, the sharded layouts and exchanges, the opening
 plan and the wire format -- the same assertions as on the GPU, bit for bit against the oracle."""
 import os
@@ -67,6 +69,9 @@ SELECTION = WHOLE_DOMAIN + [
     "test_lde_every_tile_length[lds-13-5]",
     "test_lde_every_tile_length[dit2-13-5]",
     "test_lde_every_tile_length[waves8-13-5]",
+    "test_structured_columns_through_the_transforms[reg-13-5]",
+    "test_structured_columns_through_the_transforms[lds-13-5]",
+    "test_structured_columns_through_the_transforms[dit2-13-5]",
     "test_lde_every_tile_length[lds-16-5]",
     "test_trace_from_pinned_host_memory[w17]",
     "test_synthetic_division_by_power_tables",
@@ -123,6 +128,15 @@ def test_arbitrary_rows_and_the_widest_trace_on_the_emulated_build(emulated_libr
     out = r.stdout.decode()
     assert r.returncode == 0, out[-4000:]
     assert "33 passed" in out, out[-2000:]                               # 23 uniform cases + 8 prefix cases + 2
+
+
+def test_directed_field_arithmetic_on_the_emulated_build(emulated_library):
+    """tests/test_field_directed.py as a whole: the limb-level dataflow of every fe.h function behind dst_field_op meets the directed
+    classes on the CPU first (which also validates the vectors and the hook's plumbing); on the GPU the same file pins the instructions."""
+    r = _run(emulated_library, ["tests/test_field_directed.py"])
+    out = r.stdout.decode()
+    assert r.returncode == 0, out[-4000:]
+    assert "41 passed" in out, out[-2000:]                               # 11 operations and 6 term counts in 2 lane layouts, 6 maximal sums, 1
 
 
 def test_whole_domain_parity_on_the_emulated_build(emulated_library):

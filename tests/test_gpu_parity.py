@@ -782,6 +782,96 @@ def test_lde_every_tile_length(oracle, monkeypatch, family, log_n, log_blowup):
     assert (lde[::B] == cols[c]).all()                                 # coset 0 of the extension is the trace itself
 
 
+_STRUCTURED = {}
+
+
+def _structured_columns(O, log_n, log_blowup, W=16):
+    """-> (columns [W, n, 2], {column: (coefficients, extension) in closed form}); computed once and shared.  Columns that uniform data never
+    gives: constants (0, 1, p - 1), an impulse at row 0 and one at row n - 1, alternating 0 / p - 1 and p - 1 / 1, the monomials
+    g_n^(i m) for m = 1, n / 2, n - 1; the rest uniform.  Whole stages of butterflies see x + y == p, x - x and products with p - 1 at once.
+    Closed forms (Python integers): a constant c is the polynomial c; x^m extends to g_N^(i m); an impulse v at row r has the
+    coefficients v / n * g_n^(-j r), and at z = g_N^(i - r B) != 1 the value v / n * (z^n - 1) / (z - 1), z^n = (g_N^n)^(i mod B)."""
+    key = (log_n, log_blowup, W)
+    if key in _STRUCTURED:
+        return _STRUCTURED[key]
+    P = O.P
+    n, B = 1 << log_n, 1 << log_blowup
+    N = n * B
+    g_n, g_N = O.root_of_unity(n), O.root_of_unity(N)
+    assert pow(g_N, B, P) == g_n and pow(g_n, n // 2, P) == P - 1
+
+    def powers(base, count):
+        out, x = [], 1
+        for _ in range(count):
+            out.append(x)
+            x = x * base % P
+        return out
+    w_n, w_N = powers(g_n, n), powers(g_N, N)
+    n_inv = pow(n, -1, P)
+    ints, closed = {}, {}
+    for c, v in enumerate((0, 1, P - 1)):
+        ints[c] = [v] * n
+        closed[c] = ([v] + [0] * (n - 1), [v] * N)
+    for c, r, v in ((3, 0, 1), (4, n - 1, P - 1)):
+        ints[c] = [v if k == r else 0 for k in range(n)]
+        scale = v * n_inv % P
+        z = [w_N[(i - r * B) % N] for i in range(N)]
+        inv, acc = [0] * N, 1                                            # 1 / (z - 1) for every z != 1 with one inversion
+        for i in range(N):
+            if z[i] != 1:
+                inv[i], acc = acc, acc * (z[i] - 1) % P
+        acc = pow(acc, -1, P)
+        for i in reversed(range(N)):
+            if z[i] != 1:
+                inv[i], acc = inv[i] * acc % P, acc * (z[i] - 1) % P
+        root_B = powers(w_N[n], B)                                       # z^n
+        closed[c] = ([scale * w_n[(-j * r) % n] % P for j in range(n)],
+                     [v if z[i] == 1 else scale * (root_B[i % B] - 1) * inv[i] % P for i in range(N)])
+    ints[5] = [0, P - 1] * (n // 2)
+    ints[6] = [P - 1, 1] * (n // 2)
+    for c, m in ((7, 1), (8, n // 2), (9, n - 1)):
+        ints[c] = [w_n[k * m % n] for k in range(n)]
+        closed[c] = ([int(j == m) for j in range(n)], [w_N[i * m % N] for i in range(N)])
+    cols = _random_columns(W, n, 4000 + log_n)
+    for c, col in ints.items():
+        cols[c] = O.to_arr(col)
+    _STRUCTURED[key] = cols, {c: (O.to_arr(poly), O.to_arr(lde)) for c, (poly, lde) in closed.items()}
+    return _STRUCTURED[key]
+
+
+@pytest.mark.parametrize("family,log_n,log_blowup", [("reg", 13, 5), ("lds", 13, 5), ("dit2", 13, 5)])
+def test_structured_columns_through_the_transforms(oracle, monkeypatch, family, log_n, log_blowup):
+    """Interpolation and extension of columns with structure (see _structured_columns) through the register family, the LDS family and
+    the coset DIT: every element of every column against the coefficients by the oracle's sum identity, and the constant, impulse and
+    monomial columns against their closed forms, bit for bit."""
+    import distaff_amd as D
+    O = oracle
+    n, B, W = 1 << log_n, 1 << log_blowup, 16
+    cols, closed = _structured_columns(O, log_n, log_blowup, W)
+    for k in ("DISTAFF_NTT", "DISTAFF_NTT_DIF", "DISTAFF_NTT_WAVES", "DISTAFF_NTT_ORDER", "DISTAFF_NTT_FIXED"):
+        monkeypatch.delenv(k, raising=False)
+    if family == "dit2":
+        monkeypatch.setenv("DISTAFF_NTT_DIF", "2")
+    else:
+        monkeypatch.setenv("DISTAFF_NTT", family)
+    ctx = D.Context(log_n, W, 0, 0, log_blowup=log_blowup)
+    ctx.upload(cols)
+    ctx.commit_trace()
+    polys = ctx.read_elements("polys").reshape(W, n, 2)
+    ldes = [ctx.read_elements("lde", c) for c in range(W)]
+    ctx.close()
+    rng = np.random.default_rng(40 + log_n)
+    for c in range(W):
+        res = O.check_evaluations(polys[c], cols[c], int.from_bytes(rng.bytes(16), "little") % O.P)
+        assert res[0] == -1, ("interpolation", c) + res
+        res = O.check_evaluations(polys[c], ldes[c], int.from_bytes(rng.bytes(16), "little") % O.P)
+        assert res[0] == -1, ("extension", c) + res
+        assert (ldes[c][::B] == cols[c]).all(), ("coset 0", c)
+    for c, (poly, lde) in closed.items():
+        assert (polys[c] == poly).all(), ("coefficients in closed form", c, np.argwhere(polys[c] != poly)[:3].tolist())
+        assert (ldes[c] == lde).all(), ("extension in closed form", c, np.argwhere(ldes[c] != lde)[:3].tolist())
+
+
 def test_config3_full_size_proof_is_accepted_and_tamper_evident(oracle):
     """BASELINE config 3 at full size (2^20-step Fibonacci trace, default ProofOptions).  The oracle cannot produce this proof in
     seconds, so the checks are size-independent: the oracle's restatement of the reference verifier accepts the GPU proof for the

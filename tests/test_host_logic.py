@@ -124,7 +124,8 @@ def test_limb_level_field_arithmetic_on_the_host(tmp_path):
     """fe.h's gfx950 formulations (windowed and table-pair multiplication, the nine-limb reduction with its overflow limb, sum/difference
     pairs, sums of products) are written over carry primitives that have a plain-integer host form: tools/felab/host_test.cpp runs
     that dataflow on 6 million random and edge-case operands against the portable multiplication, which the oracle tests pin.  (The
-    device form of the same primitives -- one instruction each -- is pinned on the GPU by test_device_field_arithmetic.)"""
+    device form of the same primitives -- one instruction each -- is pinned on the GPU by tests/test_field_directed.py, on operands directed
+    at the branches that uniform ones never reach, and by test_device_field_arithmetic.)"""
     import os, subprocess
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     exe = tmp_path / "fe_host_test"

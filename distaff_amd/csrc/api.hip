@@ -1,5 +1,5 @@
 // C-ABI of libdistaff_hip.so (include/distaff_hip.h): context, tables, the prover phases and proof assembly.  The verifier (verify/), the
-// shared prover steps (host/steps_impl.h) and the Rescue trees (host/rtree_impl.h) are host code compiled with this unit.
+// shared prover steps (host/steps_impl.h) and the Rescue trees (host/rtree_impl.h, host/stree_impl.h) are host code compiled with this unit.
 // The phase order and every Fiat-Shamir dependency follow stark::prove (/root/reference/src/stark/prover.rs:17-168).
 #include <algorithm>
 #include <cstdio>
@@ -619,6 +619,8 @@ int dst_proof_info(const uint8_t* proof, size_t len, dst_proof_info_t* info) {
 
 // ---- Rescue digests and Rescue Merkle trees (dst_rescue_digest_many, dst_rtree_*): no context, compiled with this unit ---------------------
 #include "host/rtree_impl.h"
+// ---- sparse Rescue Merkle trees (dst_stree_*): the same, over keys of up to 63 bits ----------------------------------------------------------
+#include "host/stree_impl.h"
 
 // ---- inspection --------------------------------------------------------------------------------------------------------------------
 int dst_read_buffer(dst_ctx* c, uint32_t what, uint32_t arg, uint8_t* out, size_t cap, size_t* len) {

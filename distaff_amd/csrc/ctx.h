@@ -405,3 +405,9 @@ int k_rescue_tree(hipStream_t stream, fe* nodes /* 2 elements per node, leaf lev
 int k_rescue_tree_update(hipStream_t stream, fe* nodes, uint32_t log_leaves, const uint32_t* lists /* device */, const size_t* off, const size_t* cnt);
 int k_rescue_tree_scatter(hipStream_t stream, fe* nodes, const uint32_t* pos /* device */, const fe* vals /* 2 per node */, size_t count);   // nodes[pos[i]] = vals[i]
 int k_rescue_tree_gather(hipStream_t stream, const fe* nodes, const uint32_t* pos /* device */, fe* out /* 2 per node */, size_t count);       // out[i] = nodes[pos[i]]
+// sparse trees (host/stree_levels.h): all levels in one node array and one prefix array (device), indexed by flat positions.  One level: the `count`
+// parents at list[..] (device; nullptr: pstart + [0, count)) from the child level [cstart, cstart + ccnt); empty = the value of an empty child (host)
+int k_rescue_stree_level(hipStream_t stream, fe* nodes, const uint64_t* pref, const uint32_t* list, size_t count, size_t pstart, size_t cstart, size_t ccnt, const fe* empty);
+int k_rescue_stree_carry(hipStream_t stream, fe* dst, const fe* src, const uint32_t* from /* device */, size_t count);     // dst[j] = src[from[j]] unless from[j] == STREE_NEW
+// out[(i * (depth + 1) + k) ..] = node k of the path of indices[i], stored or empty; levels = (start, length) per level, empties = 2 elements per level (device)
+int k_rescue_stree_open(hipStream_t stream, const fe* nodes, const uint64_t* pref, const uint64_t* levels, const fe* empties, const uint64_t* indices, fe* out, size_t count, uint32_t depth);

@@ -82,8 +82,9 @@ int dst_rescue_digest_many(int device, const uint8_t* in, size_t count, uint8_t*
     return DST_OK;
 }
 
-// selects the tree's device; its stream and events on the first call, and at least `bytes` of device staging
-static int rtree_stage(const dst_rtree* t, size_t bytes) {
+// selects the tree's device; its stream and events on the first call, and at least `bytes` of device staging (T: dst_rtree, dst_stree)
+template <class T>
+static int rtree_stage(const T* t, size_t bytes) {
     RT_HIP(t->err, hipSetDevice(t->device));
     if (!t->stream) RT_HIP(t->err, hipStreamCreateWithFlags(&t->stream, hipStreamNonBlocking));
     if (!t->ev[0]) RT_HIP(t->err, hipEventCreate(&t->ev[0]));
@@ -96,7 +97,8 @@ static int rtree_stage(const dst_rtree* t, size_t bytes) {
     return DST_OK;
 }
 // ev[0] .. ev[1] of the stream, which has been synchronised
-static int rtree_elapsed(const dst_rtree* t, double* ms) {
+template <class T>
+static int rtree_elapsed(const T* t, double* ms) {
     float f = 0;
     RT_HIP(t->err, hipEventElapsedTime(&f, t->ev[0], t->ev[1]));
     *ms = f;
@@ -276,6 +278,14 @@ int dst_rtree_path(const dst_rtree* t, uint64_t index, uint8_t* path) {
     if (!path) return rt_fail(t, DST_ERR_ARG, "null pointer");
     return rtree_paths(t, &index, 1, path);
 }
+// the tapes of `count` paths of n nodes each, `each` elements per tape and path (dense and sparse trees)
+static void tapes_from_paths(const u128* paths, size_t n, const uint64_t* indices, size_t count, uint32_t what, size_t each, uint8_t* tape_a, uint8_t* tape_b) {
+    std::vector<u128> a, b;
+    for (size_t i = 0; i < count; i++) {
+        rescue_tapes(paths + 2 * n * i, n, indices[i], what, a, b);
+        memcpy(tape_a + 16 * each * i, a.data(), 16 * each); memcpy(tape_b + 16 * each * i, b.data(), 16 * each);
+    }
+}
 // generate_program_inputs (src/examples/merkle.rs:63-94) for `count` leaves; `size_name`: what the entry calls its size output
 static int rtree_tapes(const dst_rtree* t, const uint64_t* indices, size_t count, uint32_t what, uint8_t* tape_a, uint8_t* tape_b, size_t cap_each, size_t* each_out,
                        const char* size_name) {
@@ -291,11 +301,7 @@ static int rtree_tapes(const dst_rtree* t, const uint64_t* indices, size_t count
     try {
         std::vector<u128> paths(2 * n * count);
         if (int r = rtree_paths(t, indices, count, (uint8_t*)paths.data())) return r;
-        std::vector<u128> a, b;
-        for (size_t i = 0; i < count; i++) {
-            rescue_tapes(paths.data() + 2 * n * i, n, indices[i], what, a, b);
-            memcpy(tape_a + 16 * each * i, a.data(), 16 * each); memcpy(tape_b + 16 * each * i, b.data(), 16 * each);
-        }
+        tapes_from_paths(paths.data(), n, indices, count, what, each, tape_a, tape_b);
     } catch (const std::bad_alloc&) { return rt_fail(t, DST_ERR_HIP, "out of host memory"); }
     return DST_OK;
 }

@@ -1,0 +1,234 @@
+// Sparse Rescue Merkle trees behind dst_stree_*: the dense tree of rtree_impl.h over 2^depth leaves in which every leaf that was never set holds
+// the tree's empty leaf, stored as the nodes with a set leaf below them only (host/stree_levels.h has the layout and the plan of a set; the
+// kernels are in kernels_hash.hip).  Included by api.hip after rtree_impl.h, whose stream / staging / error helpers it shares.
+#pragma once
+#include "rtree_impl.h"
+#include "stree_levels.h"
+
+struct dst_stree {
+    int device = -1;                      // < 0: the nodes live in `host`
+    uint32_t depth = 0;
+    u128 empties[2 * (STREE_MAX_DEPTH + 1)] = {0};      // E_l, the value of an empty subtree of level l, at empties[2 l ..); E_depth = the empty leaf
+    stree_shape shape;                    // every level's prefixes; of a device tree too: sets are planned on the host
+    std::vector<u128> host;               // the node values at the shape's flat positions, 2 elements per node
+    uint8_t* dev = nullptr;               // one allocation per set: [nodes 32 * total][empties 32 * 64][levels 16 * 64][prefixes 8 * total]
+    uint64_t last_digests = 0;
+    double last_ms = 0;                   // events around the level launches of the last set
+    bool broken = false;                  // a HIP error inside dst_stree_set: only destroy / last_error remain
+    mutable hipStream_t stream = nullptr;
+    mutable hipEvent_t ev[2] = {nullptr, nullptr};
+    mutable uint8_t* stage = nullptr; mutable size_t stage_bytes = 0;
+    mutable std::string err;
+    fe* dev_nodes() const { return reinterpret_cast<fe*>(dev); }
+    fe* dev_empties() const { return reinterpret_cast<fe*>(dev + 32 * shape.total()); }
+    uint64_t* dev_levels() const { return reinterpret_cast<uint64_t*>(dev + 32 * shape.total() + 2048); }
+    uint64_t* dev_pref() const { return dev_levels() + 128; }
+    ~dst_stree() {
+        if (device < 0) return;
+        (void)hipSetDevice(device);
+        if (dev) hipFree(dev);
+        if (stage) hipFree(stage);
+        for (hipEvent_t e : ev) if (e) hipEventDestroy(e);
+        if (stream) hipStreamDestroy(stream);
+    }
+};
+static thread_local std::string g_stree_error;         // dst_stree_last_error(NULL)
+static int st_enter(const dst_stree* t) { return !t ? DST_ERR_ARG : t->broken ? DST_ERR_STATE : DST_OK; }
+static int st_fail(const dst_stree* t, int code, const char* why) { t->err = why; return code; }
+static bool all_keys(const dst_stree* t, const uint64_t* indices, size_t count) {
+    for (size_t i = 0; i < count; i++) if (indices[i] >> t->depth) return false;
+    return true;
+}
+struct st_generation {                                 // a device allocation that is freed unless the set completes
+    uint8_t* p = nullptr;
+    ~st_generation() { if (p) hipFree(p); }
+};
+
+// the plan on the device: the next generation's allocation, the uploads (prefixes and level table into the generation; new leaves, carry-over
+// sources and dirty lists into the staging buffer), one carry-over launch, one scatter of the new leaves, one launch per level, one synchronisation
+static int stree_apply_device(dst_stree* t, const stree_plan& p, const uint8_t* leaves /* in the order of the sorted keys */, size_t count) {
+    const stree_shape& nx = p.next;
+    const size_t total = nx.total(), D = t->depth;
+    if (int r = rtree_stage(t, 32 * count + 4 * total + 4 * p.dirty.size() + 16)) return r;
+    st_generation g;
+    RT_HIP(t->err, hipMalloc((void**)&g.p, 40 * total + 3072));
+    fe* nodes = reinterpret_cast<fe*>(g.p);
+    uint64_t* levels = reinterpret_cast<uint64_t*>(g.p + 32 * total + 2048), *pref = levels + 128;
+    uint64_t lv[128] = {0};
+    for (size_t l = 0; l <= D; l++) { lv[2 * l] = nx.start[l]; lv[2 * l + 1] = nx.cnt[l]; }
+    RT_HIP(t->err, hipMemcpyAsync(g.p + 32 * total, t->empties, 2048, hipMemcpyHostToDevice, t->stream));
+    RT_HIP(t->err, hipMemcpyAsync(levels, lv, 1024, hipMemcpyHostToDevice, t->stream));
+    if (count) {
+        const fe* d_leaves = reinterpret_cast<const fe*>(t->stage);
+        uint32_t *d_src = reinterpret_cast<uint32_t*>(t->stage + 32 * count), *d_dirty = d_src + total;
+        RT_HIP(t->err, hipMemcpyAsync(pref, nx.pref.data(), 8 * total, hipMemcpyHostToDevice, t->stream));
+        RT_HIP(t->err, hipMemcpyAsync(t->stage, leaves, 32 * count, hipMemcpyHostToDevice, t->stream));
+        RT_HIP(t->err, hipMemcpyAsync(d_src, p.src.data(), 4 * total, hipMemcpyHostToDevice, t->stream));
+        RT_HIP(t->err, hipMemcpyAsync(d_dirty, p.dirty.data(), 4 * p.dirty.size(), hipMemcpyHostToDevice, t->stream));
+        if (k_rescue_stree_carry(t->stream, nodes, t->dev_nodes(), d_src, total)) return st_fail(t, DST_ERR_HIP, "rescue_stree_carry_kernel: launch failed");
+        if (k_rescue_tree_scatter(t->stream, nodes, d_dirty + p.doff[D], d_leaves, count)) return st_fail(t, DST_ERR_HIP, "rescue_tree_scatter_kernel: launch failed");
+        RT_HIP(t->err, hipEventRecord(t->ev[0], t->stream));
+        for (size_t l = D; l-- > 0;) {
+            const bool whole = p.dcnt[l] == nx.cnt[l];
+            if (k_rescue_stree_level(t->stream, nodes, pref, whole ? nullptr : d_dirty + p.doff[l], p.dcnt[l], nx.start[l], nx.start[l + 1], nx.cnt[l + 1],
+                                     reinterpret_cast<const fe*>(t->empties + 2 * (l + 1))))
+                return st_fail(t, DST_ERR_HIP, "rescue_stree_level_kernel: launch failed");
+        }
+        RT_HIP(t->err, hipEventRecord(t->ev[1], t->stream));
+    }
+    RT_HIP(t->err, hipStreamSynchronize(t->stream));
+    if (count) { if (int r = rtree_elapsed(t, &t->last_ms)) return r; }
+    if (t->dev) hipFree(t->dev);
+    t->dev = g.p; g.p = nullptr;
+    return DST_OK;
+}
+// ... and on the host: the same carry-over, the same lookups, rescue_digest_many_host over each level's dirty list
+static void stree_apply_host(dst_stree* t, const stree_plan& p, const uint8_t* leaves, size_t count) {
+    const stree_shape& nx = p.next;
+    const size_t D = t->depth;
+    std::vector<u128> nn(2 * nx.total()), in(4 * count), out(2 * count);          // no level has more dirty parents than there are new leaves
+    for (size_t j = 0; j < nx.total(); j++) if (p.src[j] != STREE_NEW) memcpy(&nn[2 * j], &t->host[2 * (size_t)p.src[j]], 32);
+    for (size_t i = 0; i < count; i++) memcpy(&nn[2 * (size_t)p.dirty[p.doff[D] + i]], leaves + 32 * i, 32);
+    for (size_t l = D; l-- > 0;) {
+        const uint32_t* list = p.dirty.data() + p.doff[l];
+        const size_t m = p.dcnt[l], cstart = nx.start[l + 1];
+        const u128* e = t->empties + 2 * (l + 1);
+        for (size_t g = 0; g < m; g++) {
+            size_t left, right;
+            stree_children(nx.pref.data() + cstart, nx.cnt[l + 1], nx.pref[list[g]], left, right);
+            memcpy(&in[4 * g], left != STREE_ABSENT ? &nn[2 * (cstart + left)] : e, 32);
+            memcpy(&in[4 * g + 2], right != STREE_ABSENT ? &nn[2 * (cstart + right)] : e, 32);
+        }
+        rescue_digest_many_host(in.data(), m, out.data());
+        for (size_t g = 0; g < m; g++) memcpy(&nn[2 * (size_t)list[g]], &out[2 * g], 32);
+    }
+    t->host.swap(nn);
+}
+
+int dst_stree_create(int device, uint32_t depth, const uint8_t empty_leaf[32], dst_stree** out) {
+    if (out) *out = nullptr;
+    if (!out || depth < 1 || depth > STREE_MAX_DEPTH) { g_stree_error = "invalid argument (1 <= depth <= 63)"; return DST_ERR_ARG; }
+    if (empty_leaf && !all_below_p(empty_leaf, 2)) { g_stree_error = "an element of the empty leaf is not below the modulus"; return DST_ERR_ARG; }
+    std::unique_ptr<dst_stree> t(new (std::nothrow) dst_stree);
+    if (!t) { g_stree_error = "out of host memory"; return DST_ERR_HIP; }
+    t->device = device < 0 ? -1 : device; t->depth = depth; t->shape.depth = depth;
+    if (empty_leaf) memcpy(t->empties + 2 * depth, empty_leaf, 32);
+    for (uint32_t l = depth; l-- > 0;) {                                           // E_l = digest(E_{l+1}, E_{l+1})
+        const u128 in[4] = {t->empties[2 * l + 2], t->empties[2 * l + 3], t->empties[2 * l + 2], t->empties[2 * l + 3]};
+        rescue_digest_many_host(in, 1, t->empties + 2 * l);
+    }
+    if (device >= 0) {                                                             // the generation of a tree without keys
+        const int r = stree_apply_device(t.get(), stree_plan_set(t->shape, {}), nullptr, 0);
+        if (r != DST_OK) { g_stree_error = t->err; return r; }
+    }
+    *out = t.release();
+    return DST_OK;
+}
+void dst_stree_destroy(dst_stree* t) { delete t; }
+const char* dst_stree_last_error(const dst_stree* t) { return t ? t->err.c_str() : g_stree_error.c_str(); }
+
+int dst_stree_set(dst_stree* t, const uint64_t* indices, const uint8_t* leaves, size_t count) {
+    if (int r = st_enter(t)) return r;
+    if (count == 0) { t->last_digests = 0; t->last_ms = 0; return DST_OK; }
+    if (!indices || !leaves) return st_fail(t, DST_ERR_ARG, "null pointer");
+    if (count >= STREE_NEW || t->shape.total() + count * (t->depth + 1) >= STREE_NEW) return st_fail(t, DST_ERR_ARG, "more than 2^32 - 1 stored nodes");
+    if (!all_keys(t, indices, count)) return st_fail(t, DST_ERR_ARG, "index past the end");
+    try {
+        // everything is checked and the whole plan made here, before anything is queued or a node changes
+        std::vector<uint32_t> order(count);
+        for (size_t i = 0; i < count; i++) order[i] = (uint32_t)i;
+        std::sort(order.begin(), order.end(), [&](uint32_t a, uint32_t b) { return indices[a] < indices[b]; });
+        std::vector<uint64_t> keys(count);
+        for (size_t i = 0; i < count; i++) keys[i] = indices[order[i]];
+        if (std::adjacent_find(keys.begin(), keys.end()) != keys.end()) return st_fail(t, DST_ERR_ARG, "an index is repeated");
+        if (!all_below_p(leaves, 2 * count)) return st_fail(t, DST_ERR_ARG, "a leaf element is not below the modulus");
+        std::vector<uint8_t> sorted(32 * count);
+        for (size_t i = 0; i < count; i++) memcpy(&sorted[32 * i], leaves + 32 * (size_t)order[i], 32);
+        stree_plan p = stree_plan_set(t->shape, std::move(keys));
+        if (t->device < 0) stree_apply_host(t, p, sorted.data(), count);
+        else if (int r = stree_apply_device(t, p, sorted.data(), count)) {
+            t->broken = true; t->err += "; the set did not complete, the tree is unusable";
+            return r;
+        }
+        t->shape = std::move(p.next);
+        t->last_digests = p.digests;
+        return DST_OK;
+    } catch (const std::bad_alloc&) { return st_fail(t, DST_ERR_HIP, "out of host memory"); }      // thrown before anything was queued
+}
+
+int dst_stree_read_level(const dst_stree* t, uint32_t level, uint64_t first, uint64_t count, uint64_t* prefixes, uint8_t* nodes, uint64_t* level_count) {
+    if (int r = st_enter(t)) return r;
+    if (level > t->depth) return st_fail(t, DST_ERR_ARG, "level past the leaf level");
+    const size_t m = t->shape.cnt[level], at = t->shape.start[level] + first;
+    if (level_count) *level_count = m;
+    if (first > m || count > m - first) return st_fail(t, DST_ERR_ARG, "range past the end of the level");
+    if (count == 0) return DST_OK;
+    if (prefixes) memcpy(prefixes, t->shape.pref.data() + at, 8 * count);
+    if (!nodes) return DST_OK;
+    if (t->device < 0) { memcpy(nodes, t->host.data() + 2 * at, 32 * count); return DST_OK; }
+    RT_HIP(t->err, hipSetDevice(t->device));
+    RT_HIP(t->err, hipMemcpy(nodes, t->dev_nodes() + 2 * at, 32 * count, hipMemcpyDeviceToHost));
+    return DST_OK;
+}
+int dst_stree_root(const dst_stree* t, uint8_t root[32]) {
+    if (int r = st_enter(t)) return r;
+    if (!root) return st_fail(t, DST_ERR_ARG, "null pointer");
+    if (t->shape.cnt[0] == 0) { memcpy(root, t->empties, 32); return DST_OK; }     // no keys: E_0
+    return dst_stree_read_level(t, 0, 0, 1, nullptr, root, nullptr);
+}
+int dst_stree_info(const dst_stree* t, dst_stree_info_t* out) {
+    if (int r = st_enter(t)) return r;
+    if (!out) return st_fail(t, DST_ERR_ARG, "null pointer");
+    out->depth = t->depth; out->device = t->device;
+    out->keys = t->shape.cnt[t->depth]; out->nodes = t->shape.total();
+    out->last_digests = t->last_digests; out->last_device_ms = t->last_ms;
+    return DST_OK;
+}
+
+// ---- openings: any index below 2^depth, stored or not; a node that is not stored is the E_l of its level ------------------------------------
+static int stree_paths(const dst_stree* t, const uint64_t* indices, size_t count, uint8_t* out) {
+    const size_t n = t->depth + 1, m = count * n;
+    if (count > ((size_t)1 << 40)) return st_fail(t, DST_ERR_ARG, "too many indices");
+    if (!all_keys(t, indices, count)) return st_fail(t, DST_ERR_ARG, "index past the end");
+    if (count == 0) return DST_OK;
+    if (t->device < 0) {
+        for (size_t s = 0; s < m; s++) {
+            uint32_t level; uint64_t prefix;
+            stree_path_slot(t->depth, indices[s / n], (uint32_t)(s % n), level, prefix);
+            const size_t start = t->shape.start[level], pos = stree_find(t->shape.pref.data() + start, t->shape.cnt[level], prefix);
+            memcpy(out + 32 * s, pos != STREE_ABSENT ? &t->host[2 * (start + pos)] : t->empties + 2 * level, 32);
+        }
+        return DST_OK;
+    }
+    if (int r = rtree_stage(t, 32 * m + 8 * count)) return r;                     // [m nodes][count indices]
+    uint64_t* d_idx = reinterpret_cast<uint64_t*>(t->stage + 32 * m);
+    RT_HIP(t->err, hipMemcpyAsync(d_idx, indices, 8 * count, hipMemcpyHostToDevice, t->stream));
+    if (k_rescue_stree_open(t->stream, t->dev_nodes(), t->dev_pref(), t->dev_levels(), t->dev_empties(), d_idx, reinterpret_cast<fe*>(t->stage), count, t->depth))
+        return st_fail(t, DST_ERR_HIP, "rescue_stree_open_kernel: launch failed");
+    RT_HIP(t->err, hipMemcpyAsync(out, t->stage, 32 * m, hipMemcpyDeviceToHost, t->stream));
+    RT_HIP(t->err, hipStreamSynchronize(t->stream));
+    return DST_OK;
+}
+int dst_stree_paths(const dst_stree* t, const uint64_t* indices, size_t count, uint8_t* paths) {
+    if (int r = st_enter(t)) return r;
+    if ((!indices || !paths) && count) return st_fail(t, DST_ERR_ARG, "null pointer");
+    return stree_paths(t, indices, count, paths);
+}
+// dst_rtree_tapes_many with n = depth + 1
+int dst_stree_tapes_many(const dst_stree* t, const uint64_t* indices, size_t count, uint32_t what, uint8_t* tape_a, uint8_t* tape_b, size_t cap_elems_each, size_t* elems_each) {
+    if (int r = st_enter(t)) return r;
+    if (!elems_each || what < 1 || what > 3) return st_fail(t, DST_ERR_ARG, "elems_each missing, or what outside 1..3");
+    if (!indices && count) return st_fail(t, DST_ERR_ARG, "null pointer");
+    const size_t n = t->depth + 1;
+    const size_t each = ((what & 1u) ? 2 * n - 1 : 0) + ((what & 2u) ? n - 1 : 0);
+    *elems_each = each;
+    if (!tape_a && !tape_b)                                                                // size query
+        return all_keys(t, indices, count) ? DST_OK : st_fail(t, DST_ERR_ARG, "index past the end");
+    if (!tape_a || !tape_b || cap_elems_each < each) return st_fail(t, DST_ERR_ARG, "tape buffers missing or too small");
+    try {
+        std::vector<u128> paths(2 * n * count);
+        if (int r = stree_paths(t, indices, count, (uint8_t*)paths.data())) return r;
+        tapes_from_paths(paths.data(), n, indices, count, what, each, tape_a, tape_b);
+    } catch (const std::bad_alloc&) { return st_fail(t, DST_ERR_HIP, "out of host memory"); }
+    return DST_OK;
+}

@@ -1,0 +1,94 @@
+// Sparse Rescue Merkle trees (dst_stree_*): the integer bookkeeping, free of HIP and of field arithmetic.  A tree of depth D stores, per level
+// l (D = the leaves, 0 = the root), the sorted distinct prefixes key >> (D - l) of its keys; a node is found by a lower-bound search for its
+// prefix.  Here: that search (shared with the kernels of kernels_hash.hip, hence STREE_HD), and the plan of a dst_stree_set -- the merge of the
+// new keys into every level, where each node of the merged level comes from, and which nodes have to be hashed.  The host path and the device
+// path run the same plan.
+#pragma once
+#include <algorithm>
+#include <cstddef>
+#include <cstdint>
+#include <vector>
+
+#if defined(__HIPCC__)
+#define STREE_HD __host__ __device__ inline
+#else
+#define STREE_HD inline
+#endif
+
+#define STREE_MAX_DEPTH 63u
+#define STREE_ABSENT (~(size_t)0)                        // no such prefix on the level
+#define STREE_NEW 0xFFFFFFFFu                            // stree_plan::src of a node that the set writes (a new leaf, a hashed parent)
+
+// the first position in the sorted pref[0 .. cnt) whose prefix is not below `want`; cnt when there is none
+STREE_HD size_t stree_lower_bound(const uint64_t* pref, size_t cnt, uint64_t want) {
+    size_t lo = 0;
+    while (cnt) {
+        const size_t half = cnt >> 1;
+        if (pref[lo + half] < want) { lo += half + 1; cnt -= half + 1; }
+        else cnt = half;
+    }
+    return lo;
+}
+STREE_HD size_t stree_find(const uint64_t* pref, size_t cnt, uint64_t want) {
+    const size_t i = stree_lower_bound(pref, cnt, want);
+    return i < cnt && pref[i] == want ? i : STREE_ABSENT;
+}
+// the children of the parent with prefix q among the child level's prefixes: the positions of 2q and 2q + 1, STREE_ABSENT for an empty side
+STREE_HD void stree_children(const uint64_t* cpref, size_t ccnt, uint64_t q, size_t& left, size_t& right) {
+    const size_t i = stree_lower_bound(cpref, ccnt, 2 * q);
+    const bool has_left = i < ccnt && cpref[i] == 2 * q;
+    const size_t j = i + (has_left ? 1 : 0);
+    left = has_left ? i : STREE_ABSENT;
+    right = j < ccnt && cpref[j] == 2 * q + 1 ? j : STREE_ABSENT;
+}
+// node k of the authentication path [leaf, sibling, uncle, ...] of `index`: its level and its prefix there
+STREE_HD void stree_path_slot(uint32_t depth, uint64_t index, uint32_t k, uint32_t& level, uint64_t& prefix) {
+    if (k == 0) { level = depth; prefix = index; return; }
+    level = depth - (k - 1);
+    prefix = (index >> (k - 1)) ^ 1;
+}
+
+// the stored nodes of a tree: level l's sorted prefixes at pref[start[l] .. start[l] + cnt[l]).  The node values live in an array of the same
+// layout (host: u128 pairs, device: fe pairs); a "flat position" indexes both.  Levels are laid out from the leaves (depth) to the root (0).
+struct stree_shape {
+    uint32_t depth = 0;
+    std::vector<uint64_t> pref;
+    size_t start[STREE_MAX_DEPTH + 1] = {0}, cnt[STREE_MAX_DEPTH + 1] = {0};
+    size_t total() const { return pref.size(); }
+};
+// what a set of sorted distinct keys does to a shape
+struct stree_plan {
+    stree_shape next;                                    // the merged levels
+    std::vector<uint32_t> src;                           // per flat position of `next`: the flat position in the old shape the node is carried over from, or STREE_NEW
+    std::vector<uint32_t> dirty;                         // flat positions in `next` of the touched nodes: level l's, sorted, at dirty[doff[l] .. doff[l] + dcnt[l]);
+    size_t doff[STREE_MAX_DEPTH + 1] = {0}, dcnt[STREE_MAX_DEPTH + 1] = {0};      // level depth: the new leaves, in the order of the sorted keys
+    uint64_t digests = 0;                                // parents to hash: the distinct ancestors of the keys = sum of dcnt[l] over l < depth
+};
+// flat positions are 32 bits: old.total() + keys.size() * (depth + 1) must stay below STREE_NEW (the caller checks)
+inline stree_plan stree_plan_set(const stree_shape& old, std::vector<uint64_t> cur /* sorted, distinct, below 2^depth */) {
+    stree_plan p;
+    const uint32_t depth = old.depth;
+    p.next.depth = depth;
+    const size_t most = old.total() + cur.size() * (depth + 1);
+    p.next.pref.reserve(most); p.src.reserve(most); p.dirty.reserve(cur.size() * (depth + 1));
+    for (uint32_t l = depth;; l--) {                     // cur = the touched prefixes of level l
+        const uint64_t* o = old.pref.data() + old.start[l];
+        const size_t on = old.cnt[l];
+        p.next.start[l] = p.next.pref.size(); p.doff[l] = p.dirty.size(); p.dcnt[l] = cur.size();
+        if (l < depth) p.digests += cur.size();
+        for (size_t i = 0, j = 0; i < on || j < cur.size();) {
+            if (j == cur.size() || (i < on && o[i] < cur[j])) {
+                p.next.pref.push_back(o[i]); p.src.push_back((uint32_t)(old.start[l] + i)); i++;
+            } else {
+                if (i < on && o[i] == cur[j]) i++;
+                p.dirty.push_back((uint32_t)p.next.pref.size());
+                p.next.pref.push_back(cur[j]); p.src.push_back(STREE_NEW); j++;
+            }
+        }
+        p.next.cnt[l] = p.next.pref.size() - p.next.start[l];
+        if (l == 0) break;
+        for (auto& v : cur) v >>= 1;
+        cur.erase(std::unique(cur.begin(), cur.end()), cur.end());
+    }
+    return p;
+}

@@ -8,6 +8,7 @@
 #include "ctx.h"
 #include "blake3_dev.h"
 #include "rescue_dev.h"
+#include "host/stree_levels.h"
 
 #define HASH_THREADS 256
 
@@ -481,5 +482,86 @@ int k_rescue_tree_scatter(hipStream_t stream, fe* nodes, const uint32_t* pos, co
 }
 int k_rescue_tree_gather(hipStream_t stream, const fe* nodes, const uint32_t* pos, fe* out, size_t count) {
     hipLaunchKernelGGL(rescue_tree_gather_kernel, dim3((unsigned)((2 * count + HASH_THREADS - 1) / HASH_THREADS)), dim3(HASH_THREADS), 0, stream, nodes, pos, out, count);
+    return hipGetLastError() == hipSuccess ? 0 : -1;
+}
+
+// ---- sparse Rescue Merkle trees (dst_stree_*, host/stree_levels.h): a level is a sorted list of prefixes and a node list beside it, all levels in
+//      one node array and one prefix array; a "flat position" indexes both.  A parent with prefix q looks its children up by a lower-bound search
+//      for 2q among the child level's prefixes [cstart, cstart + ccnt) and takes a side that is not stored from (e0, e1), the value of an empty
+//      subtree of the child level.  The search comes first: only the flat positions found live across the digest.  The parents of a launch are
+//      the flat positions list[0 .. count) (a dirty list) or pstart + [0 .. count) (the whole level, list == nullptr).  The host has validated the
+//      leaves, every inner node is a digest: nothing is checked here. ----------------------------------------------------------------------------
+__global__ void __launch_bounds__(RESCUE_THREADS) rescue_stree_level_kernel(fe* nodes, const uint64_t* __restrict__ pref, const uint32_t* __restrict__ list, size_t count,
+                                                                           size_t pstart, size_t cstart, size_t ccnt, fe e0, fe e1) {
+    const size_t g = (size_t)blockIdx.x * RESCUE_THREADS + threadIdx.x;
+    if (g >= count) return;
+    const size_t p = list ? (size_t)list[g] : pstart + g;
+    size_t left, right;
+    stree_children(pref + cstart, ccnt, pref[p], left, right);
+    fe v0 = e0, v1 = e1, v2 = e0, v3 = e1;
+    if (left != STREE_ABSENT) { v0 = nodes[2 * (cstart + left)]; v1 = nodes[2 * (cstart + left) + 1]; }
+    if (right != STREE_ABSENT) { v2 = nodes[2 * (cstart + right)]; v3 = nodes[2 * (cstart + right) + 1]; }
+    fe d0, d1;
+    rescue_digest4(v0, v1, v2, v3, d0, d1);
+    nodes[2 * p] = d0; nodes[2 * p + 1] = d1;
+}
+// the six-lanes-of-eight form (rescue_parent_spread): lanes 5, 4 hold l0, l1 and lanes 3, 2 hold r0, r1; a group past the end is given the first
+// parent, keeps the barriers and stores nothing
+__global__ void __launch_bounds__(RESCUE_THREADS) rescue_stree_level_spread_kernel(fe* nodes, const uint64_t* __restrict__ pref, const uint32_t* __restrict__ list, size_t count,
+                                                                                  size_t pstart, size_t cstart, size_t ccnt, fe e0, fe e1) {
+    __shared__ fe xch[RESCUE_THREADS];
+    const size_t i = (size_t)blockIdx.x * (RESCUE_THREADS / 8u) + (threadIdx.x >> 3);
+    const bool live = i < count;
+    const size_t g = live ? i : 0;
+    const size_t p = list ? (size_t)list[g] : pstart + g;
+    const uint32_t e = threadIdx.x & 7u;
+    fe v = fe_zero();                                                  // state after hasher.rs:18: (0, 0, r1, r0, l1, l0)
+    if (e >= 2u && e < 6u) {
+        size_t left, right;
+        stree_children(pref + cstart, ccnt, pref[p], left, right);
+        const size_t child = e >= 4u ? left : right;
+        v = (e & 1u) ? e0 : e1;
+        if (child != STREE_ABSENT) v = nodes[2 * (cstart + child) + (1u - (e & 1u))];
+    }
+    rescue_permute_lane(v, e, xch + (threadIdx.x & ~7u));
+    if (live && (e == 5u || e == 4u)) nodes[2 * p + (5u - e)] = v;
+}
+// the nodes a set does not touch: dst[j] = src[from[j]] for from[j] != STREE_NEW, two lanes per node
+__global__ void rescue_stree_carry_kernel(fe* __restrict__ dst, const fe* __restrict__ src, const uint32_t* __restrict__ from, size_t count) {
+    const size_t t = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (t >= 2 * count) return;
+    const uint32_t f = from[t >> 1];
+    if (f != STREE_NEW) dst[t] = src[2 * (size_t)f + (t & 1)];
+}
+// openings: one lane per (index, path node, element).  levels[2 l], levels[2 l + 1] = start and length of level l; empties[2 l ..) = the value of
+// an empty subtree of level l.  A node that is not stored, the leaf included, is that value.
+__global__ void rescue_stree_open_kernel(const fe* __restrict__ nodes, const uint64_t* __restrict__ pref, const uint64_t* __restrict__ levels, const fe* __restrict__ empties,
+                                         const uint64_t* __restrict__ indices, fe* __restrict__ out, size_t count, uint32_t depth) {
+    const size_t t = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    const size_t n = depth + 1;
+    if (t >= 2 * count * n) return;
+    const size_t s = t >> 1;
+    uint32_t level;
+    uint64_t prefix;
+    stree_path_slot(depth, indices[s / n], (uint32_t)(s % n), level, prefix);
+    const size_t start = levels[2 * level], pos = stree_find(pref + start, levels[2 * level + 1], prefix);
+    out[t] = pos != STREE_ABSENT ? nodes[2 * (start + pos) + (t & 1)] : empties[2 * level + (t & 1)];
+}
+
+int k_rescue_stree_level(hipStream_t stream, fe* nodes, const uint64_t* pref, const uint32_t* list, size_t count, size_t pstart, size_t cstart, size_t ccnt, const fe* empty) {
+    const bool spread = count <= RESCUE_SPREAD_MAX;
+    const size_t per_block = spread ? RESCUE_THREADS / 8 : RESCUE_THREADS;
+    const dim3 grid((unsigned)((count + per_block - 1) / per_block)), block(RESCUE_THREADS);
+    if (spread) hipLaunchKernelGGL(rescue_stree_level_spread_kernel, grid, block, 0, stream, nodes, pref, list, count, pstart, cstart, ccnt, empty[0], empty[1]);
+    else hipLaunchKernelGGL(rescue_stree_level_kernel, grid, block, 0, stream, nodes, pref, list, count, pstart, cstart, ccnt, empty[0], empty[1]);
+    return hipGetLastError() == hipSuccess ? 0 : -1;
+}
+int k_rescue_stree_carry(hipStream_t stream, fe* dst, const fe* src, const uint32_t* from, size_t count) {
+    hipLaunchKernelGGL(rescue_stree_carry_kernel, dim3((unsigned)((2 * count + HASH_THREADS - 1) / HASH_THREADS)), dim3(HASH_THREADS), 0, stream, dst, src, from, count);
+    return hipGetLastError() == hipSuccess ? 0 : -1;
+}
+int k_rescue_stree_open(hipStream_t stream, const fe* nodes, const uint64_t* pref, const uint64_t* levels, const fe* empties, const uint64_t* indices, fe* out, size_t count, uint32_t depth) {
+    const size_t lanes = 2 * count * (depth + 1);
+    hipLaunchKernelGGL(rescue_stree_open_kernel, dim3((unsigned)((lanes + HASH_THREADS - 1) / HASH_THREADS)), dim3(HASH_THREADS), 0, stream, nodes, pref, levels, empties, indices, out, count, depth);
     return hipGetLastError() == hipSuccess ? 0 : -1;
 }

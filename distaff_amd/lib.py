@@ -57,7 +57,9 @@ EXPORTS = ["dst_ctx_create", "dst_ctx_destroy", "dst_last_error", "dst_phase_ms"
            "dst_comm_describe", "dst_comm_trace", "dst_test_hooks", "dst_comm_set_timeout", "dst_comm_abort", "dst_shard_exchange_ms", "dst_bench_clock",
            "dst_verify", "dst_proof_info",
            "dst_rescue_digest_many", "dst_rtree_build", "dst_rtree_root", "dst_rtree_path", "dst_rtree_tapes", "dst_rtree_read_nodes", "dst_rtree_build_ms",
-           "dst_rtree_destroy", "dst_rtree_last_error", "dst_rtree_update", "dst_rtree_update_ms", "dst_rtree_paths", "dst_rtree_tapes_many"]
+           "dst_rtree_destroy", "dst_rtree_last_error", "dst_rtree_update", "dst_rtree_update_ms", "dst_rtree_paths", "dst_rtree_tapes_many",
+           "dst_stree_create", "dst_stree_set", "dst_stree_root", "dst_stree_paths", "dst_stree_tapes_many", "dst_stree_read_level", "dst_stree_info",
+           "dst_stree_destroy", "dst_stree_last_error"]
 
 
 class DistaffError(RuntimeError):
@@ -391,6 +393,112 @@ class RescueTree:
         out = np.zeros((count, 2, 2), dtype=np.uint64)
         self._check(self.lib.dst_rtree_read_nodes(self._h, ctypes.c_uint64(first), ctypes.c_uint64(count), _ptr(out)))
         return out
+
+class StreeInfo(ctypes.Structure):
+    _fields_ = [("depth", ctypes.c_uint32), ("device", ctypes.c_int32), ("keys", ctypes.c_uint64), ("nodes", ctypes.c_uint64),
+                ("last_digests", ctypes.c_uint64), ("last_device_ms", ctypes.c_double)]
+
+
+class SparseRescueTree:
+    """A sparse Rescue Merkle tree (``dst_stree``): the dense RescueTree over 2^depth leaves, 1 <= depth <= 63, in which every leaf that was
+    never set holds `empty_leaf`; only the nodes above set leaves are stored.  Same roots, same paths (depth + 1 nodes), same tapes.
+    device >= 0 keeps it on that GPU; device < 0 on the host."""
+
+    def __init__(self, depth, empty_leaf=(0, 0), device=0, lib=None):
+        self.lib = lib or load()
+        self.depth = int(depth)
+        e = _elements([tuple(empty_leaf)], 2)
+        h = ctypes.c_void_p()
+        r = self.lib.dst_stree_create(ctypes.c_int(device), ctypes.c_uint32(self.depth), _ptr(e), ctypes.byref(h))
+        if r != DST_OK:
+            raise DistaffError(r, self._error(None))
+        self._h = h
+
+    def _error(self, handle):
+        self.lib.dst_stree_last_error.restype = ctypes.c_char_p
+        self.lib.dst_stree_last_error.argtypes = [ctypes.c_void_p]
+        return (self.lib.dst_stree_last_error(handle) or b"").decode()
+
+    def _check(self, r):
+        if r != DST_OK:
+            raise DistaffError(r, self._error(self._h))
+
+    def close(self):
+        if getattr(self, "_h", None):
+            self.lib.dst_stree_destroy.restype = None
+            self.lib.dst_stree_destroy(self._h)
+            self._h = None
+
+    def __del__(self):
+        self.close()
+
+    def set(self, indices, leaves):
+        """inserts or replaces the leaves at the distinct keys `indices` (any order; `leaves`: as many pairs of ints, or uint64 words
+        [count, 2, 2]) and hashes exactly their ancestors (dst_stree_set).  A repeated key, a key past 2^depth or an element not below p
+        raises DistaffError(DST_ERR_ARG) and leaves the tree as it was."""
+        idx, ip = RescueTree._indices(indices)
+        a = _elements(leaves, 2)
+        if a.shape[0] != idx.size:
+            raise DistaffError(DST_ERR_ARG, "as many leaves as indices")
+        self._check(self.lib.dst_stree_set(self._h, ip, _ptr(a) if idx.size else None, ctypes.c_size_t(idx.size)))
+
+    @property
+    def root(self):
+        """(r0, r1)"""
+        out = np.zeros((2, 2), dtype=np.uint64)
+        self._check(self.lib.dst_stree_root(self._h, _ptr(out)))
+        return tuple(arr_to_ints(out))
+
+    def paths_words(self, indices):
+        """paths() as uint64 words [count, depth + 1, 2, 2]"""
+        idx, ip = RescueTree._indices(indices)
+        n = self.depth + 1
+        out = np.zeros((idx.size, n, 2, 2), dtype=np.uint64)
+        self._check(self.lib.dst_stree_paths(self._h, ip, ctypes.c_size_t(idx.size), _ptr(out) if idx.size else None))
+        return out
+
+    def paths(self, indices):
+        """authentication paths [leaf, sibling, uncle, ...] of the keys `indices`, stored or not, repeats allowed, in one call
+        (dst_stree_paths): a list of lists of depth + 1 pairs of ints.  A node that is not stored is the empty subtree of its level."""
+        n = self.depth + 1
+        w = self.paths_words(indices)
+        v = arr_to_ints(w)
+        return [[(v[2 * (i * n + k)], v[2 * (i * n + k) + 1]) for k in range(n)] for i in range(w.shape[0])]
+
+    def path(self, index):
+        return self.paths([index])[0]
+
+    def tapes_many(self, indices, what=3):
+        """RescueTree.tapes_many with n = depth + 1 (dst_stree_tapes_many): a list of (A, B)"""
+        idx, ip = RescueTree._indices(indices)
+        n = ctypes.c_size_t(0)
+        self._check(self.lib.dst_stree_tapes_many(self._h, ip, ctypes.c_size_t(idx.size), ctypes.c_uint32(what), None, None, ctypes.c_size_t(0), ctypes.byref(n)))
+        each = n.value
+        a = np.zeros((max(idx.size * each, 1), 2), dtype=np.uint64)
+        b = np.zeros((max(idx.size * each, 1), 2), dtype=np.uint64)
+        self._check(self.lib.dst_stree_tapes_many(self._h, ip, ctypes.c_size_t(idx.size), ctypes.c_uint32(what), _ptr(a), _ptr(b), ctypes.c_size_t(each), ctypes.byref(n)))
+        va, vb = arr_to_ints(a[:idx.size * each]), arr_to_ints(b[:idx.size * each])
+        return [(va[i * each:(i + 1) * each], vb[i * each:(i + 1) * each]) for i in range(idx.size)]
+
+    def tapes(self, index, what=3):
+        return self.tapes_many([index], what)[0]
+
+    def level(self, l):
+        """level l's sorted list (dst_stree_read_level): (prefixes uint64 [m], nodes uint64 words [m, 2, 2]); level depth = the leaves, 0 = the root"""
+        m = ctypes.c_uint64(0)
+        self._check(self.lib.dst_stree_read_level(self._h, ctypes.c_uint32(l), ctypes.c_uint64(0), ctypes.c_uint64(0), None, None, ctypes.byref(m)))
+        prefixes = np.zeros(m.value, dtype=np.uint64)
+        nodes = np.zeros((m.value, 2, 2), dtype=np.uint64)
+        if m.value:
+            self._check(self.lib.dst_stree_read_level(self._h, ctypes.c_uint32(l), ctypes.c_uint64(0), ctypes.c_uint64(m.value), _ptr(prefixes), _ptr(nodes), ctypes.byref(m)))
+        return prefixes, nodes
+
+    def info(self):
+        """dst_stree_info: depth, device, keys, nodes, last_digests, last_device_ms"""
+        i = StreeInfo()
+        self._check(self.lib.dst_stree_info(self._h, ctypes.byref(i)))
+        return {f: getattr(i, f) for f, _ in StreeInfo._fields_}
+
 
 class Comm:
     """One rank's communicator handle (``dst_comm``) for ``Context.prove_sharded``: RCCL over xGMI, the unique id created by

@@ -189,6 +189,50 @@ DST_API int dst_rtree_tapes_many(const dst_rtree* t, const uint64_t* indices, si
 DST_API void dst_rtree_destroy(dst_rtree* t);
 DST_API const char* dst_rtree_last_error(const dst_rtree* t);     /* t may be NULL: the error of the calling thread's last failed dst_rtree_build / dst_rescue_digest_many */
 
+/* ---- sparse Rescue Merkle trees: a set addressed by keys of up to 63 bits (accounts, notes, nullifiers) ------------------------------------
+ * A sparse tree of depth D, 1 <= D <= 63, IS the dense tree above over 2^D leaves in which every leaf that was never set holds the tree's empty
+ * leaf (two canonical elements given at creation, (0, 0) by default): same parents, same roots, same paths, so smpath.n / pmpath.n with
+ * n = D + 1 <= 64 authenticate them.  Level D is the leaf level, level 0 the root; E_D = the empty leaf and E_l = digest(E_{l+1}, E_{l+1}) is
+ * every empty subtree of level l.  Only nodes with a set leaf below them are stored: per level l a list sorted by prefix, the distinct
+ * key >> (D - l) and their node values.  A key set to the empty value stays stored (its nodes then equal the defaults, so roots do not depend
+ * on it); there is no deletion.  A tree without keys has root E_0.  The reference has no such structure (it walks "a pseudo-random path
+ * through an imaginary tree", src/examples/merkle.rs:96-108).
+ * The conventions are dst_rtree's: no dst_ctx; device >= 0 on that GPU with a stream the tree owns, device < 0 on the host with one thread and
+ * no HIP call; DST_ERR_ARG is found on the host before anything is queued and leaves the tree unchanged; a HIP error inside dst_stree_set leaves
+ * the tree unusable (DST_ERR_STATE from everything but destroy and last_error). */
+typedef struct dst_stree dst_stree;
+DST_API int dst_stree_create(int device, uint32_t depth, const uint8_t empty_leaf[32] /* NULL: (0, 0) */, dst_stree** out);
+/* inserts the keys that are not stored and replaces those that are: `count` distinct indices below 2^depth in any order, count * 32 bytes of
+ * leaves.  Afterwards every stored node equals that of a tree created fresh and set once with the union (the later value of a key wins).  One
+ * digest per distinct ancestor of the touched keys -- the sum over the levels l < depth of the number of distinct index >> (depth - l) -- and no
+ * more; untouched nodes are carried over, never hashed again (moving them costs O(stored nodes)).  Building a tree is create + one set.
+ * DST_ERR_ARG: a repeated index, an index past the end, an element not below p, a null pointer with count > 0, more than 2^32 - 2 stored nodes.
+ * count = 0: DST_OK. */
+DST_API int dst_stree_set(dst_stree* t, const uint64_t* indices, const uint8_t* leaves /* count*32 */, size_t count);
+DST_API int dst_stree_root(const dst_stree* t, uint8_t root[32]);
+/* authentication paths [leaf, sibling, uncle, ...] of `count` indices below 2^depth, stored or not (repeats allowed), (depth + 1) * 32 bytes
+ * each in dst_rtree_path's layout: compute_merkle_root (merkle.rs:112-145) of the path and the index gives the root.  A leaf or sibling that is
+ * not stored is the E_l of its level; a path whose leaf is E_depth proves that the key is empty.  On a device tree: one upload, one launch, one
+ * copy back, whatever count is. */
+DST_API int dst_stree_paths(const dst_stree* t, const uint64_t* indices, size_t count, uint8_t* paths /* count*(depth+1)*32 */);
+/* dst_rtree_tapes_many with n = depth + 1: the same `what`, the same size query */
+DST_API int dst_stree_tapes_many(const dst_stree* t, const uint64_t* indices, size_t count, uint32_t what,
+                                 uint8_t* tape_a, uint8_t* tape_b, size_t cap_elems_each, size_t* elems_each);
+/* `count` entries from `first` of level `level`'s sorted list: the prefixes and / or the nodes (either may be NULL); *level_count (may be NULL)
+ * always receives the level's length.  How a host sees every node, and how it persists a tree. */
+DST_API int dst_stree_read_level(const dst_stree* t, uint32_t level, uint64_t first, uint64_t count,
+                                 uint64_t* prefixes, uint8_t* nodes /* count*32 */, uint64_t* level_count);
+typedef struct dst_stree_info_t {
+    uint32_t depth;
+    int32_t device;                     /* -1: a host tree */
+    uint64_t keys, nodes;               /* stored keys; stored nodes of all levels, the leaves included */
+    uint64_t last_digests;              /* digests computed by the last dst_stree_set */
+    double last_device_ms;              /* events around that call's level launches, as dst_rtree_update_ms; 0 on a host tree */
+} dst_stree_info_t;
+DST_API int dst_stree_info(const dst_stree* t, dst_stree_info_t* out);
+DST_API void dst_stree_destroy(dst_stree* t);
+DST_API const char* dst_stree_last_error(const dst_stree* t);     /* t may be NULL: the error of the calling thread's last failed dst_stree_create */
+
 /* ---- host-side helpers that the Rust host would otherwise take from `rand` (they run on the CPU) -------------------- */
 DST_API void dst_prng_vector(const uint8_t seed[32], uint32_t count, uint8_t* out /* count*16 */);          /* field.rs:271 */
 DST_API int dst_query_positions(const uint8_t seed[32], uint64_t domain_size, uint32_t blowup, uint32_t num_queries, uint64_t* out); /* utils/mod.rs:25 */

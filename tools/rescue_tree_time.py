@@ -3,6 +3,7 @@
 device's own modular-multiplication rate sets.
     python tools/rescue_tree_time.py [--host-log 12] [--lib path/to/another/build.so] [log_leaves ...]        (default 12 16 20)
     python tools/rescue_tree_time.py --update        updates in place and batched openings on the 2^20 tree instead (dst_rtree_update_ms)
+    python tools/rescue_tree_time.py --sparse        sparse trees of depth 63 instead (dst_stree_set, dst_stree_paths), beside a dense 2^20 build
 One digest is counted as 9 180 field multiplications, the reference's own count per hasher::digest: ten rounds of 6 x 2 for the cubes, 6 x 139
 for x^INV_ALPHA by the addition chain (127 squarings + 12 multiplications) and 2 x 36 for the two MDS products."""
 import argparse
@@ -22,6 +23,7 @@ ap.add_argument("--host-log", type=int, default=12, help="size of the host-path 
 ap.add_argument("--lib", default=None, help="another build of the library (a different RESCUE_SPREAD_MAX)")
 ap.add_argument("--runs", type=int, default=5)
 ap.add_argument("--update", action="store_true", help="time dst_rtree_update (k = 1, 256, 65 536 leaves) and dst_rtree_paths on the 2^20 tree instead of builds")
+ap.add_argument("--sparse", action="store_true", help="time dst_stree_set (2^12, 2^16, 2^20 keys into an empty depth-63 tree; 1, 256, 65 536 keys into the 2^20-key tree) and dst_stree_paths")
 ap.add_argument("sizes", nargs="*", type=int)
 args = ap.parse_args()
 lib = D.lib._open(os.path.abspath(args.lib)) if args.lib else None       # through the binding: one HIP runtime per process
@@ -90,6 +92,71 @@ if args.update:
     assert r == 0 and np.array_equal(out[-n:], one)
     print("dst_rtree_paths of %d indices: %.3f ms wall; %d calls of dst_rtree_path: %.2f ms wall (ctypes, no conversion): %.0f x" % (count, c_many * 1e3, count, c_single * 1e3, c_single / c_many))
     t.close()
+    sys.exit(0)
+if args.sparse:
+    DEPTH = 63
+
+    def keys_and_leaves(count, seed):
+        rng = np.random.default_rng(seed)
+        k = np.unique(rng.integers(0, 1 << DEPTH, size=count + count // 8 + 16, dtype=np.uint64))      # distinct; sorted, so shuffled below
+        rng.shuffle(k)
+        v = rng.integers(0, 1 << 64, size=(count, 2, 2), dtype=np.uint64)
+        v[..., 1] >>= np.uint64(1)
+        return k[:count], v
+
+    a = leaves(20)
+    D.RescueTree(a, device=0, lib=lib).close()      # warm-up
+    dense_ms = []
+    for _ in range(args.runs):
+        t = D.RescueTree(a, device=0, lib=lib)
+        dense_ms.append(t.build_ms)
+        t.close()
+    dense_rate = ((1 << 20) - 1) / (min(dense_ms) * 1e-3)
+    print("yardstick, dense tree of 2^20 leaves: %.3f ms on the device (min of %d; all: %s), %.3e digests/s"
+          % (min(dense_ms), args.runs, " ".join("%.3f" % v for v in dense_ms), dense_rate))
+    big = None
+    for log_keys in (12, 16, 20):
+        k, v = keys_and_leaves(1 << log_keys, 100 + log_keys)
+        ms = []
+        for run in range(1 + (args.runs if log_keys < 20 else 1)):      # the first is the warm-up; the 2^20-key tree is built twice only
+            t0 = time.perf_counter()
+            t = D.SparseRescueTree(DEPTH, device=0, lib=lib)
+            t.set(k, v)
+            wall = time.perf_counter() - t0
+            i = t.info()
+            ms.append(i["last_device_ms"])
+            root = t.root
+            if log_keys == 20 and run == 1:
+                big = t                             # the tree the sets below go into
+            else:
+                t.close()
+        ms = ms[1:]
+        rate = i["last_digests"] / (min(ms) * 1e-3)
+        narrow = sum(1 for l in range(DEPTH) if min(1 << l, 1 << log_keys) <= (1 << 15))
+        print("set of 2^%d keys into an empty depth-%d tree: %.3f ms on the device (min of %d after one warm-up; all: %s), %d digests, %.3e digests/s = %.3f of the dense rate; "
+              "%d stored nodes; %d of 63 levels within RESCUE_SPREAD_MAX; %.1f ms wall with the plan and the uploads; root %032x %032x"
+              % (log_keys, DEPTH, min(ms), len(ms), " ".join("%.3f" % x for x in ms), i["last_digests"], rate, rate / dense_rate, i["nodes"], narrow, wall * 1e3, root[0], root[1]))
+    for count in (1, 256, 65536):
+        ms, wall = [], []
+        for run in range(1 + args.runs):
+            k, v = keys_and_leaves(count, 1000 * count + run)
+            t0 = time.perf_counter()
+            big.set(k, v)
+            wall.append((time.perf_counter() - t0) * 1e3)
+            i = big.info()
+            ms.append(i["last_device_ms"])
+        ms, wall = ms[1:], wall[1:]
+        print("set of %d keys into the 2^20-key tree: %.3f ms on the device (min of %d after one warm-up; all: %s), %d digests, %.3e digests/s = %.3f of the dense rate, "
+              "%.3f ms per level; %.1f ms wall (the carry-over of %d nodes, the plan and the uploads included)"
+              % (count, min(ms), len(ms), " ".join("%.3f" % x for x in ms), i["last_digests"], i["last_digests"] / (min(ms) * 1e-3), i["last_digests"] / (min(ms) * 1e-3) / dense_rate,
+                 min(ms) / DEPTH, min(wall), i["nodes"]))
+    rng = np.random.default_rng(7)
+    stored = big.level(DEPTH)[0]
+    idx = np.concatenate([stored[rng.integers(0, stored.size, size=2048)], rng.integers(0, 1 << DEPTH, size=2048, dtype=np.uint64)])
+    big.paths_words(idx[:16])                       # warm-up
+    t0 = time.perf_counter(); w = big.paths_words(idx); s_many = time.perf_counter() - t0
+    print("dst_stree_paths of %d indices (half stored, half absent) on the %d-key tree: %.3f ms wall (%d nodes of %d searched levels each)" % (idx.size, big.info()["keys"], s_many * 1e3, DEPTH + 1, DEPTH + 1))
+    big.close()
     sys.exit(0)
 for log_leaves in args.sizes or [12, 16, 20]:
     a = leaves(log_leaves)

@@ -294,7 +294,7 @@ int dst_commit_trace(dst_ctx* c, uint8_t trace_root[32]) {
     }
     HIP_TRY(c, hipEventRecord(c->ph_ev[5], c->stream));         // end of the extension: the host does not wait here
     k_trace_leaves(c);                                           // trace_table.rs:174-185
-    k_merkle_levels(c, c->trace_leaves, c->trace_nodes, c->Bc * c->n);
+    k_merkle(c, c->trace_leaves, c->trace_nodes, c->Bc * c->n, 0);
     HIP_TRY(c, hipMemcpyAsync(c->trace_root, c->trace_nodes + 1, 32, hipMemcpyDeviceToHost, c->stream));
     // last state of the un-extended trace: op counter and program hash (evaluator.rs:37,73-74)
     fe last[3];
@@ -444,7 +444,7 @@ int dst_fri_commit_layer(dst_ctx* c, uint8_t layer_root[32], int* more) {
     HIP_TRY(c, hipSetDevice(c->device));
     double t0 = wall_ms();
     if (d == 0) k_fri_leaves_layer0(c); else k_fri_leaves(c, d);
-    k_merkle_levels(c, c->fri_leaves[d], c->fri_nodes[d], c->fri_size[d] / 4);
+    k_merkle(c, c->fri_leaves[d], c->fri_nodes[d], c->fri_size[d] / 4, 0);
     uint8_t root[32];
     HIP_TRY(c, hipMemcpyAsync(root, c->fri_nodes[d] + 1, 32, hipMemcpyDeviceToHost, c->stream));
     HIP_TRY(c, hipStreamSynchronize(c->stream));

@@ -66,7 +66,7 @@ static const dst_switch_def DST_SWITCHES[] = {
     {"DISTAFF_LDE_BATCH",          false, "cols,cosets",     "registers x cosets per transform launch"},
     {"DISTAFF_FOLD8_DFT",          false, "0",               "8n-coefficient extensions without the fused fold + 8-point step"},
     {"DISTAFF_TRACE_BUFFER",       false, "1",               "give the trace its own buffer instead of coset 0 of the extension"},
-    {"DISTAFF_MERKLE_LEVEL2_LOG",  false, "k",               "build two tree levels per launch from 2^k nodes on (default 2^15)"},
+    {"DISTAFF_MERKLE_LEVEL2_LOG",  false, "k",               "build two tree levels per launch from 2^k grandparents per launch on (default 2^19)"},
     {"DISTAFF_MERKLE_LEVELS",      false, "1",               "one launch per tree level"},
     {"DISTAFF_SYN_DIV_TABLES",     false, "1",               "synthetic division by power tables + scan instead of the blocked form"},
     {"DISTAFF_FRI_TAIL",           false, "0",               "no single-launch tail: every FRI layer by its own launches (the tail otherwise starts at the first layer of at most 2^13 elements)"},
@@ -348,8 +348,10 @@ void k_fri_leaves_at(dst_ctx* c, const fe* e, digest* leaves, size_t R);
 void k_fri_fold_at(dst_ctx* c, const fe* e, fe* out, size_t R, int layer, fe special_x, const fe* alpha_dev = nullptr);   // alpha_dev: x read from device memory instead
 // hashing
 void k_trace_leaves(dst_ctx* c);
-void k_merkle_levels(dst_ctx* c, const digest* leaves, digest* nodes, size_t num_leaves);
-void k_constraint_tree(dst_ctx* c);
+// the levels of a BLAKE3 tree above `count` children -- `leaves`, or with leaves = nullptr the filled level nodes[count .. 2*count) -- down to the
+// level of stop_count nodes; stop_count = 0: down to the root nodes[1] (host/merkle_plan.h chooses the kernels)
+void k_merkle(dst_ctx* c, const digest* leaves, digest* nodes, size_t count, size_t stop_count);
+void k_constraint_tree(dst_ctx* c);                                                     // k_constraint_level1 and the levels above it, down to the root
 void k_fri_leaves_layer0(dst_ctx* c);
 void k_fri_leaves(dst_ctx* c, int layer);
 // AIR
@@ -387,12 +389,9 @@ int k_bench_mad(dst_ctx* c, uint64_t lanes, uint32_t iters, double* ms);
 int k_bench_clock(dst_ctx* c, uint64_t lanes, uint32_t iters, double* mhz);          // shader clock (MHz) sustained under four fe_mul chains per lane on `lanes` lanes
 int k_bench_code(dst_ctx* c, uint32_t code_kib, double* ms);      // kernels_probe.hip
 // coset-sharded (multi-GPU) helpers
-void k_merkle_local_levels(dst_ctx* c, digest* nodes, size_t count, size_t stop_count);
-void k_merkle_levels_to(dst_ctx* c, const digest* leaves, digest* nodes, size_t num_leaves, size_t stop_count);
-void k_upper_tree(dst_ctx* c, const digest* gathered, digest* upper, size_t nb, uint32_t G);
-void k_merkle_upper(dst_ctx* c, digest* nodes, size_t count);       // nodes[1 .. count) from the filled level nodes[count .. 2*count)
+void k_upper_tree(dst_ctx* c, const digest* gathered, digest* upper, size_t nb, uint32_t G);      // the ranks' boundary nodes interleaved into upper[nb G ..), then the tree above them
 void k_digests_from_records(dst_ctx* c, const void* recs, size_t stride, digest* dst, size_t count);   // dst[i] = first 32 bytes of record i (count <= 8)
-void k_constraint_level1(dst_ctx* c);
+void k_constraint_level1(dst_ctx* c);                                                    // first node level of the constraint tree over this context's cosets
 void k_fri_leaves_cm(dst_ctx* c, const fe* e, digest* leaves, size_t nd);
 void k_fri_fold_cm(dst_ctx* c, const fe* e, fe* out, size_t nd, int layer, fe special_x, const fe* alpha_dev = nullptr);
 void k_fri_draw_at(dst_ctx* c, const digest* nodes, fe* alpha_out, digest* root_out);    // x = prng(nodes[1]) on the device

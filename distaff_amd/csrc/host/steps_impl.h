@@ -175,7 +175,7 @@ int step::fri_commit_natural(dst_ctx* c, int d0) {
         const bool coset_major = d == 0 && !c->sharded_layout;        // the composition as the single-GPU phases leave it
         const fe* e = fri_layer_natural(c, d);
         if (coset_major) k_fri_leaves_layer0(c); else k_fri_leaves_at(c, e, c->fri_leaves[d], R);
-        k_merkle_levels(c, c->fri_leaves[d], c->fri_nodes[d], R);
+        k_merkle(c, c->fri_leaves[d], c->fri_nodes[d], R, 0);
         k_fri_draw(c, d, d_alpha + d, d_roots + d);
         if (d + 1 == L) continue;
         if (coset_major) k_fri_fold_dev(c, 0, d_alpha); else k_fri_fold_at(c, e, c->fri_e[d + 1], R, d, fe_zero(), d_alpha + d);
@@ -198,7 +198,7 @@ int step::fri_commit_natural(dst_ctx* c, int d0) {
 void step::fri_shard_layer(dst_ctx* c, int d) {
     const size_t nd = fri_nd(c, d), nb = nd / 4;
     k_fri_leaves_cm(c, c->fri_e[d], c->fri_leaves[d], nd);
-    k_merkle_levels_to(c, c->fri_leaves[d], c->fri_nodes[d], nb * c->Bc, nb);
+    k_merkle(c, c->fri_leaves[d], c->fri_nodes[d], nb * c->Bc, nb);
     c->fri_committed = d + 1;
 }
 void step::fri_shard_fold(dst_ctx* c, int d, fe x, const fe* alpha_dev) {

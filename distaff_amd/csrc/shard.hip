@@ -95,7 +95,7 @@ int dst_shard_commit_trace(dst_ctx* c) {
     k_intt_columns(c, c->trace, c->trace_stride, c->polys, c->W);
     k_lde_columns(c, c->polys, c->lde, c->W);
     k_trace_leaves(c);
-    k_merkle_levels_to(c, c->trace_leaves, c->trace_nodes, c->Bc * c->n, c->n);
+    k_merkle(c, c->trace_leaves, c->trace_nodes, c->Bc * c->n, c->n);
     fe last[3];
     for (int i = 0; i < 3; i++) HIP_TRY(c, hipMemcpyAsync(&last[i], c->trace + (size_t)i * c->trace_stride + (c->n - 1), 16, hipMemcpyDeviceToHost, c->stream));
     HIP_TRY(c, hipStreamSynchronize(c->stream));
@@ -125,7 +125,7 @@ static int shard_combine_parts(dst_ctx* c, int parts) {
         k_lde_fold8(c, c->cpoly, c->cevals);
         if (c->Bc >= 4) {                                   // with two cosets per rank the leaves themselves are the boundary (see dst_shard_export)
             k_constraint_level1(c);
-            k_merkle_local_levels(c, c->cnodes, c->Bc * c->n / 4, c->n);
+            k_merkle(c, nullptr, c->cnodes, c->Bc * c->n / 4, c->n);
         }
         c->constraints_done = true; c->composed = false;
     }
@@ -754,7 +754,7 @@ void tree_exchange(Sharded& S, uint32_t what, uint32_t arg, uint8_t root[32], co
             return DST_OK;
         });
         if (!S.coll(S.coll_on(2, c->stream, [&] { return comm->all_gather(recs + comm->rank, recs, sizeof(TreeRec), c->stream); }), "tree_exchange")) return;
-        S.local([&] { k_digests_from_records(c, recs, sizeof(TreeRec), upper + G, G); k_merkle_upper(c, upper, G); return DST_OK; });      // the top log2(G) levels, on every rank
+        S.local([&] { k_digests_from_records(c, recs, sizeof(TreeRec), upper + G, G); k_merkle(c, nullptr, upper, G, 0); return DST_OK; });      // the top log2(G) levels, on every rank
     } else {
         if (!S.coll(S.coll_on(2, c->stream, [&] { return comm->all_gather(src, c->gather_buf, K * 32, c->stream); }), "tree_exchange")) return;
         S.local([&] { k_upper_tree(c, (const digest*)c->gather_buf, upper, K, (uint32_t)G); return DST_OK; });
@@ -831,7 +831,7 @@ void commit_trace_columns(Sharded& S) {
             k_lde_columns(c, c->polys, c->lde, W);
             if (c->sh_ev[1]) (void)hipEventRecord(c->sh_ev[1], c->stream);        // end of the extension (phase 0 | 1)
             k_trace_leaves(c);
-            k_merkle_levels_to(c, c->trace_leaves, c->trace_nodes, c->Bc * n, n);
+            k_merkle(c, c->trace_leaves, c->trace_nodes, c->Bc * n, n);
             return DST_OK;
         });
         return;
@@ -858,7 +858,7 @@ void commit_trace_columns(Sharded& S) {
     if (c->sh_ev[1]) (void)hipEventRecord(c->sh_ev[1], c->stream);        // end of the extension (phase 0 | 1)
     S.local([&]() -> int {
         k_trace_leaves(c);
-        k_merkle_levels_to(c, c->trace_leaves, c->trace_nodes, c->Bc * n, n);
+        k_merkle(c, c->trace_leaves, c->trace_nodes, c->Bc * n, n);
         return DST_OK;
     });
 }

@@ -27,10 +27,17 @@ __device__ __forceinline__ fe ptab(const PowTab& p, uint64_t e) {
     fe v = p.lo[l];
     return h ? fe_mul(v, p.hi[h]) : v;
 }
+// the split of the exponents 0 .. max_exp: what the tables hold and what has to be reserved for them follow from this one statement
+struct PowSplit { uint32_t lb, hb; };
+static PowSplit pow_split(size_t max_exp) {
+    uint32_t bits = 1; while (((size_t)1 << bits) < max_exp + 1) bits++;
+    PowSplit s; s.lb = (bits + 1) / 2; s.hb = bits - s.lb;
+    return s;
+}
 // builds the tables for `b` into scratch memory at `where` (needs 2^lb + 2^hb elements)
 static PowTab build_pow_table(dst_ctx* c, fe* where, fe b, size_t max_exp) {
-    uint32_t bits = 1; while (((size_t)1 << bits) < max_exp + 1) bits++;
-    uint32_t lb = (bits + 1) / 2, hb = bits - lb;
+    const PowSplit s = pow_split(max_exp);
+    const uint32_t lb = s.lb, hb = s.hb;
     fe* lo = where; fe* hi = where + ((size_t)1 << lb);
     uint32_t cnt = 1u << lb;
     { KScope ks_(c, "pow_table_kernel", 0.0); hipLaunchKernelGGL(pow_table_kernel, dim3((cnt + PT - 1) / PT), dim3(PT), 0, c->stream, lo, hi, b, lb, hb); }
@@ -38,9 +45,8 @@ static PowTab build_pow_table(dst_ctx* c, fe* where, fe b, size_t max_exp) {
     return t;
 }
 static size_t pow_table_elems(size_t max_exp) {
-    uint32_t bits = 1; while (((size_t)1 << bits) < max_exp + 1) bits++;
-    uint32_t lb = (bits + 1) / 2, hb = bits - lb;
-    return ((size_t)1 << lb) + ((size_t)1 << hb);
+    const PowSplit s = pow_split(max_exp);
+    return ((size_t)1 << s.lb) + ((size_t)1 << s.hb);
 }
 
 // ---- additive exclusive suffix scan: data[i] <- sum_{t > i} data[t] --------------------------------------------------------------
@@ -141,31 +147,34 @@ __device__ __forceinline__ void sd_load_chunk(fe* tile, const fe* __restrict__ a
 #pragma unroll
     for (int j = 0; j < 8; j++) v[j] = tile[sd_slot(threadIdx.x * 8 + j)];
 }
-__global__ void __launch_bounds__(PT) syn_div_chunk_sums_kernel(const fe* __restrict__ a, size_t len, SynDivArgs p, fe* __restrict__ sums) {
-    __shared__ fe tile[SD_TILE];
-    __shared__ fe sh[PT + 1];
+// The two halves of the blocked division, each stated once; the kernels below are one of them and their own sink.  (The powers come by
+// pointer and R_c as a callable, read where the scan wants it: the kernels then compile to what they were with this body written out in
+// each of them, profiles/poly_layer.md.)
+// E_c of the workgroup's chunk (the value is lane 0's): load, lane Horner, scan
+__device__ __forceinline__ fe sd_chunk_value(fe* tile, fe* sh, const fe* __restrict__ a, size_t len, const SynDivArgs* p) {
     fe v[8], e = fe_zero();
     sd_load_chunk(tile, a, len, v);
 #pragma unroll
-    for (int j = 7; j >= 0; j--) e = fe_add(fe_mul_tw(e, p.b), v[j]);
-    const fe y = sd_lane_scan(sh, p, e, fe_zero());
-    if (threadIdx.x == 0) sums[blockIdx.x] = y;
+    for (int j = 7; j >= 0; j--) e = fe_add(fe_mul_tw(e, p->b), v[j]);
+    return sd_lane_scan(sh, *p, e, fe_zero());
 }
-__global__ void __launch_bounds__(PT) syn_div_chunk_kernel(fe* a, size_t len, SynDivArgs p, const fe* __restrict__ right) {
-    __shared__ fe tile[SD_TILE];
-    __shared__ fe sh[PT + 1];
+// the chunk's quotient coefficients, left in the padded tile, given R_c = right(): load, lane Horner keeping the lane's own part, scan, barrier
+template <class Right>
+__device__ __forceinline__ void sd_chunk_quotient(fe* tile, fe* sh, const fe* __restrict__ a, size_t len, const SynDivArgs* p, Right right) {
     fe v[8], q[8], e = fe_zero();
     sd_load_chunk(tile, a, len, v);
 #pragma unroll
-    for (int j = 7; j >= 0; j--) { q[j] = e; e = fe_add(fe_mul_tw(e, p.b), v[j]); }   // q[j] = sum_{j' > j in lane} v[j'] b^(j'-j-1);  e = sum_j v[j] b^j
-    (void)sd_lane_scan(sh, p, e, right ? right[blockIdx.x] : fe_zero());
+    for (int j = 7; j >= 0; j--) { q[j] = e; e = fe_add(fe_mul_tw(e, p->b), v[j]); }   // q[j] = sum_{j' > j in lane} v[j'] b^(j'-j-1);  e = sum_j v[j] b^j
+    (void)sd_lane_scan(sh, *p, e, right());
     fe x = sh[threadIdx.x + 1];                      // everything to the right of this lane, relative to the lane's end
 #pragma unroll
     for (int j = 7; j >= 0; j--) {                   // q_i += b^(7 - j) * x      (a lane reads and writes only its own eight tile slots)
         tile[sd_slot(threadIdx.x * 8 + j)] = fe_add(q[j], x);
-        x = fe_mul_tw(x, p.b);
+        x = fe_mul_tw(x, p->b);
     }
     __syncthreads();
+}
+__device__ __forceinline__ void sd_store_chunk(const fe* tile, fe* a, size_t len) {      // the in-place sink: tile -> a, lane-consecutive
     const size_t base = (size_t)blockIdx.x * SD_CHUNK;
 #pragma unroll
     for (int r = 0; r < 8; r++) { const uint32_t i = r * PT + threadIdx.x; if (base + i < len) a[base + i] = tile[sd_slot(i)]; }
@@ -178,18 +187,7 @@ struct SynDivEpilogue { fe_tw k1, k2, k3; const fe* t; size_t tn, inc; };
 __global__ void __launch_bounds__(PT) syn_div_chunk_out_kernel(const fe* __restrict__ a, fe* __restrict__ out, size_t len, SynDivArgs p, const fe* __restrict__ right, SynDivEpilogue ep) {
     __shared__ fe tile[SD_TILE];
     __shared__ fe sh[PT + 1];
-    fe v[8], q[8], e = fe_zero();
-    sd_load_chunk(tile, a, len, v);
-#pragma unroll
-    for (int j = 7; j >= 0; j--) { q[j] = e; e = fe_add(fe_mul_tw(e, p.b), v[j]); }
-    (void)sd_lane_scan(sh, p, e, right ? right[blockIdx.x] : fe_zero());
-    fe x = sh[threadIdx.x + 1];
-#pragma unroll
-    for (int j = 7; j >= 0; j--) {
-        tile[sd_slot(threadIdx.x * 8 + j)] = fe_add(q[j], x);
-        x = fe_mul_tw(x, p.b);
-    }
-    __syncthreads();
+    sd_chunk_quotient(tile, sh, a, len, &p, [&] { return right ? right[blockIdx.x] : fe_zero(); });
     const size_t base = (size_t)blockIdx.x * SD_CHUNK;
 #pragma unroll
     for (int r = 0; r < 8; r++) {
@@ -203,53 +201,30 @@ __global__ void __launch_bounds__(PT) syn_div_chunk_out_kernel(const fe* __restr
         }
     }
 }
+static fe sqr_times(fe x, int k) {                   // x^(2^k)
+    for (int i = 0; i < k; i++) x = fe_mul(x, x);
+    return x;
+}
 static SynDivArgs syn_div_args(fe b) {
     SynDivArgs p;
     p.b = fe_tw_make(b);
-    fe s = b;
-    for (int i = 0; i < 3; i++) s = fe_mul(s, s);                          // b^8
+    fe s = sqr_times(b, 3);                                                // b^8
     for (int k = 0; k < 9; k++) { p.step[k] = fe_tw_make(s); s = fe_mul(s, s); }
     return p;
-}
-static void syn_div_blocked(dst_ctx* c, fe* a, size_t len, fe b, fe* scratch) {
-    const size_t chunks = (len + SD_CHUNK - 1) / SD_CHUNK;
-    const SynDivArgs p = syn_div_args(b);
-    if (chunks > 1) {
-        { KScope ks_(c, "syn_div_chunk_sums_kernel", 16.0 * len); hipLaunchKernelGGL(syn_div_chunk_sums_kernel, dim3((unsigned)chunks), dim3(PT), 0, c->stream, (const fe*)a, len, p, scratch); }
-        fe bc = b;
-        for (int i = 0; i < 11; i++) bc = fe_mul(bc, bc);                   // b^2048
-        syn_div_blocked(c, scratch, chunks, bc, scratch + chunks);
-    }
-    { KScope ks_(c, "syn_div_chunk_kernel", 32.0 * len); hipLaunchKernelGGL(syn_div_chunk_kernel, dim3((unsigned)chunks), dim3(PT), 0, c->stream, a, len, p, chunks > 1 ? (const fe*)scratch : (const fe*)nullptr); }
-}
-// out = k3 * (a / (x - b)) + k1 * t + k2 * x^inc * t  (t of tn coefficients); `a` is left untouched
-void k_syn_div_compose(dst_ctx* c, const fe* a, fe* out, size_t len, fe b, const fe* t, size_t tn, size_t inc, fe k1, fe k2, fe k3) {
-    fe* scr = c->scratch;
-    const size_t chunks = (len + SD_CHUNK - 1) / SD_CHUNK;
-    const SynDivArgs p = syn_div_args(b);
-    if (chunks > 1) {
-        { KScope ks_(c, "syn_div_chunk_sums_kernel", 16.0 * len); hipLaunchKernelGGL(syn_div_chunk_sums_kernel, dim3((unsigned)chunks), dim3(PT), 0, c->stream, a, len, p, scr); }
-        fe bc = b;
-        for (int i = 0; i < 11; i++) bc = fe_mul(bc, bc);                   // b^2048
-        syn_div_blocked(c, scr, chunks, bc, scr + chunks);
-    }
-    SynDivEpilogue ep{fe_tw_make(k1), fe_tw_make(k2), fe_tw_make(k3), t, tn, inc};
-    { KScope ks_(c, "syn_div_chunk_out_kernel", 32.0 * len); hipLaunchKernelGGL(syn_div_chunk_out_kernel, dim3((unsigned)chunks), dim3(PT), 0, c->stream, a, out, len, p, chunks > 1 ? (const fe*)scr : (const fe*)nullptr, ep); }
 }
 // ---- several divisions / evaluations in one set of launches -------------------------------------------------------------------------
 // Up to four arrays of the same length, each with its own divisor (x - b_k), through the blocked division above: blockIdx.y selects the array.
 // (A division of 2^20 coefficients is three launches of a few hundred workgroups; the boundary quotients need four of them and the DEEP
-// composition two -- batched they are three launches of four times the width.)  b = 1 (plain suffix sums) goes the same way.
-struct SynDivBatch { fe* a[4]; fe* sums[4]; SynDivArgs p[4]; };
-__global__ void __launch_bounds__(PT) syn_div_sums_batch_kernel(SynDivBatch B, size_t len) {
+// composition two -- batched they are three launches of four times the width.)  b = 1 (plain suffix sums) goes the same way, and ONE array is
+// a batch of one: there is no other statement of the blocked division.
+template <class T> struct SynDivBatchT { T* a[4]; fe* sums[4]; SynDivArgs p[4]; };
+typedef SynDivBatchT<const fe> SynDivBatchIn;        // the sums pass only reads its arrays
+typedef SynDivBatchT<fe> SynDivBatch;                // the final pass divides them in place
+__global__ void __launch_bounds__(PT) syn_div_sums_batch_kernel(SynDivBatchIn B, size_t len) {
     __shared__ fe tile[SD_TILE];
     __shared__ fe sh[PT + 1];
     const SynDivArgs& p = B.p[blockIdx.y];
-    fe v[8], e = fe_zero();
-    sd_load_chunk(tile, B.a[blockIdx.y], len, v);
-#pragma unroll
-    for (int j = 7; j >= 0; j--) e = fe_add(fe_mul_tw(e, p.b), v[j]);
-    const fe y = sd_lane_scan(sh, p, e, fe_zero());
+    const fe y = sd_chunk_value(tile, sh, B.a[blockIdx.y], len, &p);
     if (threadIdx.x == 0) B.sums[blockIdx.y][blockIdx.x] = y;
 }
 __global__ void __launch_bounds__(PT) syn_div_chunk_batch_kernel(SynDivBatch B, size_t len, int use_right) {
@@ -257,38 +232,43 @@ __global__ void __launch_bounds__(PT) syn_div_chunk_batch_kernel(SynDivBatch B, 
     __shared__ fe sh[PT + 1];
     const SynDivArgs& p = B.p[blockIdx.y];
     fe* a = B.a[blockIdx.y];
-    fe v[8], q[8], e = fe_zero();
-    sd_load_chunk(tile, a, len, v);
-#pragma unroll
-    for (int j = 7; j >= 0; j--) { q[j] = e; e = fe_add(fe_mul_tw(e, p.b), v[j]); }
-    (void)sd_lane_scan(sh, p, e, use_right ? B.sums[blockIdx.y][blockIdx.x] : fe_zero());
-    fe x = sh[threadIdx.x + 1];
-#pragma unroll
-    for (int j = 7; j >= 0; j--) {
-        tile[sd_slot(threadIdx.x * 8 + j)] = fe_add(q[j], x);
-        x = fe_mul_tw(x, p.b);
-    }
-    __syncthreads();
-    const size_t base = (size_t)blockIdx.x * SD_CHUNK;
-#pragma unroll
-    for (int r = 0; r < 8; r++) { const uint32_t i = r * PT + threadIdx.x; if (base + i < len) a[base + i] = tile[sd_slot(i)]; }
+    sd_chunk_quotient(tile, sh, a, len, &p, [&] { return use_right ? B.sums[blockIdx.y][blockIdx.x] : fe_zero(); });
+    sd_store_chunk(tile, a, len);
+}
+static void syn_div_batch_rec(dst_ctx* c, fe* const* a, const fe* b, int count, size_t len, fe* scratch);
+// The recursion, once.  Fills sums[k] = scratch + k * chunks and p[k] for the caller's final launch; when `len` is more than one chunk:
+// E_c of every chunk (sums pass), then the same division one level up, by (x - b^2048) on the sums in place with the scratch behind them, which
+// leaves R_c in sums[k][c].  Returns whether these `right` arrays exist.  The caller follows with its final launch over the same chunks.
+static bool syn_div_right(dst_ctx* c, const fe* const* a, const fe* b, int count, size_t len, fe* scratch, fe** sums, SynDivArgs* p) {
+    const size_t chunks = (len + SD_CHUNK - 1) / SD_CHUNK;
+    SynDivBatchIn B{};
+    for (int k = 0; k < count; k++) { B.a[k] = a[k]; B.sums[k] = sums[k] = scratch + (size_t)k * chunks; B.p[k] = p[k] = syn_div_args(b[k]); }
+    if (chunks == 1) return false;
+    fe bc[4];
+    for (int k = 0; k < count; k++) bc[k] = sqr_times(b[k], 11);           // b^2048
+    { KScope ks_(c, "syn_div_sums_batch_kernel", 16.0 * len * count); hipLaunchKernelGGL(syn_div_sums_batch_kernel, dim3((unsigned)chunks, (unsigned)count), dim3(PT), 0, c->stream, B, len); }
+    syn_div_batch_rec(c, sums, bc, count, chunks, scratch + (size_t)count * chunks);
+    return true;
 }
 // a[k] <- a[k] / (x - b[k]) in place, k < count <= 4, all of `len` coefficients; scratch: count * (chunks + chunks' + ..) elements
 static void syn_div_batch_rec(dst_ctx* c, fe* const* a, const fe* b, int count, size_t len, fe* scratch) {
     const size_t chunks = (len + SD_CHUNK - 1) / SD_CHUNK;
     SynDivBatch B{};
-    for (int k = 0; k < count; k++) { B.a[k] = a[k]; B.sums[k] = scratch + (size_t)k * chunks; B.p[k] = syn_div_args(b[k]); }
-    if (chunks > 1) {
-        { KScope ks_(c, "syn_div_sums_batch_kernel", 16.0 * len * count); hipLaunchKernelGGL(syn_div_sums_batch_kernel, dim3((unsigned)chunks, (unsigned)count), dim3(PT), 0, c->stream, B, len); }
-        fe bc[4]; fe* sub[4];
-        for (int k = 0; k < count; k++) { bc[k] = b[k]; for (int i = 0; i < 11; i++) bc[k] = fe_mul(bc[k], bc[k]); sub[k] = B.sums[k]; }      // b^2048
-        syn_div_batch_rec(c, sub, bc, count, chunks, scratch + (size_t)count * chunks);
-    }
-    { KScope ks_(c, "syn_div_chunk_batch_kernel", 32.0 * len * count); hipLaunchKernelGGL(syn_div_chunk_batch_kernel, dim3((unsigned)chunks, (unsigned)count), dim3(PT), 0, c->stream, B, len, chunks > 1 ? 1 : 0); }
+    for (int k = 0; k < count; k++) B.a[k] = a[k];
+    const bool right = syn_div_right(c, a, b, count, len, scratch, B.sums, B.p);
+    { KScope ks_(c, "syn_div_chunk_batch_kernel", 32.0 * len * count); hipLaunchKernelGGL(syn_div_chunk_batch_kernel, dim3((unsigned)chunks, (unsigned)count), dim3(PT), 0, c->stream, B, len, right ? 1 : 0); }
 }
 void k_syn_div_batch(dst_ctx* c, fe* const* a, const fe* b, int count, size_t len) {
     for (int k = 0; k < count; k++) if (fe_is_zero(b[k]) || c->sw("DISTAFF_SYN_DIV_TABLES")) { for (int q = 0; q < count; q++) k_syn_div(c, a[q], len, b[q]); return; }   // the special forms keep their own path
     syn_div_batch_rec(c, a, b, count, len, c->scratch);
+}
+// out = k3 * (a / (x - b)) + k1 * t + k2 * x^inc * t  (t of tn coefficients); `a` is left untouched
+void k_syn_div_compose(dst_ctx* c, const fe* a, fe* out, size_t len, fe b, const fe* t, size_t tn, size_t inc, fe k1, fe k2, fe k3) {
+    const size_t chunks = (len + SD_CHUNK - 1) / SD_CHUNK;
+    fe* sums; SynDivArgs p;
+    const bool right = syn_div_right(c, &a, &b, 1, len, c->scratch, &sums, &p);
+    SynDivEpilogue ep{fe_tw_make(k1), fe_tw_make(k2), fe_tw_make(k3), t, tn, inc};
+    { KScope ks_(c, "syn_div_chunk_out_kernel", 32.0 * len); hipLaunchKernelGGL(syn_div_chunk_out_kernel, dim3((unsigned)chunks), dim3(PT), 0, c->stream, a, out, len, p, right ? (const fe*)sums : (const fe*)nullptr, ep); }
 }
 
 void k_syn_div(dst_ctx* c, fe* a, size_t len, fe b) {
@@ -300,7 +280,7 @@ void k_syn_div(dst_ctx* c, fe* a, size_t len, fe b) {
         return;
     }
     if (fe_eq(b, fe_one())) { suffix_scan(c, a, len, scr); return; }     // division by (x - 1): q_i = sum_{t > i} a_t, the exclusive scan itself (first-step boundary polynomial)
-    if (!c->sw("DISTAFF_SYN_DIV_TABLES")) { syn_div_blocked(c, a, len, b, scr); return; }
+    if (!c->sw("DISTAFF_SYN_DIV_TABLES")) { syn_div_batch_rec(c, &a, &b, 1, len, scr); return; }
     // the first formulation, kept as an independent statement (tests run both): scale by b^t, additive suffix scan, scale by b^-(i+1)
     size_t te = pow_table_elems(len + 1);
     PowTab fw = build_pow_table(c, scr, b, len + 1);
@@ -327,6 +307,16 @@ void k_syn_div_expanded(dst_ctx* c, const fe* a, fe* out, size_t len, size_t deg
 }
 
 // ---- evaluation of `ncols` polynomials of `len` coefficients at x -----------------------------------------------------------------
+// sum over the PT lanes of a workgroup, one value each, by a tree in LDS (sh[PT]); lane 0 uses the result
+__device__ __forceinline__ fe block_sum(fe* sh, fe acc) {
+    sh[threadIdx.x] = acc;
+    __syncthreads();
+    for (int off = PT / 2; off > 0; off >>= 1) {
+        if ((int)threadIdx.x < off) sh[threadIdx.x] = fe_add(sh[threadIdx.x], sh[threadIdx.x + off]);
+        __syncthreads();
+    }
+    return sh[0];
+}
 __global__ void __launch_bounds__(PT) horner_partial_kernel(const fe* __restrict__ polys, size_t len, PowTab p, fe* __restrict__ partial) {
     __shared__ fe sh[PT];
     const fe* poly = polys + (size_t)blockIdx.y * len;
@@ -335,25 +325,15 @@ __global__ void __launch_bounds__(PT) horner_partial_kernel(const fe* __restrict
         fe v = poly[i];
         acc = fe_add(acc, i ? fe_mul(v, ptab(p, i)) : v);
     }
-    sh[threadIdx.x] = acc;
-    __syncthreads();
-    for (int off = PT / 2; off > 0; off >>= 1) {
-        if ((int)threadIdx.x < off) sh[threadIdx.x] = fe_add(sh[threadIdx.x], sh[threadIdx.x + off]);
-        __syncthreads();
-    }
-    if (threadIdx.x == 0) partial[(size_t)blockIdx.y * gridDim.x + blockIdx.x] = sh[0];
+    const fe sum = block_sum(sh, acc);
+    if (threadIdx.x == 0) partial[(size_t)blockIdx.y * gridDim.x + blockIdx.x] = sum;
 }
 __global__ void __launch_bounds__(PT) reduce_rows_kernel(const fe* __restrict__ partial, size_t per_row, fe* __restrict__ out) {
     __shared__ fe sh[PT];
     fe acc = fe_zero();
     for (size_t i = threadIdx.x; i < per_row; i += PT) acc = fe_add(acc, partial[(size_t)blockIdx.x * per_row + i]);
-    sh[threadIdx.x] = acc;
-    __syncthreads();
-    for (int off = PT / 2; off > 0; off >>= 1) {
-        if ((int)threadIdx.x < off) sh[threadIdx.x] = fe_add(sh[threadIdx.x], sh[threadIdx.x + off]);
-        __syncthreads();
-    }
-    if (threadIdx.x == 0) out[blockIdx.x] = sh[0];
+    const fe sum = block_sum(sh, acc);
+    if (threadIdx.x == 0) out[blockIdx.x] = sum;
 }
 // results land in device memory `out_dev[ncols]`
 void k_horner(dst_ctx* c, const fe* polys, size_t ncols, size_t len, fe x, fe* out_dev) {
@@ -386,18 +366,17 @@ __global__ void lincomb_kernel(const fe* __restrict__ cols, size_t ncols, size_t
 #pragma unroll
     for (int q = 0; q < NOUT; q++) out.p[q][i] = fe_acc_reduce(acc[q]);
 }
-void k_lincomb(dst_ctx* c, const fe* cols, size_t ncols, size_t len, const fe* coeffs_dev, fe* out) {
-    LincombOut o{{out, nullptr, nullptr, nullptr}};
-    { KScope ks_(c, "lincomb_kernel", 16.0 * len * (ncols + 1)); hipLaunchKernelGGL(lincomb_kernel<1>, dim3((unsigned)((len + PT - 1) / PT)), dim3(PT), 0, c->stream, cols, ncols, len, coeffs_dev, ncols, o); }
+template <int NOUT>
+static void lincomb_launch(dst_ctx* c, const fe* cols, size_t ncols, size_t len, const fe* coeffs_dev, size_t coef_stride, LincombOut o) {
+    KScope ks_(c, "lincomb_kernel", 16.0 * len * (ncols + NOUT));
+    hipLaunchKernelGGL(lincomb_kernel<NOUT>, dim3((unsigned)((len + PT - 1) / PT)), dim3(PT), 0, c->stream, cols, ncols, len, coeffs_dev, coef_stride, o);
 }
 void k_lincomb4(dst_ctx* c, const fe* cols, size_t ncols, size_t len, const fe* coeffs_dev, fe* out0, fe* out1, fe* out2, fe* out3) {
-    LincombOut o{{out0, out1, out2, out3}};
-    { KScope ks_(c, "lincomb_kernel", 16.0 * len * (ncols + 4)); hipLaunchKernelGGL(lincomb_kernel<4>, dim3((unsigned)((len + PT - 1) / PT)), dim3(PT), 0, c->stream, cols, ncols, len, coeffs_dev, ncols, o); }
+    lincomb_launch<4>(c, cols, ncols, len, coeffs_dev, ncols, LincombOut{{out0, out1, out2, out3}});
 }
 // two combinations whose coefficient vectors are coef_stride elements apart
 void k_lincomb2(dst_ctx* c, const fe* cols, size_t ncols, size_t len, const fe* coeffs_dev, size_t coef_stride, fe* out0, fe* out1) {
-    LincombOut o{{out0, out1, nullptr, nullptr}};
-    { KScope ks_(c, "lincomb_kernel", 16.0 * len * (ncols + 2)); hipLaunchKernelGGL(lincomb_kernel<2>, dim3((unsigned)((len + PT - 1) / PT)), dim3(PT), 0, c->stream, cols, ncols, len, coeffs_dev, coef_stride, o); }
+    lincomb_launch<2>(c, cols, ncols, len, coeffs_dev, coef_stride, LincombOut{{out0, out1, nullptr, nullptr}});
 }
 __global__ void axpy_kernel(fe* y, const fe* x, fe a, size_t len) {
     size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
@@ -468,25 +447,28 @@ __global__ void __launch_bounds__(PT) fri_fold_kernel(const fe* __restrict__ e, 
     if (a.alpha_dev) a.alpha = *a.alpha_dev;
     out[r] = fold_row(a, e[r], e[r + R], e[r + 2 * R], e[r + 3 * R], (uint64_t)r << log_stride);
 }
+static FoldArgs fold_args(dst_ctx* c, fe x, const fe* alpha_dev) {
+    FoldArgs a{};
+    a.itw_lo = c->itw_lo; a.itw_hi = c->itw_hi; a.lo_bits = c->tw_lo_bits; a.log_N = c->log_N;
+    a.alpha = x; a.iota = c->iota; a.quarter = c->four_inv; a.alpha_dev = alpha_dev;
+    return a;
+}
+void k_fri_fold_at(dst_ctx* c, const fe* e, fe* out, size_t R, int layer, fe special_x, const fe* alpha_dev) {      // natural-order layer `layer` of 4R evaluations -> R
+    const FoldArgs a = fold_args(c, special_x, alpha_dev);
+    { KScope ks_(c, "fri_fold_kernel", 80.0 * R); hipLaunchKernelGGL(fri_fold_kernel, dim3((unsigned)((R + PT - 1) / PT)), dim3(PT), 0, c->stream, e, out, R, (uint32_t)(2 * layer), a); }
+}
 static void fri_fold_launch(dst_ctx* c, int layer, fe special_x, const fe* alpha_dev);
 void k_fri_fold(dst_ctx* c, int layer, fe special_x) { fri_fold_launch(c, layer, special_x, nullptr); }
 void k_fri_fold_dev(dst_ctx* c, int layer, const fe* alpha_dev) { fri_fold_launch(c, layer, fe_zero(), alpha_dev); }
 static void fri_fold_launch(dst_ctx* c, int layer, fe special_x, const fe* alpha_dev) {
-    FoldArgs a{};
-    a.itw_lo = c->itw_lo; a.itw_hi = c->itw_hi; a.lo_bits = c->tw_lo_bits; a.log_N = c->log_N;
-    a.alpha = special_x; a.iota = c->iota; a.quarter = c->four_inv; a.alpha_dev = alpha_dev;
-    size_t R = c->fri_size[layer] / 4;
-    if (layer == 0) {
-        uint32_t jt = c->Bc < 32 ? (uint32_t)c->Bc : 32u, log_jt = 0;
-        while ((1u << log_jt) < jt) log_jt++;
-        const size_t want = (c->n / 4) << log_jt;
-        const uint32_t threads = (uint32_t)(want < PT ? want : PT), KT = threads >> log_jt;      // never an empty grid (tiny traces, many ranks)
-        dim3 g((unsigned)((c->n / 4) / KT), (unsigned)(c->Bc >> log_jt));
-        { KScope ks_(c, "fri_fold0_kernel", 80.0 * (c->n / 4) * c->Bc); hipLaunchKernelGGL(fri_fold0_kernel, g, dim3(threads), 0, c->stream, (const fe*)c->comp, c->fri_e[1], c->n, (uint32_t)c->Bc, c->log_b, log_jt, (uint32_t)c->j0, a); }
-    } else {
-        { KScope ks_(c, "fri_fold_kernel", 80.0 * R); hipLaunchKernelGGL(fri_fold_kernel, dim3((unsigned)((R + PT - 1) / PT)), dim3(PT), 0, c->stream, (const fe*)c->fri_e[layer], c->fri_e[layer + 1], R,
-                           (uint32_t)(2 * layer), a); }
-    }
+    if (layer > 0) { k_fri_fold_at(c, c->fri_e[layer], c->fri_e[layer + 1], c->fri_size[layer] / 4, layer, special_x, alpha_dev); return; }
+    const FoldArgs a = fold_args(c, special_x, alpha_dev);
+    uint32_t jt = c->Bc < 32 ? (uint32_t)c->Bc : 32u, log_jt = 0;
+    while ((1u << log_jt) < jt) log_jt++;
+    const size_t want = (c->n / 4) << log_jt;
+    const uint32_t threads = (uint32_t)(want < PT ? want : PT), KT = threads >> log_jt;      // never an empty grid (tiny traces, many ranks)
+    dim3 g((unsigned)((c->n / 4) / KT), (unsigned)(c->Bc >> log_jt));
+    { KScope ks_(c, "fri_fold0_kernel", 80.0 * (c->n / 4) * c->Bc); hipLaunchKernelGGL(fri_fold0_kernel, g, dim3(threads), 0, c->stream, (const fe*)c->comp, c->fri_e[1], c->n, (uint32_t)c->Bc, c->log_b, log_jt, (uint32_t)c->j0, a); }
 }
 
 // ---- the small FRI layers in ONE launch -------------------------------------------------------------------------------------------------
@@ -606,8 +588,7 @@ int k_fri_tail(dst_ctx* c, int first, uint8_t* roots_out) {
     for (int i = 0; i < count; i++) { a.e[i] = c->fri_e[first + i]; a.leaves[i] = c->fri_leaves[first + i]; a.nodes[i] = c->fri_nodes[first + i]; a.rows[i] = (uint32_t)(c->fri_size[first + i] / 4); }
     a.first = (uint32_t)first; a.count = (uint32_t)count;
     a.roots = (uint32_t*)(c->d_u64 + 8);                                   // 12 x 32 bytes behind the small device scalars (d_u64 holds 64 words)
-    a.fold.itw_lo = c->itw_lo; a.fold.itw_hi = c->itw_hi; a.fold.lo_bits = c->tw_lo_bits; a.fold.log_N = c->log_N;
-    a.fold.alpha = fe_zero(); a.fold.iota = c->iota; a.fold.quarter = c->four_inv;
+    a.fold = fold_args(c, fe_zero(), nullptr);                             // alpha is drawn per layer
     { KScope ks_(c, "fri_tail_kernel", 0.0); hipLaunchKernelGGL(fri_tail_kernel, dim3(1), dim3(FRI_TAIL_THREADS), 0, c->stream, a); }
     // read back into page-locked memory (the sharded prover queues this behind its exchanges: a pageable destination would make the host
     // wait inside hipMemcpyAsync, in front of the bounded wait below)
@@ -854,16 +835,8 @@ __global__ void __launch_bounds__(PT) fri_fold_cm_kernel(const fe* __restrict__ 
     uint64_t r = ((uint64_t)k << log_b) + j0 + jl;
     out[jl * q + k] = fold_row(a, base[0], base[q], base[2 * q], base[3 * q], r << log_stride);
 }
-void k_fri_fold_at(dst_ctx* c, const fe* e, fe* out, size_t R, int layer, fe special_x, const fe* alpha_dev) {      // natural-order layer `layer` of 4R evaluations -> R
-    FoldArgs a{};
-    a.itw_lo = c->itw_lo; a.itw_hi = c->itw_hi; a.lo_bits = c->tw_lo_bits; a.log_N = c->log_N;
-    a.alpha = special_x; a.iota = c->iota; a.quarter = c->four_inv; a.alpha_dev = alpha_dev;
-    { KScope ks_(c, "fri_fold_kernel", 80.0 * R); hipLaunchKernelGGL(fri_fold_kernel, dim3((unsigned)((R + PT - 1) / PT)), dim3(PT), 0, c->stream, e, out, R, (uint32_t)(2 * layer), a); }
-}
 void k_fri_fold_cm(dst_ctx* c, const fe* e, fe* out, size_t nd, int layer, fe special_x, const fe* alpha_dev) {
-    FoldArgs a{};
-    a.itw_lo = c->itw_lo; a.itw_hi = c->itw_hi; a.lo_bits = c->tw_lo_bits; a.log_N = c->log_N;
-    a.alpha = special_x; a.iota = c->iota; a.quarter = c->four_inv; a.alpha_dev = alpha_dev;
+    const FoldArgs a = fold_args(c, special_x, alpha_dev);
     size_t total = nd / 4 * c->Bc;
     { KScope ks_(c, "fri_fold_cm_kernel", 80.0 * total); hipLaunchKernelGGL(fri_fold_cm_kernel, dim3((unsigned)((total + PT - 1) / PT)), dim3(PT), 0, c->stream, e, out, nd, (uint32_t)c->Bc, c->log_b,
                        (uint32_t)c->j0, (uint32_t)(2 * layer), a); }

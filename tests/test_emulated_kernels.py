@@ -75,6 +75,7 @@ SELECTION = WHOLE_DOMAIN + [
     "test_lde_every_tile_length[lds-16-5]",
     "test_trace_from_pinned_host_memory[w17]",
     "test_synthetic_division_by_power_tables",
+] + ["test_polynomial_layer_launches[%d-%s]" % (log_n, mode) for log_n in (7, 10, 12) for mode in ("default", "steps", "tables")] + [
     "test_trace_in_its_own_buffer",
     "test_small_fri_layers_in_one_launch_equal_the_per_layer_path",
     "test_prove_sharded_with_collectives_on_their_own_stream[2]",

@@ -116,6 +116,46 @@ def test_synthetic_division_by_power_tables(oracle, monkeypatch):
     _check_all_phases(oracle, D, oracle.fibonacci_trace(1 << 12))
 
 
+POLY_KERNELS = tuple(k + "_kernel" for k in (
+    "pow_table", "scan_block", "scan_add_offsets", "scale_by_powers", "shift_down", "syn_div_sums_batch", "syn_div_chunk_batch", "syn_div_chunk_out",
+    "syn_div_expanded", "horner_partial", "reduce_rows", "lincomb", "axpy", "add", "sub_dot_at0", "sub_at0", "fri_fold0", "fri_fold"))
+POLY_MODES = {"default": {}, "steps": {"DISTAFF_COMBINE": "steps"}, "tables": {"DISTAFF_SYN_DIV_TABLES": "1"}}
+
+
+def poly_layer_launches(D, log_n, mode):
+    """{kernel: [launches, profiling bytes]} of the polynomial and fold kernels of kernels_poly.hip in one 2^log_n-step Fibonacci proof"""
+    cols, _, result = D.fibonacci_trace(log_n)
+    ctx = D.Context(log_n, 20, 1, 0, grinding=8)
+    ctx.upload(cols)
+    ctx.set_profiling(1)
+    ctx.prove([1, 0], [result])
+    stats = ctx.kernel_stats()
+    ctx.close()
+    return {name: [st["launches"], st["bytes"]] for name, st in stats.items() if name in POLY_KERNELS}
+
+
+@pytest.mark.parametrize("mode", list(POLY_MODES))
+@pytest.mark.parametrize("log_n", [7, 10, 12])
+def test_polynomial_layer_launches(monkeypatch, log_n, mode):
+    """The launches of a proof do not move: which division, evaluation, combination and fold kernels a proof launches, how often and over how
+    many bytes, against tests/golden/poly_launches.json (the proofs themselves are compared by the other tests; a division routed to the
+    per-array fallback or a further recursion level would leave them right).  2^7: every division is one chunk, no sums launch; 2^10:
+    n + 1 = 1025 coefficients are one chunk and 8n = 8192 are four, one level of recursion; 2^12: n + 1 = 4097 are two full chunks and a
+    one-element tail in a batch of four, 8n are 16 chunks.  (Three levels first occur at 8n = 2^23: the sampled-parity test at 2^20.)
+    A kernel that the recorded proof did not launch must not be launched."""
+    import json
+    import os
+    import distaff_amd as D
+    for switches in POLY_MODES.values():
+        for k in switches:
+            monkeypatch.delenv(k, raising=False)
+    for k, v in POLY_MODES[mode].items():
+        monkeypatch.setenv(k, v)                      # the library reads its switches when a context is created
+    golden = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "poly_launches.json")
+    want = json.load(open(golden))["%d-%s" % (log_n, mode)]
+    assert poly_layer_launches(D, log_n, mode) == want
+
+
 @pytest.mark.parametrize("instance", ["", "small", "deep", "generic"])
 def test_boundary_constraints_by_evaluation(oracle, monkeypatch, instance):
     """The evaluate-and-interpolate route of the two boundary combinations (the reference's own, constraint_table.rs:54-62): its

@@ -56,7 +56,7 @@ static const dst_switch_def DST_SWITCHES[] = {
     {"DISTAFF_AIR",                false, "small|deep|generic", "force a more general constraint-kernel instance set than the trace shape needs (generic = per-operation formulation)"},
     {"DISTAFF_BOUNDARY",           false, "eval",            "boundary combinations by evaluation on the 8n domain (the reference's route) instead of coefficient form"},
     {"DISTAFF_COMBINE",            false, "steps",           "combine_polys / DEEP composition as the reference's sequence of whole-array steps instead of the fused passes"},
-    {"DISTAFF_NTT",                false, "pre|3pass|reg|lds", "force a transform plan family"},
+    {"DISTAFF_NTT",                false, "pre|pre_a|3pass|reg|lds|row", "force a transform plan family (pre_a: a register pre-stage in the first pass only; row: the default plan with row-major staging array and tables)"},
     {"DISTAFF_NTT_SHAPE",          false, "a,b",             "three-pass plans: log2 of the first two pass lengths"},
     {"DISTAFF_NTT_ORDER",          false, "0",               "first pass of an extension in coset-slow block order"},
     {"DISTAFF_NTT_WAVES",          false, "4|8",             "force the 512- or 1024-lane instances of the LDS passes"},
@@ -155,6 +155,7 @@ struct NttPlan {
     uint32_t log_n3 = 0;                             // 0: two passes (second pass length n2); else three passes n = n1 * (n2/n3) * n3
     uint32_t count = 0;                              // 2 or 3
     bool coset_slow = false; uint32_t debug = 0;     // DISTAFF_NTT_ORDER=0, DISTAFF_NTT_DEBUG
+    bool tile_major = false;                         // layout of the staging array and the four-step tables (kernels_ntt.hip: ntt_tile_major)
     NttPass pass[3], first_lde;                      // first_lde: pass[0] as the first pass of an extension (its DIT mode, LDS bytes and instance differ)
     const NttPass& at(uint32_t i, bool lde) const { return (i == 0 && lde) ? first_lde : pass[i]; }
 };

@@ -15,8 +15,11 @@
 // is in LDS, the 1024-lane instances of 1024-point tiles (8 waves per SIMD) leave the overlap to the CU's other workgroup.
 // The low-degree extension never materialises the zero-padded size-N input of the reference: the N = B*n evaluations
 // are B coset transforms of size n (coset j holds the reference's indices B*k + j), stored coset-major; coset 0 of the trace
-// extension is the trace itself and is copied.  HBM accesses are T*16-byte segments (T = 4 for 1024-point tiles, 16 for the
-// 256-point tiles of three-pass plans).  A second, register-radix kernel family (ntt_reg_kernel) is kept as an independent
+// extension is the trace itself and is copied.  The staging array between the passes and the four-step table are private to the
+// transforms: two-pass plans up to n = 2^21 whose tiles are four columns wide in both passes keep them TILE-MAJOR (NttArgs::tile_major)
+// -- a first-pass tile stores one contiguous block of 16 * n1 * 4 bytes and reads its twiddles from one, a second-pass tile reads
+// 256-byte runs; every other plan keeps them row-major in T*16-byte segments (T = 16 for the 256-point tiles of three-pass plans).
+// A second, register-radix kernel family (ntt_reg_kernel) is kept as an independent
 // implementation that the tests run at every tile length.
 // The host side is in this file too ("launch layer" below): the table of compiled instances, the plan of a context (ntt_plan_derive: passes, tile
 // shapes, kernel family and instance per pass), its tables (k_ntt_init, called by dst_ctx_create) and ONE function that launches a pass (ntt_run_pass).
@@ -40,8 +43,17 @@ struct NttArgs {
     const fe_tw* stage_tw;     // w_len^t, t < len/2 (forward or inverse), as table pairs
     const fe_tw* prescale;     // w_{B*n1}^t or nullptr
     const fe_tw* dit_last;     // coset DIT whose last-stage twiddles stay in global memory: [B][n1/2] pairs w_{B*n1}^(j + B*k), else nullptr
-    const tw4_t* tw4;          // four-step twiddles in output order [coset][k1][m2] (coset stride tw4_coset_stride)
+    const tw4_t* tw4;          // four-step twiddles in the order of the first pass's output (coset stride tw4_coset_stride)
     size_t tw4_coset_stride;
+    // Layout of the array between the two passes and of the four-step table.  0: row-major, element (k1, m2) at (k1 << log_n2) + m2.
+    // 1 (ntt_tile_major: two-pass plans with four-column tiles in both passes): tile-major, [m2 >> 2][k1][m2 & 3] -- element (k1, m2) at
+    // (((m2 >> 2) << log2(number of k1)) + k1) * 4 + (m2 & 3).  The block of a first-pass tile (four adjacent m2, every k1) is contiguous and
+    // in the order the tile leaves LDS; a second-pass tile (four adjacent k1, every m2) reads runs of 16 elements (256 bytes), one per group
+    // of four m2.  Plans whose SECOND pass has a register pre-stage (n = 2^22) stay row-major: there the second pass lost 1.3 ms of 42 to the
+    // runs and the first pass, whose two halves of the frequencies interleave in 64-byte segments, gained nothing (profiles/ntt_tile_major.md).
+    // Every instance whose tiles can be four columns wide reads the flag (uniform): the 1024 x 4 second pass also serves row-major plans
+    // (DISTAFF_NTT=lds at 2^21: 2048 x 2 first pass).
+    uint32_t tile_major;
     uint32_t log_n1, log_n2, tile /* log2 of the tile width */, log_N, log_b;
     uint32_t j0;               // global index of the first local coset
     uint32_t has_scale;        // 1: multiply the result by `scale` (1/n of inverse transforms)
@@ -133,8 +145,8 @@ struct OutB {                                          // natural-order store X[
 // of the pass's three global streams out of the memory system while every instruction stays -- the bound of anything that could be done
 // about that stream.  NTT_LAB_SRC_SMALL=1: the coefficient loads of every workgroup fall into a 64 KiB window (cache hits); =2: only those
 // of the odd-half workgroups of a register pre-stage pass (the upper bound of SHARING the loads between the halves);
-// NTT_LAB_TW4_SMALL: the four-step twiddles come from a 64 KiB window per coset; NTT_LAB_DST_DENSE: a tile is stored as one contiguous
-// 64 KiB block instead of 64-byte row segments a row stride apart.
+// NTT_LAB_TW4_SMALL: the four-step twiddles come from a 64 KiB window per coset.  (A third switch stored a tile as one contiguous 64 KiB
+// block instead of 64-byte row segments a row stride apart: that is what the tile-major layout now does with right results.)
 // (the window is indexed by (row, column) of the tile, so every row still carries different data: a window indexed by the masked ARRAY offset
 // would make the columns periodic, their spectra sparse -- and the kernels measurably faster for that alone, their time depends on the data)
 #if defined(NTT_LAB_SRC_SMALL)
@@ -191,6 +203,8 @@ __global__ void __launch_bounds__(THREADS, WPE) ntt_pass_a(NttArgs a, const fe* 
     const fe* __restrict__ src0 = src_base + (size_t)col * a.src_col_stride + (size_t)jl * a.src_coset_stride;
     fe* __restrict__ dst0 = dst_base + (size_t)col * a.dst_col_stride + (size_t)jl * a.dst_coset_stride;
     const uint32_t pmask = (1u << (a.log_b + log_n1 + PRE)) - 1u;
+    // layout of dst and tw4 (NttArgs); the 16-column instances exist in row-major plans only
+    const bool tile_major = (LOG_T != 0 && LOG_T != 2) ? false : a.tile_major != 0;
     const uint32_t jv = jg + (hh << a.log_b);              // PRE: the half-length transform of frequencies 2k' + h is the coset transform with shift g * w^h
     if (a.dit) {
         // stage twiddles of this coset: g^(n1/B) * w_B^k = w_{B_lde*n1}^((j + B_lde*k) * n1/B) straight from the pre-scale table
@@ -258,12 +272,10 @@ __global__ void __launch_bounds__(THREADS, WPE) ntt_pass_a(NttArgs a, const fe* 
         // live in the last round spill (13.15 / 13.3 against 13.05 ms), in the spill-free fixed-shape instance it is within the noise
         // (18.85 against 18.95 ms of extension, with the twiddle requested before or after the butterfly).
         constexpr int RB = WPE > 4 ? 1 : THREADS == 512 ? 2 : 4;
-#if defined(NTT_LAB_DST_DENSE)
-        fe* __restrict__ dst = dst_base + ((size_t)blockIdx.x * a.tiles_per_block + it) * count;
-#else
-        fe* __restrict__ dst = dst0 + tile * T;          // uniform bases, 32-bit lane offsets
-#endif
-        const tw4_t* __restrict__ tw = tw4 + tile * T;
+        // tile-major: the tile's block of the staging array and of the table, count << PRE elements each; row-major: its first column
+        const size_t tile_at = tile_major ? (size_t)tile * (count << PRE) : (size_t)tile * T;
+        fe* __restrict__ dst = dst0 + tile_at;           // uniform bases, 32-bit lane offsets
+        const tw4_t* __restrict__ tw = tw4 + tile_at;
         for (uint32_t base = 0; base < count; base += RB * THREADS) {
             fe v[RB]; tw4_t w[RB]; uint32_t off[RB]; bool ok[RB];
             static_for<0, RB>([&](auto q_) {
@@ -272,13 +284,13 @@ __global__ void __launch_bounds__(THREADS, WPE) ntt_pass_a(NttArgs a, const fe* 
                 ok[q] = idx < count;
                 idx = ok[q] ? idx : 0u;
                 const uint32_t t = idx & (T - 1), r = idx >> log_t;
-                const uint32_t k1 = ((a.dit ? r : __brev(r) >> (32 - log_n1)) << PRE) + hh;        // DIT leaves the tile in natural order; PRE: frequencies 2 k' + h
-                off[q] = (k1 << a.log_n2) + t;
+                if (tile_major && a.dit && !PRE) off[q] = idx;                                      // the block is the tile as it lies in LDS
+                else {
+                    const uint32_t k1 = ((a.dit ? r : __brev(r) >> (32 - log_n1)) << PRE) + hh;    // DIT leaves the tile in natural order; PRE: frequencies 2 k' + h
+                    off[q] = tile_major ? (k1 << log_t) + t : (k1 << a.log_n2) + t;
+                }
                 v[q] = L[idx];
                 w[q] = tw[NTT_LAB_TW(r, t, off[q])];
-#if defined(NTT_LAB_DST_DENSE)
-                off[q] = idx;
-#endif
             });
             static_for<0, RB>([&](auto q_) {
                 constexpr int q = decltype(q_)::value;
@@ -322,9 +334,15 @@ __global__ void __launch_bounds__(THREADS, WPE) ntt_pass_b(NttArgs a, const fe* 
     // Four-column tiles: lane index = (m2, row), row fastest -- a wavefront reads 16 consecutive elements (256 bytes) of each of the four
     // rows and writes 64 consecutive LDS slots.  (With m2 fastest the slots of neighbouring lanes are 64 bytes apart: the 16 lanes of an
     // access group share their banks four times over.)  Wider tiles keep m2 fastest.
+    // Tile-major source (NttArgs): the four rows of a group of four m2 are one run of 16 elements, the runs of a tile are run_stride = 4 * (number
+    // of k1) elements apart.  Lane index = (group of four m2, row, m2 & 3): the 16 lanes of an access group read one run in address order and
+    // write its 4 x 4 transpose into 16 distinct LDS slots of one 256-byte line.  A second pass with a pre-stage always reads row-major.
+    const bool tile_major = (PRE || (LOG_T != 0 && LOG_T != 2)) ? false : a.tile_major != 0;
+    const uint32_t run_shift = a.log_n1 + 2u;
     const bool colfast_b = log_t == 2 && !NTT_NO_ROTATE_DEFINED;
-#define NTT_ROW_B(idx) (colfast_b ? ((idx) & (T - 1)) : ((idx) >> log_n2))
-#define NTT_M2_B(idx) (colfast_b ? ((idx) >> log_t) : ((idx) & (n2 - 1)))
+#define NTT_ROW_B(idx) (tile_major ? (((idx) >> 2) & 3u) : colfast_b ? ((idx) & (T - 1)) : ((idx) >> log_n2))
+#define NTT_M2_B(idx) (tile_major ? ((((idx) >> 4) << 2) + ((idx) & 3u)) : colfast_b ? ((idx) >> log_t) : ((idx) & (n2 - 1)))
+#define NTT_OFF_B(idx) (tile_major ? ((((idx) >> 4) << run_shift) + ((idx) & 15u)) : (NTT_ROW_B(idx) * row_stride + NTT_M2_B(idx)))
     // PRE (DIF pre-stage, see NttArgs): u_0 = y[m] + y[m + n2], u_1 = (y[m] - y[m + n2]) * w_{2 n2}^m
 #if NTT_STREAM_B_LOAD
 #define NTT_LOAD_B(p) fe_load_stream(p)
@@ -332,10 +350,10 @@ __global__ void __launch_bounds__(THREADS, WPE) ntt_pass_b(NttArgs a, const fe* 
 #define NTT_LOAD_B(p) (*(p))
 #endif
 #define NTT_FETCH_B1(e, var) if constexpr ((e) < EPT) { uint32_t idx = lane + (e) * THREADS; idx = idx < count ? idx : 0u; \
-        if constexpr (PRE != 0) { const uint32_t m_ = NTT_M2_B(idx); const fe* p_ = srct + NTT_ROW_B(idx) * row_stride + m_; const fe x0_ = p_[0], x1_ = p_[n2]; \
+        if constexpr (PRE != 0) { const uint32_t m_ = NTT_M2_B(idx); const fe* p_ = srct + NTT_OFF_B(idx); const fe x0_ = p_[0], x1_ = p_[n2]; \
                                   var = hh ? fe_mul_tw(fe_sub(x0_, x1_), a.pre_tw[m_]) : fe_add(x0_, x1_); } \
-        else var = NTT_LOAD_B(srct + (NTT_ROW_B(idx) * row_stride + NTT_M2_B(idx))); }
-#define NTT_FETCH_B(tile) { const fe* __restrict__ srct = src + (size_t)((tile) * T) * a.src_row_stride; NTT_EACH(NTT_FETCH_B1) }
+        else var = NTT_LOAD_B(srct + NTT_OFF_B(idx)); }
+#define NTT_FETCH_B(tile) { const fe* __restrict__ srct = src + (tile_major ? (size_t)(tile) * (T * T) : (size_t)((tile) * T) * a.src_row_stride); NTT_EACH(NTT_FETCH_B1) }
     const uint32_t row_stride = (uint32_t)a.src_row_stride;
     const uint32_t tile0 = group * a.tiles_per_block;
     uint32_t lane = threadIdx.x;
@@ -561,16 +579,18 @@ static const NttRegInstance NTT_REG_INSTANCES[] = {NTT_REG_INSTANCE(6), NTT_REG_
 
 // the DISTAFF_NTT_* switches (ctx.h DST_SWITCHES) as the plan reads them, parsed once
 struct NttSwitches {
-    enum Force { NONE, OTHER, PRE, THREE, REG, LDS } force = NONE;   // DISTAFF_NTT (OTHER: set to something else -- no plan family forced, but not the default either)
+    enum Force { NONE, OTHER, PRE, PRE_A, THREE, REG, LDS } force = NONE;   // DISTAFF_NTT (OTHER: set to something else -- no plan family forced, but not the default either)
     unsigned shape_a = 0, shape_b = 0;     // DISTAFF_NTT_SHAPE
     int waves = 0;                         // DISTAFF_NTT_WAVES: 0 unset, else 4 / 8
     int dif = -1;                          // DISTAFF_NTT_DIF: -1 unset, else the first-pass mode it forces
     bool any_shape = false, coset_slow = false;   // DISTAFF_NTT_FIXED=0, DISTAFF_NTT_ORDER=0
+    bool row_major = false;                // DISTAFF_NTT=row: the default plan with the row-major layout where it would be tile-major (tests)
     uint32_t debug = 0;                    // DISTAFF_NTT_DEBUG
 };
 static NttSwitches ntt_switches(const dst_ctx* c) {
     NttSwitches s;
-    if (const char* e = c->sw("DISTAFF_NTT")) s.force = !strcmp(e, "pre") ? s.PRE : !strcmp(e, "3pass") ? s.THREE : !strcmp(e, "reg") ? s.REG : !strcmp(e, "lds") ? s.LDS : s.OTHER;
+    if (c->sw_is("DISTAFF_NTT", "row")) s.row_major = true;
+    else if (const char* e = c->sw("DISTAFF_NTT")) s.force = !strcmp(e, "pre") ? s.PRE : !strcmp(e, "pre_a") ? s.PRE_A : !strcmp(e, "3pass") ? s.THREE : !strcmp(e, "reg") ? s.REG : !strcmp(e, "lds") ? s.LDS : s.OTHER;
     if (const char* e = c->sw("DISTAFF_NTT_SHAPE")) if (sscanf(e, "%u,%u", &s.shape_a, &s.shape_b) != 2) s.shape_a = s.shape_b = 0;
     if (const char* e = c->sw("DISTAFF_NTT_WAVES")) s.waves = e[0] == '8' ? 8 : 4;
     if (const char* e = c->sw("DISTAFF_NTT_DIF")) s.dif = e[0] == '0' ? 1 : e[0] == '2' ? 2 : 0;
@@ -608,14 +628,23 @@ static uint32_t ntt_first_pass_mode(const NttSwitches& sw, size_t n1, size_t til
     return 0;
 }
 
+// The ONE place that decides the layout of the staging array and of the four-step tables (NttPlan::tile_major -> NttArgs::tile_major): tile-major for two-pass plans of
+// the LDS family whose tiles are four columns wide in both passes and whose second pass has no register pre-stage (n = 2^4 .. 2^21; a pre-stage
+// in the first pass alone, n = 2^21, is included).  Three-pass plans (16-column tiles: 256-byte segments as they are), the register-radix family,
+// tiles of one or two columns and n = 2^22 (measured slower, NttArgs) keep the row-major layout.
+static bool ntt_tile_major(const NttPlan& pl) {
+    return pl.count == 2 && !pl.pass[0].reg && !pl.first_lde.reg && !pl.pass[1].reg && pl.pass[0].log_tile == 2 && pl.first_lde.log_tile == 2 && pl.pass[1].log_tile == 2
+           && !pl.pass[1].pre;
+}
 // The plan, a pure function of the transform length and the switches.  n = n1 * n2 in two HBM passes, tiles bounded by 64 KiB of LDS; from n = 2^21
 // (measured cross-over) three passes n = n1 * nm * n3 with 16-column tiles (256-byte HBM segments) instead of 4096-point tiles that hold one or two
 // columns -- except n = 2^21, 2^22: still two passes, their 2048-point factors run as a register pre-stage + 1024-point LDS tiles (NttArgs::pre).
-// DISTAFF_NTT=pre forces the pre-stages onto smaller transforms (tests), DISTAFF_NTT=3pass the three-pass plan from 2^12 on.
+// DISTAFF_NTT=pre forces the pre-stages onto smaller transforms (tests; pre_a: onto the first pass only), DISTAFF_NTT=3pass the three-pass plan from 2^12 on.
 static NttPlan ntt_plan_derive(uint32_t log_n, const NttSwitches& sw) {
     NttPlan pl;
     const bool force_pre = sw.force == sw.PRE && log_n >= 10 && log_n <= 22;
-    const bool pre_plan = force_pre || ((log_n == 21 || log_n == 22) && sw.force == sw.NONE);
+    const bool force_pre_a = sw.force == sw.PRE_A && log_n >= 10 && log_n <= 21;      // a pre-stage in the first pass only, as n = 2^21 has by itself
+    const bool pre_plan = force_pre || force_pre_a || ((log_n == 21 || log_n == 22) && sw.force == sw.NONE);
     const bool three = !pre_plan && ((log_n >= 21 && sw.force != sw.REG && sw.force != sw.LDS) || (sw.force == sw.THREE && log_n >= 12));
     uint32_t pre_a = 0, pre_b = 0;
     if (three) {
@@ -627,7 +656,7 @@ static NttPlan ntt_plan_derive(uint32_t log_n, const NttSwitches& sw) {
         pl.log_n1 = a; pl.log_n2 = log_n - a; pl.log_n3 = log_n - a - b;
     }
     else { pl.log_n1 = (log_n + 1) / 2; pl.log_n2 = log_n / 2; }
-    if (pre_plan) { pre_a = (force_pre || pl.log_n1 > 10) ? 1u : 0u; pre_b = (force_pre || pl.log_n2 > 10) ? 1u : 0u; }
+    if (pre_plan) { pre_a = (force_pre || force_pre_a || pl.log_n1 > 10) ? 1u : 0u; pre_b = (force_pre || pl.log_n2 > 10) ? 1u : 0u; }
     // kernel family per pass (measured): the LDS radix-2 kernels win while a tile holds >= 2 columns in 64 KiB of LDS; the
     // register-radix kernels take over for 4096-point tiles.  DISTAFF_NTT=reg|lds forces one two-pass family (tests run both); a 4096-point
     // coset DIT (64 KiB tile + 128 KiB of twiddle pairs) does not fit LDS, so `lds` leaves those to the register family
@@ -652,6 +681,7 @@ static NttPlan ntt_plan_derive(uint32_t log_n, const NttSwitches& sw) {
     if (three) pl.pass[1] = pass(NTT_MIDDLE, pl.log_n2 - pl.log_n3, pl.log_n3, cap, 0, false, false);
     pl.pass[three ? 2 : 1] = three ? pass(NTT_LAST, pl.log_n3, pl.log_n1, cap, 0, false, false) : pass(NTT_LAST, pl.log_n2 - pre_b, pl.log_n1, cap, pre_b, reg_b, false);
     pl.count = three ? 3 : 2; pl.coset_slow = sw.coset_slow; pl.debug = sw.debug;
+    pl.tile_major = ntt_tile_major(pl) && !sw.row_major;
     return pl;
 }
 static int ntt_plan_set(dst_ctx* c) {                 // c->plan from the context's size and switches; every pass must have found its compiled instance
@@ -724,6 +754,7 @@ static void ntt_run_pass(dst_ctx* c, const NttPass& P, const NttIo& io, size_t c
     a.dst = io.dst; a.dst_col_stride = io.dst_col_stride; a.dst_coset_stride = io.dst_coset_stride;
     a.stage_tw = P.stage_tw[inverse]; a.tile = P.log_tile; a.pre = P.pre; a.pre_tw = P.pre_tw[inverse];
     a.log_n1 = p.log_n1; a.log_n2 = p.log_n2;
+    a.tile_major = p.tile_major ? 1u : 0u;
     size_t units = cosets;             // what the coset dimension of the block index runs over
     uint32_t tiles, batch_log = 0;     // tiles of an array; three-pass last pass: one batch of tile groups per middle frequency
     if (first) {
@@ -786,13 +817,16 @@ static void ntt_transform(dst_ctx* c, const NttIo& io, size_t cosets, size_t col
 
 // ---- four-step twiddle tables -------------------------------------------------------------------------------------------------------
 // out[coset][k1][m2] = w_N^(m2 * ((k1 << log_b) + j)) for a transform of 2^log_n points whose inner dimension has 2^log_n2 points;
-// a sub-transform of length n' = n / 2^s is expressed with log_b + s (its root is w_N^(B * 2^s))
+// a sub-transform of length n' = n / 2^s is expressed with log_b + s (its root is w_N^(B * 2^s)).  tile_major: the same values as
+// out[coset][m2 >> 2][k1][m2 & 3] (NttArgs::tile_major)
 __global__ void twiddle_table_kernel(tw4_t* out, const fe* tw_lo, const fe* tw_hi, uint32_t lo_bits, uint32_t log_n2, uint32_t log_n, uint32_t log_b,
-                                     uint32_t log_N, uint32_t j0, uint32_t coset_twiddle) {
+                                     uint32_t log_N, uint32_t j0, uint32_t coset_twiddle, uint32_t tile_major) {
     const size_t n = (size_t)1 << log_n;
     size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= n) return;
-    const uint64_t k1 = i >> log_n2, m2 = i & (((size_t)1 << log_n2) - 1);
+    const uint32_t log_n1 = log_n - log_n2;
+    const uint64_t k1 = tile_major ? (i >> 2) & (((size_t)1 << log_n1) - 1) : i >> log_n2;
+    const uint64_t m2 = tile_major ? ((i >> (log_n1 + 2)) << 2) + (i & 3) : i & (((size_t)1 << log_n2) - 1);
     const uint64_t jg = coset_twiddle ? j0 + blockIdx.y : 0;
     const uint64_t e = (m2 * ((k1 << log_b) + jg)) & (((uint64_t)1 << log_N) - 1);
 #if NTT_TW4_PAIRS
@@ -845,17 +879,18 @@ int k_ntt_init(dst_ctx* c) {
     if ((r = dev_alloc(c, &c->tw4_inv, c->n))) return r;
     pl.pass[0].tw4[0] = c->tw4_fwd; pl.pass[0].tw4[1] = c->tw4_inv;
     dim3 g((unsigned)((c->n + 255) / 256), (unsigned)c->Bc);
-    hipLaunchKernelGGL(twiddle_table_kernel, g, dim3(256), 0, c->stream, c->tw4_lde, c->tw_lo, c->tw_hi, c->tw_lo_bits, pl.log_n2, c->log_n, c->log_b, c->log_N, (uint32_t)c->j0, 1u);
+    const uint32_t tm = pl.tile_major ? 1u : 0u;
+    hipLaunchKernelGGL(twiddle_table_kernel, g, dim3(256), 0, c->stream, c->tw4_lde, c->tw_lo, c->tw_hi, c->tw_lo_bits, pl.log_n2, c->log_n, c->log_b, c->log_N, (uint32_t)c->j0, 1u, tm);
     g.y = 1;
-    hipLaunchKernelGGL(twiddle_table_kernel, g, dim3(256), 0, c->stream, c->tw4_fwd, c->tw_lo, c->tw_hi, c->tw_lo_bits, pl.log_n2, c->log_n, c->log_b, c->log_N, 0u, 0u);
-    hipLaunchKernelGGL(twiddle_table_kernel, g, dim3(256), 0, c->stream, c->tw4_inv, c->itw_lo, c->itw_hi, c->tw_lo_bits, pl.log_n2, c->log_n, c->log_b, c->log_N, 0u, 0u);
+    hipLaunchKernelGGL(twiddle_table_kernel, g, dim3(256), 0, c->stream, c->tw4_fwd, c->tw_lo, c->tw_hi, c->tw_lo_bits, pl.log_n2, c->log_n, c->log_b, c->log_N, 0u, 0u, tm);
+    hipLaunchKernelGGL(twiddle_table_kernel, g, dim3(256), 0, c->stream, c->tw4_inv, c->itw_lo, c->itw_hi, c->tw_lo_bits, pl.log_n2, c->log_n, c->log_b, c->log_N, 0u, 0u, tm);
     if (pl.count == 3) {  // middle pass of a three-pass plan: rows of n' = n2 points, w_{n'}^(k2*m3) = w_N^(m3 * (k2 << (log_b + log_n1)))
         if ((r = dev_alloc(c, &c->tw4_row_fwd, (size_t)1 << pl.log_n2))) return r;
         if ((r = dev_alloc(c, &c->tw4_row_inv, (size_t)1 << pl.log_n2))) return r;
         pl.pass[1].tw4[0] = c->tw4_row_fwd; pl.pass[1].tw4[1] = c->tw4_row_inv;
         dim3 gr((unsigned)((((size_t)1 << pl.log_n2) + 255) / 256), 1u);
-        hipLaunchKernelGGL(twiddle_table_kernel, gr, dim3(256), 0, c->stream, c->tw4_row_fwd, c->tw_lo, c->tw_hi, c->tw_lo_bits, pl.log_n3, pl.log_n2, c->log_b + pl.log_n1, c->log_N, 0u, 0u);
-        hipLaunchKernelGGL(twiddle_table_kernel, gr, dim3(256), 0, c->stream, c->tw4_row_inv, c->itw_lo, c->itw_hi, c->tw_lo_bits, pl.log_n3, pl.log_n2, c->log_b + pl.log_n1, c->log_N, 0u, 0u);
+        hipLaunchKernelGGL(twiddle_table_kernel, gr, dim3(256), 0, c->stream, c->tw4_row_fwd, c->tw_lo, c->tw_hi, c->tw_lo_bits, pl.log_n3, pl.log_n2, c->log_b + pl.log_n1, c->log_N, 0u, 0u, 0u);
+        hipLaunchKernelGGL(twiddle_table_kernel, gr, dim3(256), 0, c->stream, c->tw4_row_inv, c->itw_lo, c->itw_hi, c->tw_lo_bits, pl.log_n3, pl.log_n2, c->log_b + pl.log_n1, c->log_N, 0u, 0u, 0u);
     }
     for (int inv = 0; inv < 2; inv++) { pl.first_lde.stage_tw[inv] = pl.pass[0].stage_tw[inv]; pl.first_lde.pre_tw[inv] = pl.pass[0].pre_tw[inv]; }   // its four-step table is tw4_lde
     HIP_TRY(c, hipStreamSynchronize(c->stream));

@@ -1,0 +1,306 @@
+// The user-stack constraints as nested sums: the statement that the product instances of the constraint kernel evaluate (air_kernel.h,
+// section air_stack_nested).  What is here has no kernel arguments and no memory access -- two stack rows, the small flag tables and a
+// selection of operations in, one constraint value out -- so the suite's air_merge_test.cpp checks its three tables (st_has, st_desc,
+// st_term) against each other on the host.  The per-operation statement of the same constraints is air_stack_perop.h.
+#pragma once
+#include <hip/hip_runtime.h>
+#include <stdint.h>
+#include <type_traits>
+#include "fe.h"
+
+__device__ __forceinline__ fe bnot(const fe& v) { return fe_sub(fe_one(), v); }
+__device__ __forceinline__ fe is_bin(const fe& v) { return fe_sub(fe_sqr(v), v); }
+
+template <int I, int N, class F>
+__device__ __forceinline__ void static_for_air(F&& f) {
+    if constexpr (I < N) { f(std::integral_constant<int, I>{}); static_for_air<I + 1, N>(f); }
+}
+
+// ---- low-degree stack operations as nested sums -------------------------------------------------------------------------------
+// The flag of low-degree operation `op` is lo2[op & 3] * mid[(op >> 2) & 3] * top[op >> 4] (trace_state.rs:281-350), and every
+// stack constraint is sum_op flag(op) * term(op, slot) (constraints/stack/mod.rs:117-195).  Written as
+//     sum_c top[c] * ( sum_b mid[b] * ( sum_a lo2[a] * term(a + 4b + 16c, slot) ) )
+// the 32 flags are never formed and every level is a sum of products with one reduction (fe_acc): ~13k instructions per point
+// instead of ~21k for flag products + per-term multiply-adds.  st_term states, per operation and slot, exactly what the
+// per-operation statement (air_stack_perop.h) passes to agg(): slots 0..7 are the stack constraints, ST_AUX0 and ST_AUX1 the two
+// auxiliary constraints.
+struct StackRows { fe o[12], nw[8]; int sl; };            // o[8..11] and sl only matter to the deep instance (slice longer than 8)
+#define ST_AUX0 8
+#define ST_AUX1 9
+
+// stack slots 0..7 (the slice always has max(depth, 8) = 8 items for depth <= 8), ST_AUX0, ST_AUX1
+template <int OP, int I> constexpr bool st_has() {
+    constexpr bool slot = I < 8, aux0 = I == ST_AUX0, aux1 = I == ST_AUX1;
+    switch (OP) {
+        case 0x00: case 0x01: case 0x05: case 0x06: case 0x07: return slot || aux0;       // ASSERT, ASSERTEQ, CHOOSE, CHOOSE2, CSWAP2
+        case 0x02: case 0x0E: return slot || aux0;                                       // EQ, NOT
+        case 0x03: case 0x04: case 0x08: case 0x09: case 0x0C: case 0x0D: return slot;   // DROP, DROP4, ADD, MUL, INV, NEG
+        case 0x0A: case 0x0B: return slot || aux0 || aux1;                               // AND, OR
+        case 0x10: return I >= 1 && slot;                                                // READ
+        case 0x11: return I >= 2 && slot;                                                // READ2
+        case 0x12: case 0x13: case 0x14: case 0x15: return slot;                         // DUP, DUP2, DUP4, PAD2
+        case 0x18: return slot && I != 1;                                                // SWAP: both constraints in slot 0 (manipulation.rs:63-64)
+        case 0x19: case 0x1A: case 0x1B: case 0x1C: case 0x1D: return slot;              // SWAP2, SWAP4, ROLL4, ROLL8, BINACC
+        default: return false;
+    }
+}
+
+template <int OP, int I>
+__device__ __forceinline__ fe st_term(const StackRows& s) {
+    const fe* o = s.o; const fe* nw = s.nw;
+    constexpr int i = I < 8 ? I : 0;
+    // the shift helpers of constraints/stack/mod.rs on a slice of s.sl >= 8 items (8 unless the stack is deeper): a left shift by
+    // num zero-fills the last num slots
+    auto L = [&](int num) {
+        if (i + num < 8) return fe_sub(o[i + num < 8 ? i + num : 0], nw[i]);
+        return i + num < s.sl ? fe_sub(o[i + num < 12 ? i + num : 0], nw[i]) : nw[i];
+    };
+    auto R = [&](int num) { return fe_sub(o[i - num < 0 ? 0 : i - num], nw[i]); };   // right shift by num (callers: i >= num)
+    auto C = [&]() { return fe_sub(o[i], nw[i]); };                       // copy
+    auto sel = [&](const fe& c, const fe& x, const fe& y) { return fe_add(y, fe_mul(c, fe_sub(x, y))); };   // c*x + (1-c)*y with one multiplication
+    if constexpr (OP == 0x00) { if constexpr (I == ST_AUX0) return bnot(o[0]); else return L(1); }   // the ASSERT flag carries hd[0] (trace_state.rs:346): st_output puts it into the coefficient
+    else if constexpr (OP == 0x01) { if constexpr (I == ST_AUX0) return fe_sub(o[0], o[1]); else return L(2); }
+    else if constexpr (OP == 0x02) {
+        const fe diff = fe_sub(o[1], o[2]);
+        if constexpr (I == ST_AUX0) return fe_mul(nw[0], diff);
+        else if constexpr (I == 0) return fe_sub(nw[0], bnot(fe_mul(diff, o[0])));
+        else return L(2);
+    }
+    else if constexpr (OP == 0x03) return L(1);
+    else if constexpr (OP == 0x04) return L(4);
+    else if constexpr (OP == 0x05) {
+        if constexpr (I == ST_AUX0) return is_bin(o[2]);
+        else if constexpr (I == 0) return fe_sub(nw[0], sel(o[2], o[0], o[1]));
+        else return L(2);
+    }
+    else if constexpr (OP == 0x06) {
+        if constexpr (I == ST_AUX0) return is_bin(o[4]);
+        else if constexpr (I == 0) return fe_sub(nw[0], sel(o[4], o[0], o[2]));
+        else if constexpr (I == 1) return fe_sub(nw[1], sel(o[4], o[1], o[3]));
+        else return L(4);
+    }
+    else if constexpr (OP == 0x07) {
+        if constexpr (I == ST_AUX0) return is_bin(o[4]);
+        else if constexpr (I == 0) return fe_sub(nw[0], sel(o[4], o[2], o[0]));
+        else if constexpr (I == 1) return fe_sub(nw[1], sel(o[4], o[3], o[1]));
+        else if constexpr (I == 2) return fe_sub(nw[2], sel(o[4], o[0], o[2]));
+        else if constexpr (I == 3) return fe_sub(nw[3], sel(o[4], o[1], o[3]));
+        else return L(2);
+    }
+    else if constexpr (OP == 0x08) { if constexpr (I == 0) return fe_sub(nw[0], fe_add(o[0], o[1])); else return L(1); }
+    else if constexpr (OP == 0x09) { if constexpr (I == 0) return fe_sub(nw[0], fe_mul(o[0], o[1])); else return L(1); }
+    else if constexpr (OP == 0x0A) {
+        if constexpr (I == ST_AUX0) return is_bin(o[0]);
+        else if constexpr (I == ST_AUX1) return is_bin(o[1]);
+        else if constexpr (I == 0) return fe_sub(nw[0], fe_mul(o[0], o[1]));
+        else return L(1);
+    }
+    else if constexpr (OP == 0x0B) {
+        if constexpr (I == ST_AUX0) return is_bin(o[0]);
+        else if constexpr (I == ST_AUX1) return is_bin(o[1]);
+        else if constexpr (I == 0) return fe_sub(nw[0], fe_sub(fe_add(o[0], o[1]), fe_mul(o[0], o[1])));     // 1 - (1-x)(1-y) = x + y - xy (shares xy with MUL / AND)
+        else return L(1);
+    }
+    else if constexpr (OP == 0x0C) { if constexpr (I == 0) return fe_sub(fe_one(), fe_mul(nw[0], o[0])); else return C(); }
+    else if constexpr (OP == 0x0D) { if constexpr (I == 0) return fe_add(nw[0], o[0]); else return C(); }
+    else if constexpr (OP == 0x0E) {
+        if constexpr (I == ST_AUX0) return is_bin(o[0]);
+        else if constexpr (I == 0) return fe_sub(nw[0], bnot(o[0]));
+        else return C();
+    }
+    else if constexpr (OP == 0x10) return R(1);
+    else if constexpr (OP == 0x11) return R(2);
+    else if constexpr (OP == 0x12) { if constexpr (I == 0) return fe_sub(nw[0], o[0]); else return R(1); }
+    else if constexpr (OP == 0x13) { if constexpr (I < 2) return fe_sub(nw[i], o[i]); else return R(2); }
+    else if constexpr (OP == 0x14) { if constexpr (I < 4) return fe_sub(nw[i], o[i]); else return R(4); }
+    else if constexpr (OP == 0x15) { if constexpr (I < 2) return nw[i]; else return R(2); }
+    else if constexpr (OP == 0x18) { if constexpr (I == 0) return fe_add(fe_sub(nw[0], o[1]), fe_sub(nw[1], o[0])); else return C(); }
+    else if constexpr (OP == 0x19) { if constexpr (I < 4) return fe_sub(nw[i], o[i ^ 2]); else return C(); }
+    else if constexpr (OP == 0x1A) return fe_sub(nw[i], o[i ^ 4]);
+    else if constexpr (OP == 0x1B) { if constexpr (I < 4) return fe_sub(nw[i], o[(i + 3) & 3]); else return C(); }
+    else if constexpr (OP == 0x1C) return fe_sub(nw[i], o[(i + 7) & 7]);
+    else if constexpr (OP == 0x1D) {
+        if constexpr (I == 0) return is_bin(nw[0]);
+        else if constexpr (I == 1) return nw[1];
+        else if constexpr (I == 2) return fe_sub(nw[2], fe_double(o[2]));
+        else if constexpr (I == 3) return fe_sub(nw[3], fe_add(o[3], fe_mul(nw[0], o[2])));
+        else return C();
+    }
+    else return fe_zero();
+}
+
+// ---- which operations a launch evaluates ---------------------------------------------------------------------------------------------
+// The stack constraints are linear in the operation flags, so a launch may evaluate any subset of the operations for all slots and hand
+// the partial values on through memory (AirArgs::ev); the launch that holds the last subset emits the constraints.  Cutting by operation
+// group rather than by slot keeps what a launch has to derive first small: the low-degree groups of one `c` need lo2, mid and one top
+// entry, the high-degree / flow operations the four hd flags -- and no straight-line kernel grows past the 64 KiB instruction cache of a
+// CU pair (tools/codeobj_info.py, gated by build()).
+//   bits 0..3: low-degree operations 4b .. 4b+3 (c = 0), bits 4..7: 16 + 4b .. (c = 1), then PUSH, CMP, RESCR, BEGIN / NOOP ("keep"),
+//   and the slots >= 8 of the deep instance.
+#define AG_LOW(c, b) (1u << ((c) * 4 + (b)))
+#define AG_LOW0 0x00Fu
+#define AG_LOW1 0x0F0u
+#define AG_PUSH 0x100u
+#define AG_CMP 0x200u
+#define AG_RESCR 0x400u
+#define AG_KEEP 0x800u
+#define AG_HIGH 0xF00u
+#define AG_DEEP 0x1000u
+#define AG_STACK_ALL 0x1FFFu
+
+// What term(op, slot) is, for the terms that are plain differences of stack items: kind 1: o[j] - nw[I], 2: nw[I] - o[j], 3: nw[I],
+// 4: -nw[I], 5: anything else (st_term computes it), 0: the operation does not constrain the slot.  SDK = compile-time stack depth (0:
+// known at run time only): items o[j], j >= SDK, are zeros then (trace_state.rs:58-60 pads the slice), which turns differences into +-nw[I]
+// and removes the selector of CHOOSE2 / CSWAP2 (item 4).  DEEP: the slice may be longer than 8, left shifts past item 7 stay with st_term.
+struct StDesc { int kind, j; };
+template <int SDK, bool DEEP>
+constexpr StDesc st_desc(int op, int I) {
+    const bool o4_zero = SDK != 0 && SDK <= 4;
+    if (I >= 8) {                                                      // auxiliary constraints: computed; j >= 100 names values that several operations share
+        if ((op == 0x0A || op == 0x0B)) return StDesc{5, I == ST_AUX0 ? 100 : 101};         // is_bin(o[0]) / is_bin(o[1])
+        if ((op == 0x06 || op == 0x07) && o4_zero) return StDesc{0, 0};                     // is_bin(o[4]) of a zero
+        return StDesc{5, -1};
+    }
+    const int i = I;
+    auto diff = [&](int j) { return (SDK != 0 && j >= SDK) ? StDesc{4, 0} : StDesc{1, j}; };
+    auto rdiff = [&](int j) { return (SDK != 0 && j >= SDK) ? StDesc{3, 0} : StDesc{2, j}; };
+    auto L = [&](int num) { return i + num < 8 ? diff(i + num) : (DEEP ? StDesc{5, -1} : StDesc{3, 0}); };
+    auto R = [&](int num) { return diff(i - num < 0 ? 0 : i - num); };
+    switch (op) {
+        case 0x00: return L(1);
+        case 0x01: return L(2);
+        case 0x02: return i == 0 ? StDesc{5, -1} : L(2);
+        case 0x03: return L(1);
+        case 0x04: return L(4);
+        case 0x05: return i == 0 ? StDesc{5, -1} : L(2);
+        case 0x06: return i < 2 ? (o4_zero ? rdiff(i + 2) : StDesc{5, -1}) : L(4);          // selector o[4] = 0: the second operand
+        case 0x07: return i < 4 ? (o4_zero ? rdiff(i) : StDesc{5, -1}) : L(2);
+        case 0x08: case 0x0B: return i == 0 ? StDesc{5, -1} : L(1);
+        case 0x09: case 0x0A: return i == 0 ? StDesc{5, 102} : L(1);                         // MUL and AND: nw[0] - o[0] * o[1]
+        case 0x0C: case 0x0D: case 0x0E: return i == 0 ? StDesc{5, -1} : diff(i);
+        case 0x10: return R(1);
+        case 0x11: return R(2);
+        case 0x12: return i == 0 ? rdiff(0) : R(1);
+        case 0x13: return i < 2 ? rdiff(i) : R(2);
+        case 0x14: return i < 4 ? rdiff(i) : R(4);
+        case 0x15: return i < 2 ? StDesc{3, 0} : R(2);
+        case 0x18: return i == 0 ? StDesc{5, -1} : diff(i);
+        case 0x19: return i < 4 ? rdiff(i ^ 2) : diff(i);
+        case 0x1A: return rdiff(i ^ 4);
+        case 0x1B: return i < 4 ? rdiff((i + 3) & 3) : diff(i);
+        case 0x1C: return rdiff((i + 7) & 7);
+        case 0x1D: return i == 1 ? StDesc{3, 0} : (i < 4 ? StDesc{5, -1} : diff(i));
+        default: return StDesc{0, 0};
+    }
+}
+// operations of one group (4 consecutive opcodes) whose terms for slot I coincide up to sign share ONE product: entry e of the merge
+// holds the basis term (kind / j of its first member) and the sign of every member's coefficient relative to it
+struct StMerge { int n; int kind[4], j[4], lead[4]; int sgn[4][4]; };
+template <int BASE, int I, int SDK, bool DEEP>
+constexpr StMerge st_merge() {
+    StMerge m{};
+    for (int a = 0; a < 4; a++) {
+        const StDesc d = st_desc<SDK, DEEP>(BASE + a, I);
+        // has the operation a term here at all?  (st_has is the authority: st_desc only classifies)
+        bool has = false;
+        switch (a) { case 0: has = st_has<BASE, I>(); break; case 1: has = st_has<BASE + 1, I>(); break; case 2: has = st_has<BASE + 2, I>(); break; default: has = st_has<BASE + 3, I>(); }
+        if (!has || d.kind == 0) continue;
+        const int cls = d.kind == 5 ? 5 : (d.kind <= 2 ? 1 : 3);           // 1: differences with o[j], 3: +-nw[I], 5: computed
+        const int sign = (d.kind == 2 || d.kind == 4) ? -1 : 1;
+        int e = -1;
+        for (int k = 0; k < m.n; k++) {
+            const int kc = m.kind[k] == 5 ? 5 : (m.kind[k] <= 2 ? 1 : 3);
+            if (kc != cls) continue;
+            if (cls == 3 || (cls == 1 && m.j[k] == d.j) || (cls == 5 && d.j >= 100 && m.j[k] == d.j)) e = k;
+        }
+        if (e < 0) { e = m.n++; m.kind[e] = d.kind; m.j[e] = d.j; m.lead[e] = a; m.sgn[e][a] = 1; }
+        else { const int lead_sign = (m.kind[e] == 2 || m.kind[e] == 4) ? -1 : 1; m.sgn[e][a] = sign * lead_sign; }
+    }
+    return m;
+}
+
+// The operations selected by the high-degree bits and the flow flags join the outermost sum of a slot (one more product each,
+// no separate multiplication and modular addition): PUSH (input.rs:6), CMP (comparison.rs:64-105), RESCR (hash.rs:9-35; its six
+// differences are computed once by the caller), BEGIN / NOOP (stack untouched).
+struct StackHigh { fe push, cmp, rescr, keep; fe resc[6]; };       // the four flags and the RESCR differences
+
+template <int I, uint32_t GROUPS>
+__device__ __forceinline__ void st_high_degree(fe_acc& outer, const StackRows& s, const StackHigh& h) {
+    if constexpr (I < 8) {
+        const fe* o = s.o; const fe* nw = s.nw;
+        if constexpr (I >= 1 && (GROUPS & AG_PUSH) != 0) fe_acc_mac(outer, h.push, fe_sub(o[I - 1 < 0 ? 0 : I - 1], nw[I]));
+        if constexpr ((GROUPS & AG_CMP) != 0) {
+            const fe x_bit = nw[1], y_bit = nw[2], not_set = nw[3];
+            fe v;
+            if constexpr (I == 0) v = is_bin(x_bit);
+            else if constexpr (I == 1) v = is_bin(y_bit);
+            else if constexpr (I == 2) v = fe_sub(nw[4], fe_add(o[4], fe_mul(fe_mul(x_bit, bnot(y_bit)), not_set)));
+            else if constexpr (I == 3) v = fe_sub(nw[5], fe_add(o[5], fe_mul(fe_mul(y_bit, bnot(x_bit)), not_set)));
+            else if constexpr (I == 4) v = fe_sub(nw[6], fe_add(o[6], fe_mul(y_bit, o[0])));
+            else if constexpr (I == 5) v = fe_sub(nw[7], fe_add(o[7], fe_mul(x_bit, o[0])));
+            else if constexpr (I == 6) v = fe_sub(not_set, fe_mul(bnot(o[5]), bnot(o[4])));
+            else v = fe_sub(fe_double(nw[0]), o[0]);
+            fe_acc_mac(outer, h.cmp, v);
+        }
+        if constexpr ((GROUPS & (AG_RESCR | AG_KEEP)) != 0) {
+            const fe keep = fe_sub(o[I < 8 ? I : 0], nw[I < 8 ? I : 0]);
+            if constexpr ((GROUPS & AG_RESCR) != 0) { if constexpr (I < 6) fe_acc_mac(outer, h.rescr, h.resc[I < 6 ? I : 0]); else fe_acc_mac(outer, h.rescr, keep); }
+            if constexpr ((GROUPS & AG_KEEP) != 0) fe_acc_mac(outer, h.keep, keep);
+        }
+    }
+}
+
+// does the launch's selection contribute anything to output I?  (the auxiliary constraints only hear from low-degree operations of c = 0)
+template <int I, uint32_t GROUPS> constexpr bool st_touches() {
+    if (I >= 8) return (GROUPS & AG_LOW0) != 0;
+    return (GROUPS & (AG_LOW0 | AG_LOW1 | AG_HIGH)) != 0;
+}
+
+// output I (slot 0..7, ST_AUX0, ST_AUX1) of the selected operations:
+//     sum_c top[c] * ( sum_b mid[b] * ( sum_e coefficient_e * basis term_e ) )  +  high-degree / flow flags * their terms
+// every level one sum of products with a single reduction (fe_acc); coefficient_e = +-lo2[a] summed over the merged members
+// (lo0h = lo2[0] * hd[0] stands for lo2[0] in group 0: the ASSERT flag carries hd[0], trace_state.rs:346)
+template <int I, uint32_t GROUPS, int SDK, bool DEEP>
+__device__ __forceinline__ fe st_output(const StackRows& s, const fe* lo2, const fe& lo0h, const fe* mid, const fe* top, const StackHigh& h) {
+    fe_acc outer; fe_acc_zero(outer);
+    static_for_air<0, 2>([&](auto c_) {
+        constexpr int c = decltype(c_)::value;
+        if constexpr (((GROUPS >> (4 * c)) & 0xFu) != 0) {
+            fe_acc middle; fe_acc_zero(middle);
+            static_for_air<0, 4>([&](auto b_) {
+                constexpr int b = decltype(b_)::value;
+                constexpr int base = 4 * b + 16 * c;
+                if constexpr ((GROUPS & AG_LOW(c, b)) != 0) {
+                    static constexpr StMerge M = st_merge<base, I, SDK, DEEP>();
+                    if constexpr (M.n > 0) {
+                        fe_acc inner; fe_acc_zero(inner);
+                        static_for_air<0, M.n>([&](auto e_) {
+                            constexpr int e = decltype(e_)::value;
+                            // coefficient: the leader's, plus / minus the other members'
+                            fe cf = (base == 0 && M.lead[e] == 0) ? lo0h : lo2[M.lead[e]];
+                            static_for_air<0, 4>([&](auto a_) {
+                                constexpr int a = decltype(a_)::value;
+                                if constexpr (a != M.lead[e] && M.sgn[e][a] != 0) {
+                                    const fe other = (base == 0 && a == 0) ? lo0h : lo2[a];
+                                    cf = M.sgn[e][a] > 0 ? fe_add(cf, other) : fe_sub(cf, other);
+                                }
+                            });
+                            constexpr int ii = I < 8 ? I : 0;
+                            fe term;
+                            if constexpr (M.kind[e] == 1) term = fe_sub(s.o[M.j[e]], s.nw[ii]);
+                            else if constexpr (M.kind[e] == 2) term = fe_sub(s.nw[ii], s.o[M.j[e]]);
+                            else if constexpr (M.kind[e] == 3) term = s.nw[ii];
+                            else if constexpr (M.kind[e] == 4) term = fe_neg(s.nw[ii]);
+                            else term = st_term<base + M.lead[e], I>(s);
+                            fe_acc_mac(inner, cf, term);
+                        });
+                        fe_acc_mac(middle, mid[b], fe_acc_reduce(inner));
+                    }
+                }
+            });
+            fe_acc_mac(outer, top[c], fe_acc_reduce(middle));
+        }
+    });
+    if constexpr ((GROUPS & AG_HIGH) != 0) st_high_degree<I, GROUPS>(outer, s, h);
+    return fe_acc_reduce(outer);
+}

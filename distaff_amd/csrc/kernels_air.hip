@@ -1,4 +1,4 @@
-// Launcher of the AIR constraint kernel (air_kernel.h) and its fully generic instance.
+// Launcher of the AIR constraint kernel (air_kernel.h) and, in the test build, its per-operation instance (air_stack_perop.h).
 #include "air_kernel.h"
 #include "rescue_constants.h"
 
@@ -6,16 +6,27 @@
 void air_launch_generic(dst_ctx* c, const AirArgs& a, uint32_t Q) {
     // any shape the VM can produce (up to 16 context, 8 loop and 32 stack registers, known at run time), per-operation formulation,
     // cut into the same section launches as the specialised instances
-    launch_air<16, 8, 0, 32, 2, 0, AF_FIRST>(c, a, Q);     // op bits
-    if (dst_internal_boundary_by_evaluation(c)) launch_air<16, 8, 0, 32, 1, 0, 0>(c, a, Q);    // boundary (normally in coefficient form, api.hip)
-    launch_air<16, 8, 0, 32, 132, 0, 0>(c, a, Q);          // sponge, loop image, context / loop stacks
-    launch_air<16, 8, 0, 32, 8, 0, 0>(c, a, Q);            // stack: low-degree ops that move items
-    launch_air<16, 8, 0, 32, 32, 0, 0>(c, a, Q);           // stack: low-degree arithmetic / selection ops
-    launch_air<16, 8, 0, 32, 16, 0, 0>(c, a, Q);           // stack: PUSH, CMP, BEGIN / NOOP
-    launch_air<16, 8, 0, 32, 64, 0, AF_LAST>(c, a, Q);     // stack: RESCR + combination
+    launch_air<16, 8, 0, 32, AS_OP_BITS, 0, AF_FIRST>(c, a, Q);            // op bits
+    launch_air_boundary<16, 8, 0, 32>(c, a, Q);                            // boundary combinations by evaluation
+    launch_air<16, 8, 0, 32, AS_SPONGE | AS_FLOW, 0, 0>(c, a, Q);          // sponge, loop image, context / loop stacks
+    launch_air<16, 8, 0, 32, AS_STACK_MOVE, 0, 0>(c, a, Q);                // stack: low-degree ops that move items
+    launch_air<16, 8, 0, 32, AS_STACK_ARITH, 0, 0>(c, a, Q);               // stack: low-degree arithmetic / selection ops
+    launch_air<16, 8, 0, 32, AS_STACK_HIGH, 0, 0>(c, a, Q);                // stack: PUSH, CMP, BEGIN / NOOP
+    launch_air<16, 8, 0, 32, AS_STACK_RESCR, 0, AF_LAST>(c, a, Q);         // stack: RESCR + combination
 }
 #endif
 
+// Which instance set evaluates a trace of the shape (cl, ll, sd): the most special one that fits, unless DISTAFF_AIR=small|deep|generic
+// forces a more general one (tests run the same trace through all of them).  The per-operation set exists in the test build only: the
+// product library answers `generic` with the deep set.
+enum AirInstanceSet { AIR_SET_SD4, AIR_SET_SMALL, AIR_SET_DEEP, AIR_SET_GENERIC };
+static AirInstanceSet air_instance_set(uint32_t cl, uint32_t ll, uint32_t sd, const char* force) {
+    const bool small_shape = cl <= 2 && ll <= 1 && sd <= 8;
+    const auto forced = [&](const char* name) { return force && !strcmp(force, name); };
+    if (forced("generic")) return DST_TEST_HOOKS ? AIR_SET_GENERIC : AIR_SET_DEEP;
+    if (forced("deep") || !small_shape) return AIR_SET_DEEP;
+    return sd == 4 && !forced("small") ? AIR_SET_SD4 : AIR_SET_SMALL;
+}
 
 int k_constraint_check(dst_ctx* c, int64_t* bad_step) {
     const unsigned long long res = c->air_flag_host;
@@ -56,16 +67,15 @@ int k_eval_constraints(dst_ctx* c, const fe* coeffs_dev, const fe* tc_dev, int64
     HIP_TRY(c, hipMemsetAsync(c->d_u64, 0xFF, 8, c->stream));          // ~0 = no failing step yet
     const uint32_t cd = c->prm.ctx_depth, lp = c->prm.loop_depth, sd = (uint32_t)c->stack_depth;
     a.cl = cd > 1 ? cd : 1; a.ll = lp > 1 ? lp : 1; a.sl = sd > 8 ? sd : 8;
-    // DISTAFF_AIR=generic|deep|small forces a more general instance than the shape needs (tests run the same trace through all of them)
-    const char* force = c->sw("DISTAFF_AIR");
-    const bool want_generic = force && !strcmp(force, "generic"), want_small = force && !strcmp(force, "small"), want_deep = force && !strcmp(force, "deep");
-    const bool general = want_generic || want_deep;
-    if (a.cl <= 2 && a.ll <= 1 && sd == 4 && !general && !want_small) air_launch_sd4(c, a, Q);
-    else if (a.cl <= 2 && a.ll <= 1 && sd <= 8 && !general) air_launch_small(c, a, Q);
+    switch (air_instance_set(a.cl, a.ll, sd, c->sw("DISTAFF_AIR"))) {
+        case AIR_SET_SD4: air_launch_sd4(c, a, Q); break;
+        case AIR_SET_SMALL: air_launch_small(c, a, Q); break;
+        case AIR_SET_GENERIC:                   // the product library has no per-operation set: the deep set answers
 #if DST_TEST_HOOKS
-    else if (want_generic) air_launch_generic(c, a, Q);
+            air_launch_generic(c, a, Q); break;
 #endif
-    else air_launch_deep(c, a, Q);
+        case AIR_SET_DEEP: air_launch_deep(c, a, Q); break;
+    }
     // the failing step, if any (evaluator.rs:152-158 panics there): read back into page-locked memory; with defer_check the host does not
     // wait here -- the caller looks at it (k_constraint_check) at its next synchronisation, after work that does not depend on it
     unsigned long long* flag = c->h_stage ? reinterpret_cast<unsigned long long*>(c->h_stage + HS_AIR_FLAG) : &c->air_flag_host;

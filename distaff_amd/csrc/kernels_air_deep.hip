@@ -1,15 +1,14 @@
 // AIR kernel instances for any trace shape the VM can produce (up to 16 context, 8 loop and 32 stack registers, known at run time)
-// in the nested-sum formulation: the first eight stack slots as in the depth <= 8 instances (from twelve register-resident items of
-// the current row), deeper slots from memory as flag sums times shifted differences (air_kernel.h, AG_DEEP).  The per-operation
-// formulation of kernels_air.hip stays as an independent statement of the same constraints (DISTAFF_AIR=generic).
+// in the deep formulation (air_kernel.h air_stack): the first eight stack slots as nested sums like the depth <= 8 instances
+// (air_stack_nested.h, from twelve register-resident items of the current row), deeper slots from memory as flag sums times shifted
+// differences (air_kernel.h air_stack_deep_slots, AG_DEEP).  The per-operation formulation (air_stack_perop.h, launched by
+// kernels_air.hip) stays as an independent statement of the same constraints (DISTAFF_AIR=generic).
 #include "air_kernel.h"
 void air_launch_deep(dst_ctx* c, const AirArgs& a, uint32_t Q) {
-#if DST_TEST_HOOKS
-    if (dst_internal_boundary_by_evaluation(c)) launch_air<16, 8, 0, 12, 1, 0, 0>(c, a, Q);          // boundary constraints
-#endif
-    launch_air<16, 8, 0, 12, 2, 0, AF_FIRST>(c, a, Q);                                              // op bits (starts the partial sums)
-    launch_air<16, 8, 0, 12, 4, 0, 0>(c, a, Q);                                                     // sponge
-    launch_air<16, 8, 0, 12, 128, 0, 0>(c, a, Q);                                                   // loop image, context / loop stacks
+    launch_air_boundary<16, 8, 0, 12>(c, a, Q);                                                     // boundary combinations by evaluation (test build only)
+    launch_air<16, 8, 0, 12, AS_OP_BITS, 0, AF_FIRST>(c, a, Q);                                     // op bits (starts the partial sums)
+    launch_air<16, 8, 0, 12, AS_SPONGE, 0, 0>(c, a, Q);                                             // sponge
+    launch_air<16, 8, 0, 12, AS_FLOW, 0, 0>(c, a, Q);                                               // loop image, context / loop stacks
     launch_air<16, 8, 0, 12, 0, AG_DEEP, 0>(c, a, Q);                                               // stack slots 8..: flag sums x shifted differences
     launch_air<16, 8, 0, 12, 0, AG_RESCR, AF_EV_OUT>(c, a, Q);                                      // stack slots 0..7: RESCR
     launch_air<16, 8, 0, 12, 0, AG_PUSH | AG_CMP | AG_KEEP, AF_EV_IN | AF_EV_OUT>(c, a, Q);         // PUSH, CMP, BEGIN / NOOP

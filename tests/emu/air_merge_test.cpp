@@ -1,12 +1,12 @@
 // TEST INFRASTRUCTURE (host build against the stand-in HIP header of this directory): the merged formulation of the low-degree stack
-// operations (air_kernel.h: st_desc / st_merge / st_output -- operations of a group whose terms for a slot coincide up to sign share one
+// operations (air_stack_nested.h: st_desc / st_merge / st_output -- operations of a group whose terms for a slot coincide up to sign share one
 // product, items above the compile-time stack depth are zeros) against the plain sum  sum_op flag(op) * st_term(op, slot)  of the
 // per-operation statement it was derived from, on random rows and random (not one-hot) flag factors, for every slot and auxiliary
 // constraint, every compile-time stack depth and the run-time-depth instances.  The proof-level tests cannot see a wrong table entry of an
 // operation whose flag is zero in the tested programs; this one can.
 #include <stdio.h>
 #include <stdlib.h>
-#include "../../distaff_amd/csrc/air_kernel.h"
+#include "../../distaff_amd/csrc/air_stack_nested.h"
 
 static uint64_t rs = 0x9E3779B97F4A7C15ull;
 static uint64_t rnd() { rs ^= rs << 13; rs ^= rs >> 7; rs ^= rs << 17; return rs; }
@@ -35,7 +35,7 @@ static void run(int sl, const char* what) {
         StackRows s{};
         for (int j = 0; j < 12; j++) s.o[j] = rfe();
         for (int j = 0; j < 8; j++) s.nw[j] = rfe();
-        s.hd0 = rfe(); s.sl = sl;
+        s.sl = sl;
         if (it % 5 == 0) { s.o[0] = fe_make(it & 1, 0, 0, 0); s.o[1] = fe_make((it >> 1) & 1, 0, 0, 0); s.o[2] = s.o[4] = fe_make((it >> 2) & 1, 0, 0, 0); }   // binary operands now and then
         if (SDK != 0) for (int j = SDK; j < 12; j++) s.o[j] = fe_zero();        // items above the stack depth are zeros (trace_state.rs:58-60 pads the slice)
         if (!DEEP || sl <= 8) for (int j = 8; j < 12; j++) s.o[j] = fe_zero();

@@ -76,6 +76,8 @@ SELECTION = WHOLE_DOMAIN + [
     "test_trace_from_pinned_host_memory[w17]",
     "test_synthetic_division_by_power_tables",
 ] + ["test_polynomial_layer_launches[%d-%s]" % (log_n, mode) for log_n in (7, 10, 12) for mode in ("default", "steps", "tables")] + [
+    "test_constraint_kernel_launches[%s-%s]" % (case, boundary) for case in ("fibonacci", "fibonacci-small", "fibonacci-deep", "fibonacci-generic", "depth8", "depth25", "depth25-generic")
+    for boundary in ("", "eval")] + [
     "test_trace_in_its_own_buffer",
     "test_small_fri_layers_in_one_launch_equal_the_per_layer_path",
     "test_prove_sharded_with_collectives_on_their_own_stream[2]",

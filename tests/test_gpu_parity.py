@@ -156,6 +156,48 @@ def test_polynomial_layer_launches(monkeypatch, log_n, mode):
     assert poly_layer_launches(D, log_n, mode) == want
 
 
+# case -> (trace family of test_air_arbitrary_rows._valid_trace_of_256_rows, outputs, DISTAFF_AIR)
+AIR_LAUNCH_CASES = {"fibonacci": ("sd4", 1, ""), "fibonacci-small": ("sd4", 1, "small"), "fibonacci-deep": ("sd4", 1, "deep"), "fibonacci-generic": ("sd4", 1, "generic"),
+                    "depth8": ("small", 2, ""), "depth25": ("deep", 4, ""), "depth25-generic": ("deep", 4, "generic")}
+
+
+def air_kernel_launches(D, O, family, num_outputs):
+    """{kernel: [launches, profiling bytes]} of the air_kernel<...> instances in one proof of the family's valid 256-row trace"""
+    from test_air_arbitrary_rows import _valid_trace_of_256_rows
+    t = _valid_trace_of_256_rows(O, family)
+    outputs = O.Prover.from_trace(t, num_outputs).outputs
+    ctx = _ctx(D, t, grinding=8)
+    ctx.upload(t.columns)
+    ctx.set_profiling(1)
+    ctx.prove(t.public_inputs, outputs)
+    stats = ctx.kernel_stats()
+    ctx.close()
+    return {name: [st["launches"], st["bytes"]] for name, st in stats.items() if name.startswith("air_kernel<")}
+
+
+@pytest.mark.parametrize("boundary", ["", "eval"])
+@pytest.mark.parametrize("case", list(AIR_LAUNCH_CASES))
+def test_constraint_kernel_launches(oracle, monkeypatch, case, boundary):
+    """The launches of the constraint evaluation do not move: which air_kernel<...> instances a proof of 256 rows launches, how often and
+    over how many profiling bytes, against tests/golden/air_launches.json -- the Fibonacci trace by shape (depth-4 set) and forced through
+    the small, deep and per-operation sets, the depth-8 program (small set), the depth-25 program with three context registers (deep set)
+    and forced through the per-operation set; with the boundary combinations in coefficient form (no boundary launch) and by evaluation
+    (one more launch).  The evaluations themselves are compared by the other tests; an instance set chosen differently, a launch cut
+    differently or other profiling bytes would leave them right.  An instance that the record does not hold must not be launched."""
+    import json
+    import os
+    import distaff_amd as D
+    family, num_outputs, instance = AIR_LAUNCH_CASES[case]
+    for k, v in (("DISTAFF_AIR", instance), ("DISTAFF_BOUNDARY", boundary)):
+        if v:
+            monkeypatch.setenv(k, v)                  # the library reads its switches when a context is created
+        else:
+            monkeypatch.delenv(k, raising=False)
+    golden = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "air_launches.json")
+    want = json.load(open(golden))["%s-%s" % (case, boundary or "default")]
+    assert air_kernel_launches(D, oracle, family, num_outputs) == want
+
+
 @pytest.mark.parametrize("instance", ["", "small", "deep", "generic"])
 def test_boundary_constraints_by_evaluation(oracle, monkeypatch, instance):
     """The evaluate-and-interpolate route of the two boundary combinations (the reference's own, constraint_table.rs:54-62): its

@@ -20,8 +20,8 @@ def demangle(name):
         return name
 
 
-def count_file(path):
-    """-> {demangled kernel name: {"valu": n, "mad64": n, "s_nop": n}} for every kernel of a gfx950 assembly file"""
+def parse_file(path):
+    """-> {mangled kernel name: Counter of opcodes} for every kernel of a gfx950 assembly file"""
     kernels, cur = {}, None
     for line in open(path):
         m = re.match(r"^(_Z\w+):\s*(;.*)?$", line)
@@ -36,11 +36,13 @@ def count_file(path):
         m = re.match(r"^\t([a-z_0-9]+)", line)
         if m and not m.group(1).startswith("."):
             cur[m.group(1)] += 1
-    out = {}
-    for name, ops in kernels.items():
-        if ops:
-            out[demangle(name)] = {"valu": sum(v for k, v in ops.items() if k.startswith("v_")), "mad64": ops.get("v_mad_u64_u32", 0), "s_nop": ops.get("s_nop", 0)}
-    return out
+    return {name: ops for name, ops in kernels.items() if ops}
+
+
+def count_file(path):
+    """-> {demangled kernel name: {"valu": n, "mad64": n, "s_nop": n}} for every kernel of a gfx950 assembly file"""
+    return {demangle(name): {"valu": sum(v for k, v in ops.items() if k.startswith("v_")), "mad64": ops.get("v_mad_u64_u32", 0), "s_nop": ops.get("s_nop", 0)}
+            for name, ops in parse_file(path).items()}
 
 
 def air_key(demangled):
@@ -86,23 +88,7 @@ def main():
         return
     path = sys.argv[1]
     top = int(sys.argv[sys.argv.index("--top") + 1]) if "--top" in sys.argv else 10
-    kernels, cur = {}, None
-    for line in open(path):
-        m = re.match(r"^(_Z\w+):\s*(;.*)?$", line)
-        if m:
-            cur = kernels.setdefault(m.group(1), collections.Counter())
-            continue
-        if line.startswith("\t.end_amdhsa_kernel") or line.startswith(".Lfunc_end"):
-            cur = None
-            continue
-        if cur is None:
-            continue
-        m = re.match(r"^\t([a-z_0-9]+)", line)
-        if m and not m.group(1).startswith("."):
-            cur[m.group(1)] += 1
-    for name, ops in kernels.items():
-        if not ops:
-            continue
+    for name, ops in parse_file(path).items():
         valu = sum(v for k, v in ops.items() if k.startswith("v_"))
         salu = sum(v for k, v in ops.items() if k.startswith("s_") and not k.startswith(("s_nop", "s_waitcnt", "s_load", "s_buffer")))
         nops = ops.get("s_nop", 0)

@@ -27,7 +27,7 @@
 #define AIR_WAVES_PER_SIMD 2      // -DAIR_WAVES_PER_SIMD=3 builds a three-wave form for comparison (tools/ab_variant.sh passes flags through)
 #endif
 // Waves per SIMD the compiler must make room for: two = at most 256 registers per lane.  Since the evaluation is cut by operation group
-// the nested-sum launches need 117 - 217 registers and no scratch (two to four waves per SIMD are resident, profiles/air_layer.md); only the per-operation
+// the nested-sum launches need 117 - 193 registers and no scratch (two to four waves per SIMD are resident, profiles/air_layer.md, profiles/air_flags.md); only the per-operation
 // instance (tests) reaches the cap.  History: round 2's 172 KB stack launch ran three times slower on one lease and on the driver's box
 // (12.7 - 13.4 against 4.3 - 4.6 ms); it had no scratch, so the size of its straight-line code is the suspect -- no
 // launch is larger than the 64 KiB instruction cache any more.  Workgroup barriers between the sections (256 lanes per workgroup, the
@@ -194,31 +194,43 @@ __device__ __forceinline__ void air_load_rows(AirRows<CL, LL>& r, fe* o, fe* nw,
 struct AirFlags {
     fe cff[8], hdf[4], begin_flag, noop_flag, n_void, assert_flag;      // hdf[0] is the PUSH flag
     fe lo2[4], mid[4], top[2];
+    fe ld_all;                                                          // ldf(31) = ld[0] * ld[1] * ld[2] * ld[3] * ld[4]: NOOP's low-degree part, and the op bits' ld product
     __device__ __forceinline__ fe ldf(int idx) const { return fe_mul(fe_mul(lo2[idx & 3], mid[(idx >> 2) & 3]), top[idx >> 4]); }
 };
+
+// The four products of two values with two bits and their complements, x * y for x in {1 - a, a}, y in {1 - b, b}, from ONE
+// multiplication: with na = 1 - a, nb = 1 - b and t[0] = na * nb,
+//     a * nb = nb - t[0],   na * b = na - t[0],   a * b = a - a * nb
+// (x * (1 - b) = x - x * b holds for every field element, so also on the cosets where the bits are not 0 / 1).  A subtraction is 10
+// instructions against the 71 of a multiplication.
+__device__ __forceinline__ void air_bit_pairs(fe* t, const fe& a, const fe& na, const fe& nb) {
+    t[0] = fe_mul(na, nb); t[1] = fe_sub(nb, t[0]); t[2] = fe_sub(na, t[0]); t[3] = fe_sub(a, t[1]);
+}
 
 template <class ROWS>
 __device__ __forceinline__ void air_op_flags(AirFlags& f, const ROWS& r) {
     const fe* cf = r.cf; const fe* ld = r.ld; const fe* hd = r.hd;
     {
         fe n0 = bnot(cf[0]), n1 = bnot(cf[1]), n2 = bnot(cf[2]);
-        fe t0 = fe_mul(n0, n1), t1 = fe_mul(cf[0], n1), t2 = fe_mul(n0, cf[1]), t3 = fe_mul(cf[0], cf[1]);
-        f.cff[0] = fe_mul(t0, n2); f.cff[1] = fe_mul(t1, n2); f.cff[2] = fe_mul(t2, n2); f.cff[3] = fe_mul(t3, n2);
-        f.cff[4] = fe_mul(t0, cf[2]); f.cff[5] = fe_mul(t1, cf[2]); f.cff[6] = fe_mul(t2, cf[2]); f.cff[7] = fe_mul(t3, cf[2]);
+        fe t[4];
+        air_bit_pairs(t, cf[0], n0, n1);
+#pragma unroll
+        for (int i = 0; i < 4; i++) { f.cff[i] = fe_mul(t[i], n2); f.cff[4 + i] = fe_sub(t[i], f.cff[i]); }       // t * cf[2] = t - t * (1 - cf[2])
         f.n_void = fe_mul(fe_mul(r.n_cf[0], r.n_cf[1]), r.n_cf[2]);      // next.cf_op_flags()[VOID]
         fe l0 = bnot(ld[0]), l1 = bnot(ld[1]), l2 = bnot(ld[2]), l3 = bnot(ld[3]);
-        f.lo2[0] = fe_mul(l0, l1); f.lo2[1] = fe_mul(ld[0], l1);
-        f.lo2[2] = fe_mul(l0, cf[1]);                                  // sic: cf_op_bits[1] (trace_state.rs:301)
-        f.lo2[3] = fe_mul(ld[0], ld[1]);
-        f.mid[0] = fe_mul(l2, l3); f.mid[1] = fe_mul(ld[2], l3); f.mid[2] = fe_mul(l2, ld[3]); f.mid[3] = fe_mul(ld[2], ld[3]);
+        f.lo2[0] = fe_mul(l0, l1); f.lo2[1] = fe_sub(l1, f.lo2[0]);
+        f.lo2[2] = fe_mul(l0, cf[1]);                                  // sic: cf_op_bits[1] (trace_state.rs:301): no complement of another entry
+        f.lo2[3] = fe_sub(ld[0], f.lo2[1]);
+        air_bit_pairs(f.mid, ld[2], l2, l3);
         f.top[0] = bnot(ld[4]); f.top[1] = ld[4];
         fe h0 = bnot(hd[0]), h1 = bnot(hd[1]);
-        f.hdf[0] = fe_mul(h0, h1); f.hdf[1] = fe_mul(hd[0], h1); f.hdf[2] = fe_mul(h0, hd[1]); f.hdf[3] = fe_mul(hd[0], hd[1]);
+        air_bit_pairs(f.hdf, hd[0], h0, h1);
     }
     {
         fe ld0 = f.ldf(0);
+        f.ld_all = f.ldf(31);
         f.begin_flag = fe_mul(ld0, f.hdf[0]);                          // trace_state.rs:329
-        f.noop_flag = fe_mul(f.ldf(31), f.hdf[3]);                     // trace_state.rs:335
+        f.noop_flag = fe_mul(f.ld_all, f.hdf[3]);                      // trace_state.rs:335
         f.hdf[0] = fe_mul(f.hdf[0], ld[0]);                            // PUSH (trace_state.rs:343)
         f.assert_flag = fe_mul(ld0, hd[0]);                            // ASSERT (trace_state.rs:346)
     }
@@ -260,8 +272,9 @@ template <class ACC, class ROWS>
 __device__ __forceinline__ void air_op_bits(ACC& acc, const ROWS& r, const AirFlags& f, const fe* per) {
     const fe* cf = r.cf; const fe* ld = r.ld; const fe* hd = r.hd;
     fe cf_sum = fe_add(fe_add(cf[0], cf[1]), cf[2]);
-    fe ld_prod = fe_mul(fe_mul(fe_mul(ld[0], ld[1]), fe_mul(ld[2], ld[3])), ld[4]);
-    fe hd_prod = fe_mul(hd[0], hd[1]);
+    // the products of all ld bits and of both hd bits are what the flags already hold: ldf(31), hdf[3] (the PUSH adjustment only touches
+    // hdf[0]), and their product is the NOOP flag
+    const fe ld_prod = f.ld_all, hd_prod = f.hdf[3], all_prod = f.noop_flag;
 #pragma unroll
     for (int i = 0; i < 3; i++) acc.emit(i, 0, is_bin(cf[i]));
 #pragma unroll
@@ -269,11 +282,11 @@ __device__ __forceinline__ void air_op_bits(ACC& acc, const ROWS& r, const AirFl
 #pragma unroll
     for (int i = 0; i < 2; i++) acc.emit(8 + i, 0, is_bin(hd[i]));
     const fe is_hacc = f.cff[0];
-    fe hacc_tr = fe_mul(fe_add(r.c_opc, fe_one()), is_hacc);
-    fe rest_tr = fe_mul(r.c_opc, bnot(is_hacc));
-    acc.emit(10, 1, fe_sub(fe_add(hacc_tr, rest_tr), r.n_opc));
-    acc.emit(11, 5, fe_mul(r.c_opc, fe_mul(bnot(ld_prod), bnot(hd_prod))));
-    acc.emit(12, 5, fe_mul(cf_sum, bnot(fe_mul(ld_prod, hd_prod))));
+    // (opc + 1) * hacc + opc * (1 - hacc) - next opc  (op_bits.rs:38-42)  =  opc + hacc - next opc
+    acc.emit(10, 1, fe_sub(fe_add(r.c_opc, is_hacc), r.n_opc));
+    // opc * (1 - L)(1 - H) and cf_sum * (1 - L H) share L H:  (1 - L)(1 - H) = (1 - L) - H + L H
+    acc.emit(11, 5, fe_mul(r.c_opc, fe_add(fe_sub(bnot(ld_prod), hd_prod), all_prod)));
+    acc.emit(12, 5, fe_mul(cf_sum, bnot(all_prod)));
     acc.emit(13, 3, fe_mul(f.cff[7], bnot(f.n_void)));
     fe prefix = fe_add(fe_add(f.cff[1], f.cff[4]), fe_add(f.cff[5], f.cff[6]));  // BEGIN, LOOP, WRAP, BREAK
     fe v = fe_mul(prefix, per[21]);

@@ -224,7 +224,7 @@ constexpr StMerge st_merge() {
 // differences are computed once by the caller), BEGIN / NOOP (stack untouched).
 struct StackHigh { fe push, cmp, rescr, keep; fe resc[6]; };       // the four flags and the RESCR differences
 
-template <int I, uint32_t GROUPS>
+template <int I, uint32_t GROUPS, int SDK>
 __device__ __forceinline__ void st_high_degree(fe_acc& outer, const StackRows& s, const StackHigh& h) {
     if constexpr (I < 8) {
         const fe* o = s.o; const fe* nw = s.nw;
@@ -234,8 +234,11 @@ __device__ __forceinline__ void st_high_degree(fe_acc& outer, const StackRows& s
             fe v;
             if constexpr (I == 0) v = is_bin(x_bit);
             else if constexpr (I == 1) v = is_bin(y_bit);
-            else if constexpr (I == 2) v = fe_sub(nw[4], fe_add(o[4], fe_mul(fe_mul(x_bit, bnot(y_bit)), not_set)));
-            else if constexpr (I == 3) v = fe_sub(nw[5], fe_add(o[5], fe_mul(fe_mul(y_bit, bnot(x_bit)), not_set)));
+            // x (1 - y) = x - x y and y (1 - x) = y - x y: slots 2 and 3 share x y where the depth is a constant.  With a run-time depth
+            // the shared product stays live between the two slots and costs the PUSH / CMP / BEGIN / NOOP launch a resident wave (131
+            // against 123 registers, profiles/air_flags.md), so those instances multiply by the complements
+            else if constexpr (I == 2) v = fe_sub(nw[4], fe_add(o[4], fe_mul(SDK ? fe_sub(x_bit, fe_mul(x_bit, y_bit)) : fe_mul(x_bit, bnot(y_bit)), not_set)));
+            else if constexpr (I == 3) v = fe_sub(nw[5], fe_add(o[5], fe_mul(SDK ? fe_sub(y_bit, fe_mul(x_bit, y_bit)) : fe_mul(y_bit, bnot(x_bit)), not_set)));
             else if constexpr (I == 4) v = fe_sub(nw[6], fe_add(o[6], fe_mul(y_bit, o[0])));
             else if constexpr (I == 5) v = fe_sub(nw[7], fe_add(o[7], fe_mul(x_bit, o[0])));
             else if constexpr (I == 6) v = fe_sub(not_set, fe_mul(bnot(o[5]), bnot(o[4])));
@@ -301,6 +304,6 @@ __device__ __forceinline__ fe st_output(const StackRows& s, const fe* lo2, const
             fe_acc_mac(outer, top[c], fe_acc_reduce(middle));
         }
     });
-    if constexpr ((GROUPS & AG_HIGH) != 0) st_high_degree<I, GROUPS>(outer, s, h);
+    if constexpr ((GROUPS & AG_HIGH) != 0) st_high_degree<I, GROUPS, SDK>(outer, s, h);
     return fe_acc_reduce(outer);
 }

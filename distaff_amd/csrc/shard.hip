@@ -6,9 +6,11 @@
 // exports and imports the shards.
 #include <set>
 #include <thread>
+#include <type_traits>
 #include "ctx.h"
 #include "comm.h"
 #include "host/steps.h"
+#include "host/shard_geometry.h"
 #include "host_util.h"
 #include "host_proof.h"
 
@@ -40,6 +42,45 @@ static int fri_replicated_from(const dst_ctx* c) {
     return c->num_fri_layers - 1;
 }
 static bool fri_layer_replicated(const dst_ctx* c, int d) { return c->sharded_layout && d >= c->fri_rep_from; }
+
+// One of the prover's three kinds of Merkle tree -- the trace tree, the constraint tree, the tree of FRI layer `arg` -- as the sharded
+// protocol sees it: everything that follows from (what, arg), stated here and nowhere else.
+struct ShardTree {
+    uint32_t arg;                              // FRI layer (0 for the other two)
+    int slot;                                  // index into dst_ctx::tree_krange
+    const char* name;                          // in messages
+    size_t K;                                  // boundary nodes per rank = leaves of one column
+    digest *leaves, *nodes, *upper;            // rank-local leaf array (nullptr: the constraint tree's leaves are raw pairs of cevals) and node heap; replicated upper heap
+    uint32_t rd_leaf, rd_node, rd_upper;       // the same three as buffer ids of the openings
+    uint64_t geo_leaves, geo_cols, geo_ranks;  // its Geometry: all leaves, leaves per k, ranks they are split over (1: a layer of the replicated FRI tail)
+    uint8_t* root;                             // where the context keeps the root (nullptr: step::fri_file_root)
+};
+static int shard_tree(dst_ctx* c, uint32_t what, uint32_t arg, ShardTree* t) {
+    switch (what) {
+        case SH_TRACE_TREE: *t = {0, 0, "trace tree", c->n, c->trace_leaves, c->trace_nodes, c->trace_upper, RD_TRACE_LEAF, RD_TRACE_NODE, RD_TRACE_UPPER, c->N, c->B, c->prm.world, c->trace_root}; return DST_OK;
+        case SH_CONSTRAINT_TREE: *t = {0, 1, "constraint tree", c->n, nullptr, c->cnodes, c->c_upper, RD_CEVAL, RD_C_NODE, RD_C_UPPER, c->N / 2, c->B / 2, c->prm.world, c->constraint_root}; return DST_OK;
+        case SH_FRI_TREE:
+            if ((int)arg >= c->num_fri_layers) return DST_ERR_ARG;
+            *t = {arg, 2 + (int)arg, "FRI tree", fri_nd(c, (int)arg) / 4, c->fri_leaves[arg], c->fri_nodes[arg], c->fri_upper[arg], RD_FRI_LEAF, RD_FRI_NODE, RD_FRI_UPPER,
+                  c->fri_size[arg] / 4, c->B, fri_layer_replicated(c, (int)arg) ? 1u : c->prm.world, nullptr};
+            return DST_OK;
+    }
+    return DST_ERR_ARG;
+}
+static void file_root(dst_ctx* c, const ShardTree& t, const uint8_t root[32]) {
+    if (t.root) memcpy(t.root, root, 32); else step::fri_file_root(c, (int)t.arg, root);
+}
+// this rank's t.K boundary nodes (device pointer): the level at which nodes stop being rank-local
+static const digest* tree_boundary(dst_ctx* c, const ShardTree& t) {
+    if (!t.leaves && c->Bc == 2) {
+        // two cosets per rank: a rank holds exactly one constraint-tree leaf per k, the raw pair (C(x_{B k + 2g}), C(x_{B k + 2g + 1}))
+        // (prover.rs:180-187), and no node below the replicated part: the "boundary nodes" are the leaves, interleaved from the
+        // coset-major evaluations [2][n]
+        k_coset_to_natural_len(c, c->cevals, 2, c->n, (fe*)c->cnodes);      // [2][n] elements -> n pairs; the local heap is unused in this case
+        return c->cnodes;
+    }
+    return t.nodes + t.K;
+}
 
 // Every buffer a collective of the sharded protocol touches exists from context creation on (dst_ctx_create, world > 1): a rank that fails
 // locally at proving time (no trace uploaded, a bad argument) can still take part in every exchange and report its status through
@@ -77,6 +118,17 @@ static int copy_out(dst_ctx* c, void* dst, const void* src, size_t bytes, int ds
     return DST_OK;
 }
 
+// what every sharded trace commit starts with: the layout, and the stream waits for an upload that is still in flight
+static int begin_sharded_layout(dst_ctx* c) {
+    c->sharded_layout = true;
+    for (bool& b : c->tree_krange) b = false;                  // dst_prove_sharded switches trees to k-ranges as it exchanges them
+    if (c->upload_pending) {
+        // dst_trace_upload_async: the copies run on upload_stream; the transforms read every register, so they wait for every group
+        for (size_t g = 0; g + 1 < c->upload_bounds.size(); g++) HIP_TRY(c, hipStreamWaitEvent(c->stream, c->upload_done[g], 0));
+        c->upload_pending = false;
+    }
+    return DST_OK;
+}
 // steps 1-2, local part: LDE of the owned cosets, their leaf digests and the local tree levels (down to one node per k)
 int dst_shard_commit_trace(dst_ctx* c) {
     if (!c) return DST_ERR_ARG;
@@ -85,13 +137,7 @@ int dst_shard_commit_trace(dst_ctx* c) {
     HIP_TRY(c, hipSetDevice(c->device));
     int r = ensure_shard_buffers(c);
     if (r) return r;
-    c->sharded_layout = true;
-    for (bool& b : c->tree_krange) b = false;                  // dst_prove_sharded switches trees to k-ranges as it exchanges them
-    if (c->upload_pending) {
-        // dst_trace_upload_async: the copies run on upload_stream; the transforms below read every register, so they wait for every group
-        for (size_t g = 0; g + 1 < c->upload_bounds.size(); g++) HIP_TRY(c, hipStreamWaitEvent(c->stream, c->upload_done[g], 0));
-        c->upload_pending = false;
-    }
+    if ((r = begin_sharded_layout(c))) return r;
     k_intt_columns(c, c->trace, c->trace_stride, c->polys, c->W);
     k_lde_columns(c, c->polys, c->lde, c->W);
     k_trace_leaves(c);
@@ -123,7 +169,7 @@ static int shard_combine_parts(dst_ctx* c, int parts) {
     if (parts & 2) {
         if (c->wait_comm && c->sh_ev[4]) (void)hipEventRecord(c->sh_ev[4], c->stream);      // dst_prove_sharded: end of the combination (phase 3 | 4)
         k_lde_fold8(c, c->cpoly, c->cevals);
-        if (c->Bc >= 4) {                                   // with two cosets per rank the leaves themselves are the boundary (see dst_shard_export)
+        if (c->Bc >= 4) {                                   // with two cosets per rank the leaves themselves are the boundary (see tree_boundary)
             k_constraint_level1(c);
             k_merkle(c, nullptr, c->cnodes, c->Bc * c->n / 4, c->n);
         }
@@ -168,15 +214,15 @@ int dst_shard_fri_fold(dst_ctx* c, const uint8_t special_x[16]) {
 // size in bytes of what this rank exports for (what, arg)
 int dst_shard_export_size(dst_ctx* c, uint32_t what, uint32_t arg, size_t* bytes) {
     if (!c || !bytes) return DST_ERR_ARG;
-    switch (what) {
-        case SH_TRACE_TREE: case SH_CONSTRAINT_TREE: *bytes = c->n * 32; return DST_OK;
-        case SH_FRI_TREE: if ((int)arg >= c->num_fri_layers) return DST_ERR_ARG; *bytes = fri_nd(c, arg) / 4 * 32; return DST_OK;
+    ShardTree t;
+    if (shard_tree(c, what, arg, &t) == DST_OK) { *bytes = t.K * 32; return DST_OK; }
+    switch (what) {                                              // the other items (a tree of a layer that does not exist is none of them)
         case SH_CEVAL: *bytes = (dst_internal_boundary_by_evaluation(c) ? 3 : 1) * (c->Bc / (c->B / 8)) * c->n * 16; return DST_OK;   // [i, f,] t
         case SH_FRI_LAST: *bytes = c->fri_size[c->num_fri_layers - 1] * 16; return DST_OK;       // the whole remainder, natural order (replicated)
         case SH_FRI_SEND_CAP: {                                  // the largest item dst_shard_fri_begin hands out
-            const int t = c->gather_buf ? c->fri_rep_from : fri_replicated_from(c);    // fixed once the shard buffers exist
-            size_t m = c->Bc * fri_nd(c, t) * 16;
-            for (int d = 0; d < t; d++) if (fri_nd(c, d) / 4 * 32 > m) m = fri_nd(c, d) / 4 * 32;
+            const int rep = c->gather_buf ? c->fri_rep_from : fri_replicated_from(c);    // fixed once the shard buffers exist
+            size_t m = c->Bc * fri_nd(c, rep) * 16;
+            for (int d = 0; d < rep; d++) if (shard_tree(c, SH_FRI_TREE, (uint32_t)d, &t) == DST_OK && t.K * 32 > m) m = t.K * 32;
             *bytes = m; return DST_OK;
         }
     }
@@ -187,23 +233,15 @@ int dst_shard_export(dst_ctx* c, uint32_t what, uint32_t arg, void* dst, int dst
     HIP_TRY(c, hipSetDevice(c->device));
     size_t bytes = 0;
     if (dst_shard_export_size(c, what, arg, &bytes)) { c->err = "dst_shard_export: bad item"; return DST_ERR_ARG; }
+    ShardTree t;
+    if (shard_tree(c, what, arg, &t) == DST_OK) return copy_out(c, dst, tree_boundary(c, t), bytes, dst_is_device);
     const void* src = nullptr;
     switch (what) {
-        case SH_TRACE_TREE: src = c->trace_nodes + c->n; break;
-        case SH_CONSTRAINT_TREE: src = c->cnodes + c->n; break;
-        case SH_FRI_TREE: src = c->fri_nodes[arg] + fri_nd(c, arg) / 4; break;
         case SH_CEVAL: src = dst_internal_boundary_by_evaluation(c) ? c->ceval : c->ceval + 2 * (c->Bc / (c->B / 8)) * c->n; break;   // local layout [3][Q][n]
         case SH_FRI_LAST:
             if (c->fri_committed != c->num_fri_layers) { c->err = "dst_shard_export: FRI commit phase not finished"; return DST_ERR_STATE; }
             src = fri_layer_natural(c, c->num_fri_layers - 1); break;
         default: c->err = "dst_shard_export: bad item"; return DST_ERR_ARG;
-    }
-    if (what == SH_CONSTRAINT_TREE && c->Bc == 2) {
-        // two cosets per rank: a rank holds exactly one constraint-tree leaf per k, the raw pair (C(x_{B k + 2g}), C(x_{B k + 2g + 1}))
-        // (prover.rs:180-187), and no node below the replicated part: the "boundary nodes" are the leaves, interleaved from the
-        // coset-major evaluations [2][n]
-        k_coset_to_natural_len(c, c->cevals, 2, c->n, (fe*)c->cnodes);      // [2][n] elements -> n pairs; the local heap is unused in this case
-        return copy_out(c, dst, c->cnodes, bytes, dst_is_device);
     }
     return copy_out(c, dst, src, bytes, dst_is_device);
 }
@@ -222,29 +260,53 @@ int dst_shard_import(dst_ctx* c, uint32_t what, uint32_t arg, const void* src, i
         c->ceval_inverted = false;                                  // dst_prove_sharded sets it after importing arrays it has inverse-transformed
         const size_t Q = c->Bc / (c->B / 8), blk = Q * c->n;        // gathered [G][V][Q][n] -> ceval [3][8][n], V = 3 (i, f, t) or 1 (t)
         const size_t V = dst_internal_boundary_by_evaluation(c) ? 3 : 1;
-        CTX_SYNC(c, "an imported tree");
+        CTX_SYNC(c, "the imported constraint evaluations");
         for (size_t g = 0; g < G; g++)
             for (size_t v = 0; v < V; v++)
                 HIP_TRY(c, hipMemcpyAsync(c->ceval + ((V == 3 ? v : 2) * 8 + g * Q) * c->n, (const fe*)c->gather_buf + (g * V + v) * blk, blk * 16, hipMemcpyDeviceToDevice, c->stream));
-        CTX_SYNC(c, "an imported tree");
+        CTX_SYNC(c, "the imported constraint evaluations");
         return DST_OK;
     }
-    digest* upper = nullptr; size_t nb = 0;
-    switch (what) {
-        case SH_TRACE_TREE: upper = c->trace_upper; nb = c->n; break;
-        case SH_CONSTRAINT_TREE: upper = c->c_upper; nb = c->n; break;
-        case SH_FRI_TREE: upper = c->fri_upper[arg]; nb = fri_nd(c, arg) / 4; break;
-        default: c->err = "dst_shard_import: item cannot be imported"; return DST_ERR_ARG;
-    }
-    k_upper_tree(c, (const digest*)c->gather_buf, upper, nb, (uint32_t)G);
+    ShardTree t;
+    if (shard_tree(c, what, arg, &t)) { c->err = "dst_shard_import: item cannot be imported"; return DST_ERR_ARG; }
+    k_upper_tree(c, (const digest*)c->gather_buf, t.upper, t.K, (uint32_t)G);
     uint8_t root[32];
-    HIP_TRY(c, hipMemcpyAsync(root, upper + 1, 32, hipMemcpyDeviceToHost, c->stream));
-    CTX_SYNC(c, "the imported constraint evaluations");
+    HIP_TRY(c, hipMemcpyAsync(root, t.upper + 1, 32, hipMemcpyDeviceToHost, c->stream));
+    CTX_SYNC(c, (std::string("the imported ") + t.name).c_str());
     HIP_TRY(c, hipGetLastError());
-    if (what == SH_TRACE_TREE) memcpy(c->trace_root, root, 32);
-    else if (what == SH_CONSTRAINT_TREE) memcpy(c->constraint_root, root, 32);
-    else step::fri_file_root(c, (int)arg, root);
+    file_root(c, t, root);
     if (root_out) memcpy(root_out, root, 32);
+    return DST_OK;
+}
+
+// The buffers of the openings: (buffer id, FRI layer) -> device source and bytes per item, for dst_shard_read and for the opening plan
+// (gather_requests).  DST_ERR_ARG: no such buffer or layer; *src == nullptr: not allocated (the exchange buffers of a one-rank context).
+// While the layout is not sharded (single-GPU phases) a tree has ONE full heap and "upper" names it.
+static int read_buffer(const dst_ctx* c, uint32_t buffer, uint32_t arg, const void** src, size_t* item) {
+    const bool fri = (buffer >= RD_FRI_E && buffer <= RD_FRI_UPPER) || buffer == RD_FRI_UPPER + RD_MID_OFFSET;
+    if (fri && (int)arg >= c->num_fri_layers) return DST_ERR_ARG;
+    const bool tail = fri && fri_layer_replicated(c, (int)arg);           // natural order, full heap on every rank
+    // subtree heap of a k-range tree: behind the 2G entries of the replicated top heap
+    auto mid = [&](const digest* upper) { return upper ? upper + 2 * c->prm.world : nullptr; };
+    *item = 32;
+    switch (buffer) {
+        case RD_TRACE_LEAF: *src = c->trace_leaves; break;
+        case RD_TRACE_NODE: *src = c->trace_nodes; break;
+        case RD_TRACE_UPPER: *src = c->sharded_layout ? c->trace_upper : c->trace_nodes; break;
+        case RD_CEVAL: *src = c->cevals; *item = 16; break;
+        case RD_C_NODE: *src = c->cnodes; break;
+        case RD_C_UPPER: *src = c->sharded_layout ? c->c_upper : c->cnodes; break;
+        case RD_FRI_E: *src = tail ? fri_layer_natural(c, (int)arg) : c->fri_e[arg]; *item = 16; break;
+        case RD_FRI_LEAF: *src = c->fri_leaves[arg]; break;
+        case RD_FRI_NODE: *src = c->fri_nodes[arg]; break;
+        case RD_FRI_UPPER: *src = c->sharded_layout && !tail ? c->fri_upper[arg] : c->fri_nodes[arg]; break;
+        case RD_LDE_ROW: *src = c->lde; *item = c->W * 16; break;         // a row = one element per register, gathered by position (k_gather_rows, gather_requests)
+        case RD_TEVAL: *src = c->ceval + 2 * (c->Bc / (c->B / 8)) * c->n; *item = 16; break;        // transition combination, this rank's evaluation cosets [Q][n]
+        case RD_TRACE_UPPER + RD_MID_OFFSET: *src = mid(c->trace_upper); break;
+        case RD_C_UPPER + RD_MID_OFFSET: *src = mid(c->c_upper); break;
+        case RD_FRI_UPPER + RD_MID_OFFSET: *src = mid(c->fri_upper[arg]); break;
+        default: return DST_ERR_ARG;
+    }
     return DST_OK;
 }
 
@@ -253,35 +315,16 @@ int dst_shard_read(dst_ctx* c, uint32_t buffer, uint32_t arg, const uint64_t* id
     if (!c || !idx || !out) return DST_ERR_ARG;
     HIP_TRY(c, hipSetDevice(c->device));
     if (count == 0) return DST_OK;
-    const void* src = nullptr; size_t item = 32;
-    switch (buffer) {
-        case RD_TRACE_LEAF: src = c->trace_leaves; break;
-        case RD_TRACE_NODE: src = c->trace_nodes; break;
-        case RD_TRACE_UPPER: src = c->trace_upper; break;
-        case RD_CEVAL: src = c->cevals; item = 16; break;
-        case RD_C_NODE: src = c->cnodes; break;
-        case RD_C_UPPER: src = c->c_upper; break;
-        case RD_FRI_E: if ((int)arg >= c->num_fri_layers) return DST_ERR_ARG; src = fri_layer_replicated(c, (int)arg) ? fri_layer_natural(c, (int)arg) : c->fri_e[arg]; item = 16; break;
-        case RD_FRI_LEAF: if ((int)arg >= c->num_fri_layers) return DST_ERR_ARG; src = c->fri_leaves[arg]; break;
-        case RD_FRI_NODE: if ((int)arg >= c->num_fri_layers) return DST_ERR_ARG; src = c->fri_nodes[arg]; break;
-        case RD_FRI_UPPER: if ((int)arg >= c->num_fri_layers) return DST_ERR_ARG; src = fri_layer_replicated(c, (int)arg) ? c->fri_nodes[arg] : c->fri_upper[arg]; break;
-        case RD_LDE_ROW: break;
-        case RD_TEVAL: src = c->ceval + 2 * (c->Bc / (c->B / 8)) * c->n; item = 16; break;        // transition combination, this rank's evaluation cosets [Q][n]
-        default: c->err = "dst_shard_read: unknown buffer"; return DST_ERR_ARG;
-    }
+    const void* src = nullptr; size_t item = 0;
+    if (read_buffer(c, buffer, arg, &src, &item)) { c->err = "dst_shard_read: unknown buffer"; return DST_ERR_ARG; }
     size_t idx_bytes = ((size_t)count * 8 + 15) / 16 * 16;
-    size_t out_bytes = buffer == RD_LDE_ROW ? (size_t)count * c->W * 16 : (size_t)count * item;
+    size_t out_bytes = (size_t)count * item;
     if (idx_bytes + out_bytes > c->stage_bytes) { c->err = "dst_shard_read: staging buffer too small"; return DST_ERR_ARG; }
     uint64_t* d_idx = (uint64_t*)c->d_stage; uint8_t* d_out = c->d_stage + idx_bytes;
-    if (buffer == RD_LDE_ROW) {
-        // idx holds natural positions B*k + j owned by this rank
-        HIP_TRY(c, hipMemcpyAsync(d_idx, idx, (size_t)count * 8, hipMemcpyHostToDevice, c->stream));
-        k_gather_rows(c, d_idx, count, (fe*)d_out);
-    } else {
-        if (!src) { c->err = "dst_shard_read: buffer not allocated (world == 1?)"; return DST_ERR_STATE; }
-        HIP_TRY(c, hipMemcpyAsync(d_idx, idx, (size_t)count * 8, hipMemcpyHostToDevice, c->stream));
-        k_gather(c, src, item, d_idx, count, d_out);
-    }
+    if (!src) { c->err = "dst_shard_read: buffer not allocated (world == 1?)"; return DST_ERR_STATE; }
+    HIP_TRY(c, hipMemcpyAsync(d_idx, idx, (size_t)count * 8, hipMemcpyHostToDevice, c->stream));
+    if (buffer == RD_LDE_ROW) k_gather_rows(c, d_idx, count, (fe*)d_out);      // idx holds natural positions B*k + j owned by this rank
+    else k_gather(c, src, item, d_idx, count, d_out);
     HIP_TRY(c, hipMemcpyAsync(out, d_out, out_bytes, hipMemcpyDeviceToHost, c->stream));
     HIP_TRY(c, hipStreamSynchronize(c->stream));
     HIP_TRY(c, hipGetLastError());
@@ -327,6 +370,12 @@ static int fri_replicated_tail(dst_ctx* c, const void* gathered, int src_is_devi
     c->fri_tail_pending = false;
     return DST_OK;
 }
+// the fold of the last committed layer with x drawn from its root on the host (fri/prover.rs:40 field::prng(root))
+static int fri_fold_from_root(dst_ctx* c, const uint8_t root[32]) {
+    fe x;
+    prng_vector(root, 1, &x);
+    return dst_shard_fri_fold(c, (const uint8_t*)&x);
+}
 int dst_shard_fri_end(dst_ctx* c, const void* gathered, int src_is_device, uint8_t root_out[32]) {
     if (!c || !gathered || !root_out) return DST_ERR_ARG;
     HIP_TRY(c, hipSetDevice(c->device));
@@ -334,11 +383,7 @@ int dst_shard_fri_end(dst_ctx* c, const void* gathered, int src_is_device, uint8
     if (c->fri_committed == 0) { c->err = "dst_shard_fri_end: no layer in flight"; return DST_ERR_STATE; }
     const uint32_t d = (uint32_t)c->fri_committed - 1;
     int r = dst_shard_import(c, SH_FRI_TREE, d, gathered, src_is_device, root_out);
-    if (r) return r;
-    fe x;
-    prng_vector(root_out, 1, &x);                              // fri/prover.rs:40 field::prng(root)
-    uint8_t xb[16]; memcpy(xb, &x, 16);
-    return dst_shard_fri_fold(c, xb);                          // a sharded layer is never the last one
+    return r ? r : fri_fold_from_root(c, root_out);            // a sharded layer is never the last one
 }
 // roots of all FRI layers once the commit phase is over (the layers of the replicated tail are committed inside dst_shard_fri_end)
 int dst_shard_fri_roots(dst_ctx* c, uint8_t* roots, size_t cap, uint32_t* num_layers, uint32_t* replicated_from) {
@@ -361,32 +406,6 @@ namespace {
 struct OpenReq { int owner; uint32_t buffer, arg; uint64_t index; uint32_t bytes; };       // owner -1: replicated, served by rank 0
 struct OpenPlan { std::vector<OpenReq> reqs; std::vector<size_t> slot; Writer w; };
 
-struct Geometry {                      // distaff_amd/sharded.py TreeGeometry: leaves Bt*k + j', columns j' split over G ranks
-    uint64_t L, Bt, G, Bct, K;
-    bool krange;                       // levels between the rank-local ones and the top log2(G): owned by k-ranges (dst_prove_sharded) instead of replicated
-    Geometry(uint64_t leaves, uint64_t bt, uint64_t g, bool kr = false) : L(leaves), Bt(bt), G(g), Bct(bt / g), K(leaves / bt), krange(kr && g > 1) {}
-    void leaf(uint64_t i, int& g, uint64_t& local) const { uint64_t k = i / Bt, j = i % Bt; g = (int)(j / Bct); local = k * Bct + (j - (uint64_t)g * Bct); }
-    // zone: 0 rank-local heap, 1 replicated heap (global indices), 2 the owner's subtree heap (k-range mode)
-    void node(uint64_t heap, int& g, uint64_t& idx, int* zone = nullptr) const {
-        uint64_t level = 1; while (level * 2 <= heap) level *= 2;              // nodes on this level
-        uint64_t t = heap - level, span = L / level;
-        if (zone) *zone = 0;
-        if (span >= Bct) {
-            if (krange && level > G) {                                         // subtree of the rank that owns k in [g*K/G, (g+1)*K/G): level/G nodes of this level each
-                const uint64_t per = level / G;
-                g = (int)(t / per); idx = per + t % per;
-                if (zone) *zone = 2;
-                return;
-            }
-            g = -1; idx = heap;
-            if (zone) *zone = 1;
-            return;
-        }
-        uint64_t local_leaf; leaf(t * span, g, local_leaf);
-        idx = L / (G * span) + local_leaf / span;                              // nodes of this level held by one rank = L / (G * span), also when L < Bt
-    }
-};
-
 void plan_item(OpenPlan& p, int owner, uint32_t buffer, uint32_t arg, uint64_t index, uint32_t bytes) {
     p.reqs.push_back({owner, buffer, arg, index, bytes});
     p.slot.push_back(p.w.b.size());
@@ -399,20 +418,23 @@ void plan_element(const dst_ctx* c, OpenPlan& p, uint32_t buffer, uint32_t arg, 
     uint64_t k = pos / c->B, j = pos % c->B, g = j / c->Bc;
     plan_item(p, (int)g, buffer, arg, (j - g * c->Bc) * nd + k, 16);
 }
-void plan_tree_nodes(const dst_ctx* c, OpenPlan& p, const BatchPlan& bp, const Geometry& geo, uint32_t leaf_buf, uint32_t node_buf, uint32_t upper_buf,
-                     uint32_t arg, bool raw_pair_leaves) {
+// the nodes of a batch proof over tree (what, arg); the layer exists: build_open_plan walks the context's own layers
+void plan_tree_nodes(dst_ctx* c, OpenPlan& p, const BatchPlan& bp, uint32_t what, uint32_t arg) {
+    ShardTree t;
+    (void)shard_tree(c, what, arg, &t);
+    const Geometry geo(t.geo_leaves, t.geo_cols, t.geo_ranks, c->sharded_layout && c->tree_krange[t.slot]);
     p.w.u64(bp.nodes.size());
     for (auto& l : bp.nodes) {
         p.w.u64(l.size());
         for (auto& r : l) {
             int g; uint64_t idx;
             if (r.is_leaf) {
-                if (raw_pair_leaves) { plan_element(c, p, RD_CEVAL, 0, 2 * r.index, c->n); plan_element(c, p, RD_CEVAL, 0, 2 * r.index + 1, c->n); }
-                else { geo.leaf(r.index, g, idx); plan_item(p, g, leaf_buf, arg, idx, 32); }
+                if (!t.leaves) { plan_element(c, p, t.rd_leaf, 0, 2 * r.index, c->n); plan_element(c, p, t.rd_leaf, 0, 2 * r.index + 1, c->n); }      // the raw pair
+                else { geo.leaf(r.index, g, idx); plan_item(p, g, t.rd_leaf, t.arg, idx, 32); }
             } else {
                 int zone = 0;
                 geo.node(r.index, g, idx, &zone);
-                plan_item(p, g, zone == 0 ? node_buf : zone == 1 ? upper_buf : upper_buf + RD_MID_OFFSET, arg, idx, 32);
+                plan_item(p, g, zone == 0 ? t.rd_node : zone == 1 ? t.rd_upper : t.rd_upper + RD_MID_OFFSET, t.arg, idx, 32);
             }
         }
     }
@@ -420,7 +442,7 @@ void plan_tree_nodes(const dst_ctx* c, OpenPlan& p, const BatchPlan& bp, const G
 
 // the serialised StarkProof (proof.rs:11-22) with empty slots; same field order as dst_build_proof (api.hip)
 int build_open_plan(dst_ctx* c, const uint64_t* positions_in, uint32_t num_positions, uint64_t pow_nonce, OpenPlan& p) {
-    const uint64_t G = c->prm.world, B = c->B, N = c->N, n = c->n, W = c->W;
+    const uint64_t B = c->B, N = c->N, n = c->n, W = c->W;
     std::vector<uint64_t> positions(positions_in, positions_in + num_positions);
     for (uint64_t q : positions) if (q >= N) { c->err = "query position out of range"; return DST_ERR_ARG; }
     {   // MerkleTree::prove_batch asserts this (merkle.rs:69): a repeated position would silently drop an opening from the batch proof
@@ -433,7 +455,7 @@ int build_open_plan(dst_ctx* c, const uint64_t* positions_in, uint32_t num_posit
     w.raw(c->trace_root, 32);
     w.u8((uint8_t)c->log_N); w.u8((uint8_t)c->prm.ctx_depth); w.u8((uint8_t)c->prm.loop_depth); w.u8((uint8_t)c->stack_depth); w.u32((uint32_t)c->op_count);
     BatchPlan tp = plan_batch(positions, N);
-    plan_tree_nodes(c, p, tp, Geometry(N, B, G, c->sharded_layout && c->tree_krange[0]), RD_TRACE_LEAF, RD_TRACE_NODE, RD_TRACE_UPPER, 0, false);
+    plan_tree_nodes(c, p, tp, SH_TRACE_TREE, 0);
     w.u64(positions.size());
     for (uint64_t q : positions) { w.u64(W); plan_item(p, (int)((q % B) / c->Bc), RD_LDE_ROW, 0, q, (uint32_t)(W * 16)); }
     w.raw(c->constraint_root, 32);
@@ -442,7 +464,7 @@ int build_open_plan(dst_ctx* c, const uint64_t* positions_in, uint32_t num_posit
         BatchPlan cp = plan_batch(cpos, N / 2);
         w.u64(cp.values.size());
         for (uint64_t u : cp.values) { plan_element(c, p, RD_CEVAL, 0, 2 * u, n); plan_element(c, p, RD_CEVAL, 0, 2 * u + 1, n); }
-        plan_tree_nodes(c, p, cp, Geometry(N / 2, B / 2, G, c->sharded_layout && c->tree_krange[1]), 0, RD_C_NODE, RD_C_UPPER, 0, true);
+        plan_tree_nodes(c, p, cp, SH_CONSTRAINT_TREE, 0);
         w.u8(cp.depth);
     }
     w.u64(W); w.raw(c->deep_z1.data(), W * 16);
@@ -456,7 +478,7 @@ int build_open_plan(dst_ctx* c, const uint64_t* positions_in, uint32_t num_posit
         w.raw(c->fri_roots[d].data(), 32);
         w.u64(pos.size());
         for (uint64_t r : pos) for (uint64_t s4 = 0; s4 < 4; s4++) plan_element(c, p, RD_FRI_E, (uint32_t)d, r + s4 * R, nd);
-        plan_tree_nodes(c, p, fp, Geometry(R, B, fri_layer_replicated(c, d) ? 1 : G, c->sharded_layout && c->tree_krange[2 + d]), RD_FRI_LEAF, RD_FRI_NODE, RD_FRI_UPPER, (uint32_t)d, false);
+        plan_tree_nodes(c, p, fp, SH_FRI_TREE, (uint32_t)d);
         w.u8(fp.depth);
     }
     w.raw(c->fri_roots[L - 1].data(), 32);
@@ -466,26 +488,6 @@ int build_open_plan(dst_ctx* c, const uint64_t* positions_in, uint32_t num_posit
     w.u64(pow_nonce);
     w.u8((uint8_t)c->log_b); w.u8((uint8_t)c->prm.num_queries); w.u8((uint8_t)c->prm.grinding_factor); w.u8(0);
     return DST_OK;
-}
-
-const void* read_source(dst_ctx* c, uint32_t buffer, uint32_t arg) {
-    switch (buffer) {
-        case RD_TRACE_LEAF: return c->trace_leaves;
-        case RD_TRACE_NODE: return c->trace_nodes;
-        case RD_TRACE_UPPER: return c->sharded_layout ? c->trace_upper : c->trace_nodes;      // single-GPU phases: one full heap per tree
-        case RD_CEVAL: return c->cevals;
-        case RD_C_NODE: return c->cnodes;
-        case RD_C_UPPER: return c->sharded_layout ? c->c_upper : c->cnodes;
-        case RD_FRI_E: return (int)arg < c->num_fri_layers ? (fri_layer_replicated(c, (int)arg) ? (const void*)fri_layer_natural(c, (int)arg) : (const void*)c->fri_e[arg]) : nullptr;
-        case RD_FRI_LEAF: return (int)arg < c->num_fri_layers ? c->fri_leaves[arg] : nullptr;
-        case RD_FRI_NODE: return (int)arg < c->num_fri_layers ? c->fri_nodes[arg] : nullptr;
-        case RD_FRI_UPPER: return (int)arg < c->num_fri_layers ? (c->sharded_layout && !fri_layer_replicated(c, (int)arg) ? c->fri_upper[arg] : c->fri_nodes[arg]) : nullptr;
-        // subtree heaps of k-range trees sit behind the 2G entries of the replicated top heap
-        case RD_TRACE_UPPER + RD_MID_OFFSET: return c->trace_upper + 2 * c->prm.world;
-        case RD_C_UPPER + RD_MID_OFFSET: return c->c_upper + 2 * c->prm.world;
-        case RD_FRI_UPPER + RD_MID_OFFSET: return (int)arg < c->num_fri_layers ? c->fri_upper[arg] + 2 * c->prm.world : nullptr;
-    }
-    return nullptr;
 }
 }  // namespace
 
@@ -505,9 +507,9 @@ static int gather_requests(dst_ctx* c, const OpenPlan& p, int me, bool everythin
             const fe* base = c->lde + (j - c->j0) * c->n + k;
             for (size_t reg = 0; reg < c->W; reg++) addr.push_back((uint64_t)(uintptr_t)(base + reg * c->Bc * c->n));
         } else {
-            const uint8_t* src = (const uint8_t*)read_source(c, r.buffer, r.arg);
-            if (!src) { c->err = "openings: buffer not allocated"; return DST_ERR_STATE; }
-            for (uint32_t o = 0; o < r.bytes; o += 16) addr.push_back((uint64_t)(uintptr_t)(src + r.index * r.bytes + o));
+            const void* src = nullptr; size_t item = 0;
+            if (read_buffer(c, r.buffer, r.arg, &src, &item) || !src) { c->err = "openings: buffer not allocated"; return DST_ERR_STATE; }
+            for (uint32_t o = 0; o < r.bytes; o += 16) addr.push_back((uint64_t)(uintptr_t)((const uint8_t*)src + r.index * item + o));
         }
         total += r.bytes;
     }
@@ -559,13 +561,10 @@ int dst_shard_open(dst_ctx* c, const uint64_t* positions, uint32_t num_positions
     }
     OpenPlan& p = *sp;
     const int me = (int)c->prm.rank;
-    size_t total = 0;
-    for (auto& r : p.reqs) if (r.owner == me || (r.owner < 0 && me == 0)) total += r.bytes;
-    *blob_len = total;
-    if (all_lens) {                                        // every rank's share follows from the same plan
-        for (uint32_t g = 0; g < c->prm.world; g++) all_lens[g] = 0;
-        for (auto& r : p.reqs) all_lens[r.owner < 0 ? 0 : r.owner] += r.bytes;
-    }
+    std::vector<uint64_t> lens(c->prm.world, 0);           // every rank's share follows from the same plan
+    for (auto& r : p.reqs) lens[r.owner < 0 ? 0 : r.owner] += r.bytes;
+    const size_t total = *blob_len = (size_t)lens[me];
+    if (all_lens) memcpy(all_lens, lens.data(), lens.size() * 8);
     if (!blob) return DST_OK;
     if (cap < total) { c->err = "dst_shard_open: blob buffer too small"; return DST_ERR_ARG; }
     std::vector<uint8_t> mine;
@@ -627,7 +626,6 @@ int dst_shard_info(dst_ctx* c, uint64_t* op_count, uint32_t* num_fri_layers, uin
     return DST_OK;
 }
 
-
 // ---- the whole sharded proof behind the C-ABI ------------------------------------------------------------------------------------------
 // dst_prove_sharded = stark::prove (prover.rs:17-168) across the ranks of a communicator, with the collectives issued here (RCCL or the
 // in-process transport, comm.hip).  What is split and what is exchanged:
@@ -646,8 +644,7 @@ int dst_shard_info(dst_ctx* c, uint64_t* op_count, uint32_t* num_fri_layers, uin
 // work; its status travels with data that is exchanged anyway -- ONE 96-byte record per rank and tree (subtree root + status; for the
 // constraint tree also the first failing step of the rank's constraint check, copied from the device word the kernels wrote: no host
 // exchange and no wait of its own after the evaluation), read back with the root, and inside the opening-length exchange.  Every rank
-// returns the first failing rank's code.  (Round 2 agreed on a status word through a host-staged all-gather after every phase: ~26 per
-// proof; round 3 sent roots and status in two collectives per tree and exchanged the failing step through the host.)
+// returns the first failing rank's code.
 namespace {
 struct StatusRec { int32_t rc; int32_t pad; uint64_t bad_step; fe payload[3]; };      // 64 bytes per rank; bad_step: first trace step whose constraints fail on this rank's cosets (~0: none; constraint tree only); payload: rank 0's last trace state (op counter, program hash)
 static_assert(sizeof(StatusRec) == 64, "StatusRec is exchanged as 64 bytes");
@@ -658,8 +655,8 @@ struct Sharded {
     dst_ctx* c; dst_comm* comm;
     int rc = DST_OK;                       // this rank's own status: sticky, skips its local steps
     int agreed = DST_OK;                   // first failing rank's code once an exchange has shown one
-    // a rank-local step; collectives are issued regardless (see above)
-    template <class F> void local(F&& f) { if (rc == DST_OK) { rc = f(); } }
+    // a rank-local step, returning its code or -- launches only -- nothing; collectives are issued regardless (see above)
+    template <class F> void local(F&& f) { if (rc != DST_OK) return; if constexpr (std::is_void<decltype(f())>::value) f(); else rc = f(); }
     // host time inside the transport's calls (an enqueue on a stream-ordered transport, the whole exchange on a blocking one)
     template <class F> int timed(F&& f) { const double t = wall_ms(); const int r = f(); c->shard_ms[0] += wall_ms() - t; return r; }
     // ... and, for a collective on device buffers, two events around it on the stream it is queued on: enqueue -> completion as the device
@@ -690,50 +687,49 @@ struct Sharded {
     void fail(int code, const std::string& msg) { if (rc == DST_OK) { rc = code; c->err = msg; } }
     // collective errors are not rank-local: the transport failed for everyone (or will hang for everyone)
     bool coll(int r, const char* what) { if (r != DST_OK) { if (rc == DST_OK) { rc = r; c->err = std::string(what) + ": " + comm->err; } agreed = agreed ? agreed : r; return false; } return true; }
-    void saw(const StatusRec* all, const char* phase) {
-        for (uint32_t g = 0; g < comm->world && agreed == DST_OK; g++)
-            if (all[g].rc != DST_OK) { agreed = all[g].rc; if (rc == DST_OK) c->err = std::string(phase) + ": rank " + std::to_string(g) + " reported error " + std::to_string(all[g].rc); }
+    // the ranks' codes as an exchange delivered them (code_of(g)): the first failing rank's code wins, the message names the rank and the phase
+    template <class F> void saw(const char* phase, F&& code_of) {
+        for (uint32_t g = 0; g < comm->world && agreed == DST_OK; g++) {
+            const int64_t code = code_of(g);
+            if (code != DST_OK) { agreed = (int)code; if (rc == DST_OK) c->err = std::string(phase) + ": rank " + std::to_string(g) + " reported error " + std::to_string(code); }
+        }
     }
+    // Collectives that can overlap this rank's own work go to their own stream (dst_ctx::comm_stream), ordered against the main stream by
+    // events: on a stream-ordered transport, or with DISTAFF_SHARD_FORCE_OVERLAP=1 -- the same choreography over a blocking transport,
+    // which is how the tests reach it without several RCCL ranks.
+    bool side_stream() const { return (comm->stream_ordered() || c->sw_flag("DISTAFF_SHARD_FORCE_OVERLAP")) && comm->world > 1 && !c->sw_flag("DISTAFF_SHARD_NO_OVERLAP"); }
 };
 
-// this rank's boundary nodes of a tree (device pointer, K of them): the level at which nodes stop being rank-local
-int shard_boundary(dst_ctx* c, uint32_t what, uint32_t arg, const digest** src, size_t* K) {
-    switch (what) {
-        case SH_TRACE_TREE: *src = c->trace_nodes + c->n; *K = c->n; return DST_OK;
-        case SH_CONSTRAINT_TREE:
-            *K = c->n;
-            if (c->Bc == 2) {                                    // two cosets per rank: the raw leaf pairs are the boundary (see dst_shard_export)
-                k_coset_to_natural_len(c, c->cevals, 2, c->n, (fe*)c->cnodes);
-                *src = c->cnodes;
-            } else *src = c->cnodes + c->n;
-            return DST_OK;
-        case SH_FRI_TREE: *K = fri_nd(c, (int)arg) / 4; *src = c->fri_nodes[arg] + *K; return DST_OK;
-    }
-    c->err = "shard_boundary: bad item"; return DST_ERR_ARG;
+// the ranks' records and the root of a tree exchange, once they are on the host: first failing rank's code into S.agreed, else the root is filed
+void tree_exchange_finish(Sharded& S, const ShardTree& t, const uint8_t* slot, fe* payload_out, int64_t* first_bad) {
+    const size_t G = S.comm->world;
+    std::vector<TreeRec> all(G);
+    memcpy(all.data(), slot, G * sizeof(TreeRec));
+    S.saw(t.name, [&](uint32_t g) { return all[g].st.rc; });
+    if (payload_out) for (int i = 0; i < 3; i++) payload_out[i] = all[0].st.payload[i];
+    if (first_bad) { *first_bad = -1; for (size_t g = 0; g < G; g++) if (all[g].st.rc == DST_OK && all[g].st.bad_step != ~0ull && (*first_bad < 0 || (int64_t)all[g].st.bad_step < *first_bad)) *first_bad = (int64_t)all[g].st.bad_step; }
+    if (!S.agreed) file_root(S.c, t, slot + G * sizeof(TreeRec));
 }
-
-// Finishes a tree from the ranks' boundary nodes and returns its root (replicated).  The ranks' status records ride with the subtree
+// Finishes a tree from the ranks' boundary nodes and files its root (replicated: file_root).  The ranks' status records ride with the subtree
 // roots: on return S.agreed holds the first failing rank's code.  `payload` (rank 0 -> everyone), when given, is three field elements
 // read from rank 0's device memory at `payload_src[i]`.
 // defer_slot != nullptr: nothing is waited for -- the records and the root are copied into that page-locked slot (G * 96 + 32 bytes) behind the
 // exchange, and tree_exchange_finish looks at them after the caller's next synchronisation (the sharded FRI layers: their x is drawn on
 // the device from the root, so the host needs neither root nor status before the end of the commit phase).
-void tree_exchange_finish(Sharded& S, uint32_t what, uint32_t arg, const uint8_t* slot, fe* payload_out, int64_t* first_bad);
-void tree_exchange(Sharded& S, uint32_t what, uint32_t arg, uint8_t root[32], const fe* const* payload_src = nullptr, fe* payload_out = nullptr,
+void tree_exchange(Sharded& S, uint32_t what, uint32_t arg, const fe* const* payload_src = nullptr, fe* payload_out = nullptr,
                    const uint64_t* bad_src = nullptr, int64_t* first_bad = nullptr, uint8_t* defer_slot = nullptr) {
     dst_ctx* c = S.c; dst_comm* comm = S.comm;
     const size_t G = comm->world;
-    const digest* src = nullptr; size_t K = 0;
-    if (shard_boundary(c, what, arg, &src, &K)) { S.fail(DST_ERR_ARG, c->err); S.agreed = DST_ERR_ARG; return; }      // the same on every rank
-    digest* upper = what == SH_TRACE_TREE ? c->trace_upper : what == SH_CONSTRAINT_TREE ? c->c_upper : c->fri_upper[arg];
-    const int slot = what == SH_TRACE_TREE ? 0 : what == SH_CONSTRAINT_TREE ? 1 : 2 + (int)arg;
+    ShardTree t;
+    if (shard_tree(c, what, arg, &t)) { S.fail(DST_ERR_ARG, "tree_exchange: bad item"); S.agreed = DST_ERR_ARG; return; }      // the same on every rank
+    const digest* src = tree_boundary(c, t);
     c->shard_trees++;
-    const bool krange = G > 1 && K >= G && K % G == 0 && !c->sw_flag("DISTAFF_SHARD_TREE_GATHER");
-    c->tree_krange[slot] = krange;
-    if (c->sw_flag("DISTAFF_SHARD_DEBUG") && comm->rank == 0) fprintf(stderr, "[distaff] tree %u/%u: %zu boundary nodes per rank, %s\n", what, arg, K, krange ? "k-range exchange (all-to-all + root all-gather)" : "all-gather of boundary nodes");
-    if ((krange ? K * 32 : K * 32 * G) > c->gather_bytes) { S.fail(DST_ERR_ARG, "tree_exchange: gather buffer too small"); S.agreed = DST_ERR_ARG; return; }   // the same on every rank
+    const bool krange = G > 1 && t.K >= G && t.K % G == 0 && !c->sw_flag("DISTAFF_SHARD_TREE_GATHER");
+    c->tree_krange[t.slot] = krange;
+    if (c->sw_flag("DISTAFF_SHARD_DEBUG") && comm->rank == 0) fprintf(stderr, "[distaff] tree %u/%u: %zu boundary nodes per rank, %s\n", what, arg, t.K, krange ? "k-range exchange (all-to-all + root all-gather)" : "all-gather of boundary nodes");
+    if ((krange ? t.K * 32 : t.K * 32 * G) > c->gather_bytes) { S.fail(DST_ERR_ARG, "tree_exchange: gather buffer too small"); S.agreed = DST_ERR_ARG; return; }   // the same on every rank
     // this rank's record of the exchange: status (and rank 0's payload) staged now, the subtree root joins it below -- ONE small all-gather
-    // per tree carries both (the roots used to travel in a collective of their own)
+    // per tree carries both
     // (queued from a slot of the page-locked staging area: with defer_slot nothing below waits for the stream before `mine` would go out of scope)
     StatusRec& mine = reinterpret_cast<StatusRec*>(c->h_stage + HS_STATUS)[(c->shard_trees - 1) % HS_STATUS_SLOTS];
     mine = StatusRec{}; mine.rc = S.rc; mine.bad_step = ~0ull;
@@ -745,58 +741,34 @@ void tree_exchange(Sharded& S, uint32_t what, uint32_t arg, uint8_t root[32], co
         for (int i = 0; i < 3 && staged; i++) staged = hipMemcpyAsync(&recs[0].st.payload[i], payload_src[i], sizeof(fe), hipMemcpyDeviceToDevice, c->stream) == hipSuccess;
     if (!staged) S.fail(DST_ERR_HIP, "tree_exchange: staging of the status record failed");
     if (krange) {
-        const size_t chunk = K / G;                              // boundary nodes per (sender, owner) pair
+        const size_t chunk = t.K / G;                              // boundary nodes per (sender, owner) pair
         if (!S.coll(S.coll_on(1, c->stream, [&] { return comm->all_to_all(src, c->gather_buf, chunk * 32, c->stream); }), "tree_exchange")) return;
-        digest* mid = upper + 2 * G;                             // this rank's subtree heap: mid[1] = its root, mid[K + kl*G + r] = boundary node of rank r at k = g*K/G + kl
+        digest* mid = t.upper + 2 * G;                             // this rank's subtree heap: mid[1] = its root, mid[K + kl*G + r] = boundary node of rank r at k = g*K/G + kl
         S.local([&]() -> int {
             k_upper_tree(c, (const digest*)c->gather_buf, mid, chunk, (uint32_t)G);
             HIP_TRY(c, hipMemcpyAsync(&recs[comm->rank].root, mid + 1, sizeof(digest), hipMemcpyDeviceToDevice, c->stream));
             return DST_OK;
         });
-        if (!S.coll(S.coll_on(2, c->stream, [&] { return comm->all_gather(recs + comm->rank, recs, sizeof(TreeRec), c->stream); }), "tree_exchange")) return;
-        S.local([&] { k_digests_from_records(c, recs, sizeof(TreeRec), upper + G, G); k_merkle(c, nullptr, upper, G, 0); return DST_OK; });      // the top log2(G) levels, on every rank
     } else {
-        if (!S.coll(S.coll_on(2, c->stream, [&] { return comm->all_gather(src, c->gather_buf, K * 32, c->stream); }), "tree_exchange")) return;
-        S.local([&] { k_upper_tree(c, (const digest*)c->gather_buf, upper, K, (uint32_t)G); return DST_OK; });
-        if (!S.coll(S.coll_on(2, c->stream, [&] { return comm->all_gather(recs + comm->rank, recs, sizeof(TreeRec), c->stream); }), "tree_exchange")) return;
+        if (!S.coll(S.coll_on(2, c->stream, [&] { return comm->all_gather(src, c->gather_buf, t.K * 32, c->stream); }), "tree_exchange")) return;
+        S.local([&] { k_upper_tree(c, (const digest*)c->gather_buf, t.upper, t.K, (uint32_t)G); });
     }
-    if (defer_slot) {
-        bool okd = hipMemcpyAsync(defer_slot, recs, G * sizeof(TreeRec), hipMemcpyDeviceToHost, c->stream) == hipSuccess;
-        okd = okd && hipMemcpyAsync(defer_slot + G * sizeof(TreeRec), upper + 1, 32, hipMemcpyDeviceToHost, c->stream) == hipSuccess;
-        if (!okd) S.fail(DST_ERR_HIP, "tree_exchange: read-back could not be queued");
-        return;
-    }
+    if (!S.coll(S.coll_on(2, c->stream, [&] { return comm->all_gather(recs + comm->rank, recs, sizeof(TreeRec), c->stream); }), "tree_exchange")) return;
+    if (krange) S.local([&] { k_digests_from_records(c, recs, sizeof(TreeRec), t.upper + G, G); k_merkle(c, nullptr, t.upper, G, 0); });      // the top log2(G) levels, on every rank
     const double t_wait = wall_ms();
     // into PAGE-LOCKED memory: a copy into pageable memory would make the host wait inside hipMemcpyAsync for everything queued before it --
     // the exchange included -- without any bound (found by the stalled-collective test over the stream-ordered in-process transport)
-    uint8_t* const host = c->h_stage + HS_TREE_READBACK;
+    uint8_t* const host = defer_slot ? defer_slot : c->h_stage + HS_TREE_READBACK;
     bool ok = hipMemcpyAsync(host, recs, G * sizeof(TreeRec), hipMemcpyDeviceToHost, c->stream) == hipSuccess;
-    ok = ok && hipMemcpyAsync(host + G * sizeof(TreeRec), upper + 1, 32, hipMemcpyDeviceToHost, c->stream) == hipSuccess;
+    ok = ok && hipMemcpyAsync(host + G * sizeof(TreeRec), t.upper + 1, 32, hipMemcpyDeviceToHost, c->stream) == hipSuccess;
+    if (defer_slot) { if (!ok) S.fail(DST_ERR_HIP, "tree_exchange: read-back could not be queued"); return; }
     // the host waits here for everything queued before the root, kernels and exchanges: a bounded poll (a peer that never joined the
     // exchange would otherwise hold this rank for ever); on expiry the communicator is aborted and the rank returns DST_ERR_COMM
-    const int rw = ok ? ctx_sync(c, what == SH_TRACE_TREE ? "the root of the trace tree" : what == SH_CONSTRAINT_TREE ? "the root of the constraint tree" : "the root of a FRI tree") : DST_ERR_HIP;
+    const int rw = ok ? ctx_sync(c, (std::string("the root of the ") + t.name).c_str()) : DST_ERR_HIP;
     ok = ok && rw == DST_OK && hipGetLastError() == hipSuccess;
     c->shard_ms[1] += wall_ms() - t_wait;
     if (!ok) { const int code = rw ? rw : DST_ERR_HIP; S.fail(code, rw ? c->err : std::string("tree_exchange: root read-back failed")); S.agreed = S.agreed ? S.agreed : code; return; }
-    tree_exchange_finish(S, what, arg, host, payload_out, first_bad);
-    if (root) memcpy(root, host + G * sizeof(TreeRec), 32);
-}
-// the ranks' records and the root of a tree exchange, once they are on the host: first failing rank's code into S.agreed, else the root is filed
-void tree_exchange_finish(Sharded& S, uint32_t what, uint32_t arg, const uint8_t* slot, fe* payload_out, int64_t* first_bad) {
-    dst_ctx* c = S.c;
-    const size_t G = S.comm->world;
-    std::vector<TreeRec> all(G);
-    memcpy(all.data(), slot, G * sizeof(TreeRec));
-    const uint8_t* root = slot + G * sizeof(TreeRec);
-    std::vector<StatusRec> sts(G);
-    for (size_t g = 0; g < G; g++) sts[g] = all[g].st;
-    S.saw(sts.data(), what == SH_TRACE_TREE ? "trace tree" : what == SH_CONSTRAINT_TREE ? "constraint tree" : "FRI tree");
-    if (payload_out) for (int i = 0; i < 3; i++) payload_out[i] = all[0].st.payload[i];
-    if (first_bad) { *first_bad = -1; for (size_t g = 0; g < G; g++) if (all[g].st.rc == DST_OK && all[g].st.bad_step != ~0ull && (*first_bad < 0 || (int64_t)all[g].st.bad_step < *first_bad)) *first_bad = (int64_t)all[g].st.bad_step; }
-    if (S.agreed) return;
-    if (what == SH_TRACE_TREE) memcpy(c->trace_root, root, 32);
-    else if (what == SH_CONSTRAINT_TREE) memcpy(c->constraint_root, root, 32);
-    else step::fri_file_root(c, (int)arg, root);
+    tree_exchange_finish(S, t, host, payload_out, first_bad);
 }
 
 // steps 1-2 up to the rank-local tree levels.  Interpolation is split by COLUMNS: rank g interpolates the registers r = g (mod G); the
@@ -807,60 +779,149 @@ void commit_trace_columns(Sharded& S) {
     const size_t G = comm->world, W = c->W, n = c->n, rounds = (W + G - 1) / G;
     S.local([&]() -> int {
         if (!c->have_trace) { c->err = "dst_prove_sharded: no trace uploaded"; return DST_ERR_STATE; }
-        c->sharded_layout = true;
-        for (bool& b : c->tree_krange) b = false;
-        if (c->upload_pending) {
-            for (size_t g = 0; g + 1 < c->upload_bounds.size(); g++) HIP_TRY(c, hipStreamWaitEvent(c->stream, c->upload_done[g], 0));
-            c->upload_pending = false;
-        }
-        return DST_OK;
+        return begin_sharded_layout(c);
     });
-    // a stream-ordered transport runs the all-gathers on their own stream, ordered against the transforms by events
-    // (DISTAFF_SHARD_FORCE_OVERLAP=1: the same stream / event choreography over a blocking transport -- how the tests reach this path
-    // without several RCCL ranks)
-    const bool overlap = (comm->stream_ordered() || c->sw_flag("DISTAFF_SHARD_FORCE_OVERLAP")) && G > 1 && !c->sw_flag("DISTAFF_SHARD_NO_OVERLAP");
+    const bool overlap = S.side_stream();                      // the all-gathers of round k + 1 beside the extension of round k
     if (overlap) S.local([&]() -> int {
         if (!c->comm_stream) HIP_TRY(c, hipStreamCreateWithFlags(&c->comm_stream, hipStreamNonBlocking));
         while (c->comm_events.size() < 2 * rounds) { hipEvent_t e; HIP_TRY(c, hipEventCreateWithFlags(&e, hipEventDisableTiming)); c->comm_events.push_back(e); }
         return DST_OK;
     });
     const bool use_side = overlap && S.rc == DST_OK;
-    if (G == 1) {                                              // one rank: nothing to exchange, all registers in one pair of launches
-        S.local([&]() -> int {
-            k_intt_columns(c, c->trace, c->trace_stride, c->polys, W);
-            k_lde_columns(c, c->polys, c->lde, W);
-            if (c->sh_ev[1]) (void)hipEventRecord(c->sh_ev[1], c->stream);        // end of the extension (phase 0 | 1)
-            k_trace_leaves(c);
-            k_merkle(c, c->trace_leaves, c->trace_nodes, c->Bc * n, n);
-            return DST_OK;
-        });
-        return;
-    }
-    // interpolate the owned register of every round (a rank past the last register of the final round contributes an unused piece)
-    for (size_t k = 0; k < rounds; k++) {
-        const size_t col = k * G + comm->rank;
-        S.local([&]() -> int {
-            if (col < W) k_intt_columns(c, c->trace + col * c->trace_stride, c->trace_stride, c->polys + col * n, 1);
-            if (use_side) { HIP_TRY(c, hipEventRecord(c->comm_events[2 * k], c->stream)); HIP_TRY(c, hipStreamWaitEvent(c->comm_stream, c->comm_events[2 * k], 0)); }
-            return DST_OK;
-        });
-        if (use_side) {
-            if (!S.coll(S.coll_on(0, c->comm_stream, [&] { return comm->all_gather(c->polys + col * n, c->polys + k * G * n, n * sizeof(fe), c->comm_stream); }), "coefficient all-gather")) return;
-            S.local([&]() -> int { HIP_TRY(c, hipEventRecord(c->comm_events[2 * k + 1], c->comm_stream)); return DST_OK; });
+    if (G == 1) S.local([&] {                                  // one rank: nothing to exchange, all registers in one pair of launches
+        k_intt_columns(c, c->trace, c->trace_stride, c->polys, W);
+        k_lde_columns(c, c->polys, c->lde, W);
+    });
+    else {
+        // interpolate the owned register of every round (a rank past the last register of the final round contributes an unused piece)
+        for (size_t k = 0; k < rounds; k++) {
+            const size_t col = k * G + comm->rank;
+            S.local([&]() -> int {
+                if (col < W) k_intt_columns(c, c->trace + col * c->trace_stride, c->trace_stride, c->polys + col * n, 1);
+                if (use_side) { HIP_TRY(c, hipEventRecord(c->comm_events[2 * k], c->stream)); HIP_TRY(c, hipStreamWaitEvent(c->comm_stream, c->comm_events[2 * k], 0)); }
+                return DST_OK;
+            });
+            if (use_side) {
+                if (!S.coll(S.coll_on(0, c->comm_stream, [&] { return comm->all_gather(c->polys + col * n, c->polys + k * G * n, n * sizeof(fe), c->comm_stream); }), "coefficient all-gather")) return;
+                S.local([&]() -> int { HIP_TRY(c, hipEventRecord(c->comm_events[2 * k + 1], c->comm_stream)); return DST_OK; });
+            }
+        }
+        for (size_t k = 0; k < rounds; k++) {
+            const size_t first = k * G, cnt = first + G <= W ? G : W - first;
+            if (use_side) S.local([&]() -> int { HIP_TRY(c, hipStreamWaitEvent(c->stream, c->comm_events[2 * k + 1], 0)); return DST_OK; });
+            else if (!S.coll(S.coll_on(0, c->stream, [&] { return comm->all_gather(c->polys + (first + comm->rank) * n, c->polys + first * n, n * sizeof(fe), c->stream); }), "coefficient all-gather")) return;
+            S.local([&] { k_lde_columns(c, c->polys + first * n, c->lde + first * c->Bc * n, cnt); });
         }
     }
-    for (size_t k = 0; k < rounds; k++) {
-        const size_t first = k * G, cnt = first + G <= W ? G : W - first;
-        if (use_side) S.local([&]() -> int { HIP_TRY(c, hipStreamWaitEvent(c->stream, c->comm_events[2 * k + 1], 0)); return DST_OK; });
-        else if (!S.coll(S.coll_on(0, c->stream, [&] { return comm->all_gather(c->polys + (first + comm->rank) * n, c->polys + first * n, n * sizeof(fe), c->stream); }), "coefficient all-gather")) return;
-        S.local([&]() -> int { k_lde_columns(c, c->polys + first * n, c->lde + first * c->Bc * n, cnt); return DST_OK; });
-    }
     if (c->sh_ev[1]) (void)hipEventRecord(c->sh_ev[1], c->stream);        // end of the extension (phase 0 | 1)
-    S.local([&]() -> int {
+    S.local([&] {
         k_trace_leaves(c);
         k_merkle(c, c->trace_leaves, c->trace_nodes, c->Bc * n, n);
+    });
+}
+// steps 4-5 up to the rank-local tree levels: the transition evaluations of all ranks, then combination (replicated) and the extension over
+// the owned cosets
+void exchange_and_combine(Sharded& S) {
+    dst_ctx* c = S.c; dst_comm* comm = S.comm;
+    size_t bytes = 0;
+    if (dst_shard_export_size(c, SH_CEVAL, 0, &bytes) || bytes * comm->world > c->gather_bytes) { c->err = "dst_prove_sharded: gather buffer too small for the constraint evaluations"; S.agreed = DST_ERR_ARG; return; }   // the same on every rank
+    const size_t Q = c->Bc / (c->B / 8);
+    const void* send = dst_internal_boundary_by_evaluation(c) ? (const void*)c->ceval : (const void*)(c->ceval + 2 * Q * c->n);
+    const bool invert_first = !dst_internal_boundary_by_evaluation(c);
+    if (invert_first) S.local([&]() -> int {
+        // the size-n inverse transforms of this rank's evaluation cosets, before the exchange (in place through the scratch area)
+        fe* mine = c->ceval + 2 * Q * c->n; fe* work = c->cwork + 3 * 8 * c->n;
+        k_intt_cosets_local(c, mine, work, Q);
+        HIP_TRY(c, hipMemcpyAsync(mine, work, Q * c->n * sizeof(fe), hipMemcpyDeviceToDevice, c->stream));
         return DST_OK;
     });
+    // On the side stream the exchange runs while this rank writes the boundary combinations (they need nothing from other ranks);
+    // otherwise in sequence.  In boundary-by-evaluation mode part 1 reads the gathered arrays.
+    bool part1_done = false;
+    const bool side = S.side_stream() && invert_first && S.rc == DST_OK && c->comm_stream && c->comm_events.size() >= 2;
+    if (side) {
+        S.local([&]() -> int { HIP_TRY(c, hipEventRecord(c->comm_events[0], c->stream)); HIP_TRY(c, hipStreamWaitEvent(c->comm_stream, c->comm_events[0], 0)); return DST_OK; });
+        if (!S.coll(S.coll_on(3, c->comm_stream, [&] { return comm->all_gather(send, c->gather_buf, bytes, c->comm_stream); }), "constraint evaluations")) return;
+        S.local([&]() -> int { HIP_TRY(c, hipEventRecord(c->comm_events[1], c->comm_stream)); return DST_OK; });
+        S.local([&] { part1_done = true; return shard_combine_parts(c, 1); });
+        S.local([&]() -> int { HIP_TRY(c, hipStreamWaitEvent(c->stream, c->comm_events[1], 0)); return DST_OK; });
+    } else if (!S.coll(S.coll_on(3, c->stream, [&] { return comm->all_gather(send, c->gather_buf, bytes, c->stream); }), "constraint evaluations")) return;        // the import below rewrites `ceval` only after the exchange
+    S.local([&] { const int r = dst_shard_import(c, SH_CEVAL, 0, c->gather_buf, 1, nullptr); c->ceval_inverted = invert_first && r == DST_OK; return r; });
+    S.local([&] { return shard_combine_parts(c, part1_done ? 2 : 3); });       // records sh_ev[4] between the combination and the extension of its result
+}
+
+// step 7, the layers before rep_from: leaves + local levels | tree exchange with status | draw + fold.  chained: no host wait per layer --
+// x = prng(root) is drawn on the device from the replicated root (fri_draw_kernel) and the fold reads it there; the layers' records and
+// roots wait in fri_slot(d) for fri_replicated_tail_and_records.  Otherwise root read-back, host draw and status check per layer.
+uint8_t* fri_slot(dst_ctx* c, int d) { return c->h_stage + HS_FRI_SLOTS + (size_t)d * HS_FRI_SLOT_BYTES; }       // page-locked: G * 96 + 32 bytes per layer
+void fri_sharded_layers(Sharded& S, int rep_from, bool chained) {
+    dst_ctx* c = S.c;
+    fe* d_alpha = reinterpret_cast<fe*>(c->d_fri_chain + DST_MAX_FRI_LAYERS * 32);
+    digest* d_roots = reinterpret_cast<digest*>(c->d_fri_chain);
+    for (int d = 0; d < rep_from; d++) {
+        S.local([&]() -> int {
+            if (!c->composed || d != c->fri_committed || d != c->fri_folded) { c->err = "dst_prove_sharded: FRI layer out of order"; return DST_ERR_STATE; }
+            step::fri_shard_layer(c, d);
+            return DST_OK;
+        });
+        tree_exchange(S, SH_FRI_TREE, (uint32_t)d, nullptr, nullptr, nullptr, nullptr, chained ? fri_slot(c, d) : nullptr);
+        if (S.agreed) return;
+        if (chained) {
+            S.local([&] {
+                k_fri_draw_at(c, c->fri_upper[d], d_alpha + d, d_roots + d);
+                step::fri_shard_fold(c, d, fe_zero(), d_alpha + d);
+            });
+        } else S.local([&] { return fri_fold_from_root(c, c->fri_roots[d].data()); });
+    }
+}
+// ... and from rep_from on: one all-gather of the layer's evaluations, the rest of the commit phase on every rank; then the records the
+// chained layers left behind
+void fri_replicated_tail_and_records(Sharded& S, int rep_from, bool chained) {
+    dst_ctx* c = S.c; dst_comm* comm = S.comm;
+    const int d = rep_from;
+    const size_t bytes = c->Bc * fri_nd(c, d) * 16;
+    if (bytes * comm->world > c->gather_bytes) { c->err = "dst_prove_sharded: gather buffer too small for the FRI layer"; S.agreed = DST_ERR_ARG; return; }        // the same on every rank
+    // this rank's cosets of the layer (contiguous, coset-major) -> all cosets in the gather buffer -> natural order, then the rest
+    // of the commit phase on every rank (the natural-order layer overwrites fri_e[d] only after the exchange has completed)
+    if (!S.coll(S.coll_on(4, c->stream, [&] { return comm->all_gather(c->fri_e[d], c->gather_buf, bytes, c->stream); }), "FRI tail")) return;
+    S.local([&] { c->fri_tail_pending = true; return fri_replicated_tail(c, c->gather_buf, 1, nullptr); });
+    if (!chained || rep_from == 0) return;
+    // the deferred records of the sharded layers: everything queued has completed once the stream is idle (a rank that failed locally
+    // did not run the tail's own wait)
+    const double t_wait = wall_ms();
+    { const int rw = ctx_sync(c, "the FRI layers"); if (rw) { S.fail(rw, c->err); if (rw == DST_ERR_COMM) { S.agreed = rw; return; } } }
+    c->shard_ms[1] += wall_ms() - t_wait;
+    ShardTree t;
+    for (int l = 0; l < rep_from && !S.agreed; l++) if (shard_tree(c, SH_FRI_TREE, (uint32_t)l, &t) == DST_OK) tree_exchange_finish(S, t, fri_slot(c, l), nullptr, nullptr);
+}
+// step 9: every rank gathers what it owns; the lengths of the ranks' blobs and the blobs themselves are all-gathered, each with the rank's
+// status behind it, and every rank fills the same proof template.  Returns what dst_prove_sharded returns.
+int open_and_assemble(Sharded& S, const std::vector<uint64_t>& positions, uint64_t nonce, uint8_t* proof_out, size_t cap, size_t* proof_len) {
+    dst_ctx* c = S.c; dst_comm* comm = S.comm;
+    const size_t G = comm->world;
+    std::vector<uint64_t> lens(G, 0);
+    size_t mine = 0;
+    S.local([&] { return dst_shard_open(c, positions.data(), (uint32_t)positions.size(), nullptr, 0, &mine, lens.data()); });
+    {
+        struct LenRec { uint64_t len; int64_t rc; } rec{(uint64_t)mine, S.rc};
+        std::vector<LenRec> all(G);
+        if (!S.coll(S.coll_host([&] { return comm->all_gather_host(&rec, all.data(), sizeof(LenRec), c->stream); }), "openings")) return S.agreed;
+        S.saw("before the openings", [&](uint32_t g) { return all[g].rc; });
+        if (S.agreed) return S.agreed;
+        for (size_t g = 0; g < G; g++) lens[g] = all[g].len;            // every rank derives the same plan, so this equals what dst_shard_open computed locally
+    }
+    size_t width = 1;
+    for (uint64_t l : lens) if (l > width) width = (size_t)l;
+    std::vector<uint8_t> blob(width + 8, 0), all((width + 8) * G);
+    S.local([&] { return dst_shard_open(c, positions.data(), (uint32_t)positions.size(), blob.data(), width, &mine, nullptr); });
+    { const int64_t rc64 = S.rc; memcpy(blob.data() + width, &rc64, 8); }                    // the status rides behind the blob
+    if (!S.coll(S.coll_host([&] { return comm->all_gather_host(blob.data(), all.data(), width + 8, c->stream); }), "openings")) return S.agreed;
+    S.saw("openings", [&](uint32_t g) { int64_t rc64; memcpy(&rc64, all.data() + g * (width + 8) + width, 8); return rc64; });
+    if (S.agreed) return S.agreed;
+    std::vector<uint8_t> packed;
+    for (size_t g = 0; g < G; g++) packed.insert(packed.end(), all.begin() + g * (width + 8), all.begin() + g * (width + 8) + lens[g]);
+    // assembly is deterministic host work on identical inputs: it succeeds or fails on every rank alike
+    return dst_shard_assemble(c, positions.data(), (uint32_t)positions.size(), nonce, packed.data(), lens.data(), proof_out, cap, proof_len);
 }
 }  // namespace
 
@@ -883,7 +944,6 @@ int dst_prove_sharded(dst_ctx* c, dst_comm* comm, const dst_public* pub, uint8_t
     // from here on every host wait on this context's stream is the communicator's bounded poll (ctx_sync)
     struct WaitScope { dst_ctx* c; ~WaitScope() { c->wait_comm = nullptr; } } wait_scope{c};
     c->wait_comm = comm;
-    const size_t G = comm->world;
     double t0 = wall_ms();
     c->shard_ms[0] = c->shard_ms[1] = 0; c->shard_trees = 0;
     for (double& x : c->exchange_ms) x = 0;
@@ -900,14 +960,13 @@ int dst_prove_sharded(dst_ctx* c, dst_comm* comm, const dst_public* pub, uint8_t
     commit_trace_columns(S);                                    // records sh_ev[1] behind the last extension launch
     if (S.agreed) return S.agreed;                              // a collective itself failed
     const double t_commit = t0;
-    uint8_t trace_root[32], constraint_root[32];
     {
         // last state of the un-extended trace (op counter, program hash: evaluator.rs:37,73-74): rank 0 owns coset 0 of the extension,
         // which IS the trace; the three values ride with the status records
         const size_t stride = c->Bc * c->n;
         const fe* from[3] = {c->lde + (c->n - 1), c->lde + stride + (c->n - 1), c->lde + 2 * stride + (c->n - 1)};
         fe last[3];
-        tree_exchange(S, SH_TRACE_TREE, 0, trace_root, from, last);
+        tree_exchange(S, SH_TRACE_TREE, 0, from, last);
         if (S.agreed) return S.agreed;
         c->op_count = (uint64_t)fe_to_u128(last[0]); c->op_counter = last[0];
         c->program_hash[0] = last[1]; c->program_hash[1] = last[2];
@@ -923,44 +982,19 @@ int dst_prove_sharded(dst_ctx* c, dst_comm* comm, const dst_public* pub, uint8_t
     }
     // step 3
     std::vector<fe> coef(344);
-    prng_vector(trace_root, 344, coef.data());
+    prng_vector(c->trace_root, 344, coef.data());
     // the evaluation is queued; its verdict (first failing step of this rank's cosets, evaluator.rs:152-158) rides with the status records of the
     // constraint tree's exchange below instead of a host exchange and a wait of its own -- a trace that fails is reported one phase later
     const double t_eval = t0;
     if (timed) (void)hipEventRecord(c->sh_ev[2], c->stream);
     S.local([&] { return step::eval_constraints(c, pub, (const uint8_t*)coef.data(), nullptr, /*defer_check=*/true); });
     if (timed) (void)hipEventRecord(c->sh_ev[3], c->stream);
-    // steps 4-5: the transition evaluations of all ranks, then combination (replicated) and the constraint tree
-    {
-        size_t bytes = 0;
-        if (dst_shard_export_size(c, SH_CEVAL, 0, &bytes) || bytes * G > c->gather_bytes) { c->err = "dst_prove_sharded: gather buffer too small for the constraint evaluations"; return DST_ERR_ARG; }   // the same on every rank
-        const size_t Q = c->Bc / (c->B / 8);
-        const void* send = dst_internal_boundary_by_evaluation(c) ? (const void*)c->ceval : (const void*)(c->ceval + 2 * Q * c->n);
-        const bool invert_first = !dst_internal_boundary_by_evaluation(c);
-        if (invert_first) S.local([&]() -> int {
-            // the size-n inverse transforms of this rank's evaluation cosets, before the exchange (in place through the scratch area)
-            fe* mine = c->ceval + 2 * Q * c->n; fe* work = c->cwork + 3 * 8 * c->n;
-            k_intt_cosets_local(c, mine, work, Q);
-            HIP_TRY(c, hipMemcpyAsync(mine, work, Q * c->n * sizeof(fe), hipMemcpyDeviceToDevice, c->stream));
-            return DST_OK;
-        });
-        // On a stream-ordered transport the exchange runs on the collective stream while this rank writes the boundary combinations
-        // (they need nothing from other ranks); otherwise in sequence.  In boundary-by-evaluation mode part 1 reads the gathered arrays.
-        bool part1_done = false;
-        const bool side = (comm->stream_ordered() || c->sw_flag("DISTAFF_SHARD_FORCE_OVERLAP")) && G > 1 && invert_first && S.rc == DST_OK && c->comm_stream && c->comm_events.size() >= 2 && !c->sw_flag("DISTAFF_SHARD_NO_OVERLAP");
-        if (side) {
-            S.local([&]() -> int { HIP_TRY(c, hipEventRecord(c->comm_events[0], c->stream)); HIP_TRY(c, hipStreamWaitEvent(c->comm_stream, c->comm_events[0], 0)); return DST_OK; });
-            if (!S.coll(S.coll_on(3, c->comm_stream, [&] { return comm->all_gather(send, c->gather_buf, bytes, c->comm_stream); }), "constraint evaluations")) return S.agreed;
-            S.local([&]() -> int { HIP_TRY(c, hipEventRecord(c->comm_events[1], c->comm_stream)); return DST_OK; });
-            S.local([&] { part1_done = true; return shard_combine_parts(c, 1); });
-            S.local([&]() -> int { HIP_TRY(c, hipStreamWaitEvent(c->stream, c->comm_events[1], 0)); return DST_OK; });
-        } else if (!S.coll(S.coll_on(3, c->stream, [&] { return comm->all_gather(send, c->gather_buf, bytes, c->stream); }), "constraint evaluations")) return S.agreed;        // the import below rewrites `ceval` only after the exchange
-        S.local([&] { const int r = dst_shard_import(c, SH_CEVAL, 0, c->gather_buf, 1, nullptr); c->ceval_inverted = invert_first && r == DST_OK; return r; });
-        S.local([&] { return shard_combine_parts(c, part1_done ? 2 : 3); });       // records sh_ev[4] between the combination and the extension of its result
-    }
+    // steps 4-5, then the constraint tree
+    exchange_and_combine(S);                                    // records sh_ev[4] between the combination and the extension of its result
+    if (S.agreed) return S.agreed;
     {
         int64_t first_bad = -1;
-        tree_exchange(S, SH_CONSTRAINT_TREE, 0, constraint_root, nullptr, nullptr, c->d_u64, &first_bad);
+        tree_exchange(S, SH_CONSTRAINT_TREE, 0, nullptr, nullptr, c->d_u64, &first_bad);
         if (S.agreed) return S.agreed;
         if (first_bad >= 0) { c->err = "transition constraints were not satisfied at step " + std::to_string(first_bad); return DST_ERR_AIR; }
     }
@@ -976,96 +1010,28 @@ int dst_prove_sharded(dst_ctx* c, dst_comm* comm, const dst_public* pub, uint8_t
     }
     // step 6
     std::vector<fe> draws(516);
-    prng_vector(constraint_root, 516, draws.data());
+    prng_vector(c->constraint_root, 516, draws.data());
     std::vector<uint8_t> z1(c->W * 16), z2(c->W * 16);
     S.local([&] { return dst_compose(c, (const uint8_t*)draws.data(), z1.data(), z2.data()); });
     mark(5);
-    // step 7: sharded layers (leaves + local levels | tree exchange with status | draw + fold), then the replicated tail from one
-    // all-gather of evaluations.  fri_rep_from is fixed by the parameters: every rank walks the same layers.
+    // step 7.  fri_rep_from is fixed by the parameters: every rank walks the same layers.
     const int rep_from = c->gather_buf ? c->fri_rep_from : fri_replicated_from(c);
-    // Sharded layers.  chained (default): no host wait per layer -- x = prng(root) is drawn on the device from the replicated root
-    // (fri_draw_kernel) and the fold reads it there; the layers' records and roots are looked at once, after the tail.
-    // DISTAFF_FRI_CHAIN=0: root read-back, host draw and status check per layer (tests).
+    // DISTAFF_FRI_CHAIN=0 (tests): a host wait per sharded layer instead of the chained default
     const char* ce = c->sw("DISTAFF_FRI_CHAIN");
     const bool chained = !(ce && ce[0] == '0');
-    fe* d_alpha = reinterpret_cast<fe*>(c->d_fri_chain + DST_MAX_FRI_LAYERS * 32);
-    digest* d_roots = reinterpret_cast<digest*>(c->d_fri_chain);
-    auto slot_of = [&](int d) { return c->h_stage + HS_FRI_SLOTS + (size_t)d * HS_FRI_SLOT_BYTES; };       // page-locked: G * 96 + 32 bytes per layer
-    for (int d = 0; d < rep_from; d++) {
-        S.local([&]() -> int {
-            if (!c->composed || d != c->fri_committed || d != c->fri_folded) { c->err = "dst_prove_sharded: FRI layer out of order"; return DST_ERR_STATE; }
-            step::fri_shard_layer(c, d);
-            return DST_OK;
-        });
-        uint8_t root[32];
-        tree_exchange(S, SH_FRI_TREE, (uint32_t)d, root, nullptr, nullptr, nullptr, nullptr, chained ? slot_of(d) : nullptr);
-        if (S.agreed) return S.agreed;
-        if (chained) {
-            S.local([&]() -> int {
-                k_fri_draw_at(c, c->fri_upper[d], d_alpha + d, d_roots + d);
-                step::fri_shard_fold(c, d, fe_zero(), d_alpha + d);
-                return DST_OK;
-            });
-        } else {
-            fe x;
-            prng_vector(root, 1, &x);                                 // fri/prover.rs:40 field::prng(root)
-            S.local([&] { return dst_shard_fri_fold(c, (const uint8_t*)&x); });
-        }
-    }
-    {
-        const int d = rep_from;
-        const size_t bytes = c->Bc * fri_nd(c, d) * 16;
-        if (bytes * G > c->gather_bytes) { c->err = "dst_prove_sharded: gather buffer too small for the FRI layer"; return DST_ERR_ARG; }        // the same on every rank
-        // this rank's cosets of the layer (contiguous, coset-major) -> all cosets in the gather buffer -> natural order, then the rest
-        // of the commit phase on every rank (the natural-order layer overwrites fri_e[d] only after the exchange has completed)
-        uint8_t root[32];
-        if (!S.coll(S.coll_on(4, c->stream, [&] { return comm->all_gather(c->fri_e[d], c->gather_buf, bytes, c->stream); }), "FRI tail")) return S.agreed;
-        S.local([&] { c->fri_tail_pending = true; return fri_replicated_tail(c, c->gather_buf, 1, root); });
-    }
-    if (chained && rep_from > 0) {
-        // the deferred records of the sharded layers: everything queued has completed once the stream is idle (a rank that failed locally
-        // did not run the tail's own wait)
-        const double t_wait = wall_ms();
-        { const int rw = ctx_sync(c, "the FRI layers"); if (rw) { S.fail(rw, c->err); if (rw == DST_ERR_COMM) return rw; } }
-        c->shard_ms[1] += wall_ms() - t_wait;
-        for (int d = 0; d < rep_from && !S.agreed; d++) tree_exchange_finish(S, SH_FRI_TREE, (uint32_t)d, slot_of(d), nullptr, nullptr);
-        if (S.agreed) return S.agreed;
-    }
+    fri_sharded_layers(S, rep_from, chained);
+    if (S.agreed) return S.agreed;
+    fri_replicated_tail_and_records(S, rep_from, chained);
+    if (S.agreed) return S.agreed;
     mark(6);
     // step 8 (replicated: every rank grinds the same seed and finds the same first nonce)
     uint64_t nonce = 0;
     std::vector<uint64_t> positions;
     S.local([&] { return step::query_seed(c, &nonce, positions); });
     mark(7);
-    // step 9: the lengths of the ranks' opening blobs travel with their status
-    std::vector<uint64_t> lens(G, 0);
-    size_t mine = 0;
-    S.local([&] { return dst_shard_open(c, positions.data(), (uint32_t)positions.size(), nullptr, 0, &mine, lens.data()); });
-    {
-        struct LenRec { uint64_t len; int64_t rc; } rec{(uint64_t)mine, S.rc};
-        std::vector<LenRec> all(G);
-        if (!S.coll(S.coll_host([&] { return comm->all_gather_host(&rec, all.data(), sizeof(LenRec), c->stream); }), "openings")) return S.agreed;
-        for (size_t g = 0; g < G; g++) {
-            if (all[g].rc != DST_OK && S.agreed == DST_OK) { S.agreed = (int)all[g].rc; if (S.rc == DST_OK) c->err = "before the openings: rank " + std::to_string(g) + " reported error " + std::to_string(all[g].rc); }
-            lens[g] = all[g].len;            // every rank derives the same plan, so this equals what dst_shard_open computed locally
-        }
-        if (S.agreed) return S.agreed;
-    }
-    size_t width = 1;
-    for (uint64_t l : lens) if (l > width) width = (size_t)l;
-    std::vector<uint8_t> blob(width + 8, 0), all(( width + 8) * G);
-    S.local([&] { return dst_shard_open(c, positions.data(), (uint32_t)positions.size(), blob.data(), width, &mine, nullptr); });
-    { const int64_t rc64 = S.rc; memcpy(blob.data() + width, &rc64, 8); }                    // the status rides behind the blob
-    if (!S.coll(S.coll_host([&] { return comm->all_gather_host(blob.data(), all.data(), width + 8, c->stream); }), "openings")) return S.agreed;
-    for (size_t g = 0; g < G && S.agreed == DST_OK; g++) {
-        int64_t rc64; memcpy(&rc64, all.data() + g * (width + 8) + width, 8);
-        if (rc64 != DST_OK) { S.agreed = (int)rc64; if (S.rc == DST_OK) c->err = "openings: rank " + std::to_string(g) + " reported error " + std::to_string(rc64); }
-    }
+    // step 9
+    const int rc = open_and_assemble(S, positions, nonce, proof_out, cap, proof_len);
     if (S.agreed) return S.agreed;
-    std::vector<uint8_t> packed;
-    for (size_t g = 0; g < G; g++) packed.insert(packed.end(), all.begin() + g * (width + 8), all.begin() + g * (width + 8) + lens[g]);
-    // assembly is deterministic host work on identical inputs: it succeeds or fails on every rank alike
-    const int rc = dst_shard_assemble(c, positions.data(), (uint32_t)positions.size(), nonce, packed.data(), lens.data(), proof_out, cap, proof_len);
     mark(8);
     S.read_collective_events();                                 // everything queued has completed: the last exchange was waited for
     return rc;

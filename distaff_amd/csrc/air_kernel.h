@@ -11,7 +11,8 @@
 // cf bit 1, SWAP aggregates both constraints into slot 0, PUSH/ASSERT flag adjustments.
 //
 // The header in reading order: arguments; what a launch evaluates (AS_*, AG_*, AF_*, air_stack); the two rows and the flags of a point;
-// one function per constraint section; the kernel, which calls them in turn; launch_air.  The two statements of the user-stack
+// one function per constraint section; the kernel, which calls them in turn; the check of the trace rows (air_check_kernel), which calls them
+// with an accumulator that only asks for zero; launch_air and the two walks of an instance set's launch list.  The two statements of the user-stack
 // constraints have their own headers: air_stack_nested.h (product) and air_stack_perop.h (test build).
 //
 // Data access: with the coset-major LDE a point is (coset jl, index k); rows i and i+B are (jl,k) and (jl,k+1 mod n),
@@ -555,6 +556,13 @@ __global__ void __launch_bounds__(AIR_THREADS, AIR_WAVES_PER_SIMD) air_kernel(Ai
     air_load_rows<ST.sl>(rows, o, nw, a, cols, sd);
     if constexpr ((SECT & AS_BOUNDARY) != 0) air_boundary<CL, LL>(a, rows, o, cl, ll, gi, n64, nmask, ql, k);
     if constexpr (SECT == AS_BOUNDARY) return;              // a boundary-only launch neither reads nor writes the partial sums
+    // Coset 0 is the trace itself: the transition value of its rows is zero by definition except at the last one (air_combine), and
+    // whether their constraints vanish is air_check_kernel's question (below), not this kernel's.  Nothing reads the partial sums or
+    // partial stack values of these points.
+    if (qg == 0 && k + 1 != a.n) {
+        if constexpr (LAST) a.out[((size_t)2 * gridDim.y + ql) * a.n + k] = fe_zero();
+        return;
+    }
     AirFlags flags;
     air_op_flags(flags, rows);
     const fe* per = a.periodic + (size_t)(step & 127u) * AIR_PERIODIC_STRIDE;
@@ -579,8 +587,6 @@ __global__ void __launch_bounds__(AIR_THREADS, AIR_WAVES_PER_SIMD) air_kernel(Ai
     // degree-group sums the launch moves: op bits {2,3,4,6,8}, sponge {6,7}, loop image / context / loop stacks {4}, stack {7}
     constexpr bool EMITS_STACK = (SECT & AS_STACK_ANY) != 0 || (GROUPS & AG_DEEP) != 0 || ((GROUPS & AG_STACK_ALL) != 0 && !EV_OUT);
     constexpr uint32_t USED = ((SECT & AS_OP_BITS) ? 0x2Fu : 0u) | ((SECT & AS_SPONGE) ? 0x18u : 0u) | ((SECT & AS_FLOW) ? 0x04u : 0u) | (EMITS_STACK ? 0x10u : 0u);
-    const bool on_trace = (qg == 0);
-    if (on_trace && k + 1 != a.n && acc.nonzero) atomicMin(a.bad_step, (unsigned long long)k);      // evaluator.rs:152-158
     // hand-over: the partial sums of the previous launches join at the end (they are not live during the evaluation); a launch only
     // moves the degree-group sums its sections emit into.  (Stated here and not in a function of its own: there the index arithmetic
     // of the partial sums compiled to other instructions, profiles/air_layer.md.)
@@ -601,6 +607,59 @@ __global__ void __launch_bounds__(AIR_THREADS, AIR_WAVES_PER_SIMD) air_kernel(Ai
     air_combine(acc.res, acc.adj, a, k, ql, qg, gi, n64, nmask);
 }
 
+// ---- the check of the trace rows (evaluator.rs:152-158): one lane per row of the trace ----------------------------------------------------
+// On the trace itself every transition constraint must vanish between rows k and k + 1, k < n - 1; the first k where one does not is
+// the failing step.  The verdict depends on the trace alone -- no coefficient enters it -- so it is a chain of launches of its own that
+// may run beside anything that leaves the trace alone: the same sections, called with an accumulator that only asks whether a value
+// is zero.  The stack launches hand their partial values on exactly like air_kernel's (AF_EV_IN / AF_EV_OUT), through arrays of the
+// chain's own (AirArgs::ev, n elements each), and the launch that completes a constraint judges it.  Of AirArgs the chain reads lde,
+// periodic, consts, ev, bad_step and the shape; AF_FIRST / AF_LAST name the instance and nothing else.
+struct AirCheckAcc {
+    bool nonzero;
+    __device__ __forceinline__ void emit(uint32_t, int, const fe& d) { nonzero |= !fe_is_zero(d); }
+};
+
+template <int CL, int LL, int SD, int SLCAP, int SECT, uint32_t GROUPS, int FLAGS>
+__global__ void __launch_bounds__(AIR_THREADS, AIR_WAVES_PER_SIMD) air_check_kernel(AirArgs a) {
+    constexpr AirStack ST = air_stack(SD, SLCAP);
+    constexpr bool EV_IN = (FLAGS & AF_EV_IN) != 0, EV_OUT = (FLAGS & AF_EV_OUT) != 0;
+    static_assert(ST.nested ? (SECT & AS_STACK_ANY) == 0 : (GROUPS == 0 && !EV_IN && !EV_OUT),
+                  "nested-sum instances select stack operations with GROUPS, the per-operation instance with SECT");
+    static_assert((SECT & AS_BOUNDARY) == 0, "the boundary combinations are no part of the check");
+    const int cl = (int)a.cl, ll = (int)a.ll;
+    const int sl = SD ? ST.sl : (int)a.sl;
+    const int sd = SD ? SD : (int)a.stack_depth;
+    const size_t k = (size_t)blockIdx.x * AIR_THREADS + threadIdx.x;
+    if (k + 1 >= a.n) return;                               // the step from the last row to the first is no step of the program
+    const AirColumns cols{a.lde + k, a.lde + k + 1, a.col_stride};                  // coset 0 of the extension: rows k and k + 1 of the trace
+
+    AirRows<CL, LL> rows;
+    fe o[ST.sl], nw[ST.sl];
+    air_load_rows<ST.sl>(rows, o, nw, a, cols, sd);
+    AirFlags flags;
+    air_op_flags(flags, rows);
+    const fe* per = a.periodic + (size_t)(((uint32_t)k << 3) & 127u) * AIR_PERIODIC_STRIDE;     // step 8 k of the 8n evaluation domain
+
+    AirCheckAcc acc; acc.nonzero = false;
+    if constexpr ((SECT & AS_OP_BITS) != 0) air_op_bits(acc, rows, flags, per);
+    if constexpr ((SECT & AS_SPONGE) != 0) air_sponge<SD == 0>(acc, a, cols, rows, nw, flags, per);
+    if constexpr ((SECT & AS_FLOW) != 0) air_flow<CL, LL>(acc, a, cols, rows, flags, cl, ll);
+    if constexpr (ST.nested && (GROUPS & AG_STACK_ALL & ~AG_DEEP) != 0) air_stack_nested<SD, ST.deep, ST.slots, ST.sl, GROUPS, EV_IN, EV_OUT>(acc, a, rows, o, nw, flags, per, cl, ll, sl, sd, k);
+    if constexpr (!ST.nested && (SECT & AS_STACK_ANY) != 0) air_stack_per_operation<ST.sl, SECT>(acc, o, nw, sl, sd, 20 + cl + ll, flags, per, a.consts);
+    if constexpr (ST.deep && (GROUPS & AG_DEEP) != 0) air_stack_deep_slots(acc, a, cols, flags, cl, ll, sl, sd);
+    if (acc.nonzero) atomicMin(a.bad_step, (unsigned long long)k);
+}
+
+template <int CL, int LL, int SD, int SLCAP, int SECT, uint32_t GROUPS, int FLAGS>
+static void launch_air_check(dst_ctx* c, const AirArgs& a, hipStream_t stream) {
+    dim3 g((unsigned)((c->n + AIR_THREADS - 1) / AIR_THREADS), 1);
+    static char name[64];
+    if (!name[0]) snprintf(name, sizeof(name), "air_check<%d,%d,%d,%d,%d,%u,%d>", CL, LL, SD, SLCAP, SECT, (unsigned)GROUPS, FLAGS);
+    // algorithmic bytes: the W registers of a row, the stack partial values that come in and go out
+    constexpr int NS = air_stack(SD, SLCAP).partials;
+    const double units = c->W + ((FLAGS & AF_EV_IN) ? NS : 0) + ((FLAGS & AF_EV_OUT) ? NS : 0);
+    { KScope ks_(c, name, 16.0 * c->n * units, true, 0.0, stream); hipLaunchKernelGGL((air_check_kernel<CL, LL, SD, SLCAP, SECT, GROUPS, FLAGS>), g, dim3(AIR_THREADS), 0, stream, a); }
+}
 
 template <int CL, int LL, int SD, int SLCAP, int SECT, uint32_t GROUPS, int FLAGS>
 static void launch_air(dst_ctx* c, const AirArgs& a, uint32_t Q) {
@@ -620,8 +679,24 @@ static void launch_air_boundary(dst_ctx* c, const AirArgs& a, uint32_t Q) {
     if (dst_internal_boundary_by_evaluation(c)) launch_air<CL, LL, SD, SLCAP, AS_BOUNDARY, 0, 0>(c, a, Q);
 #endif
 }
+// The launches of an instance set are stated once (air_chain_* in the set's unit) and walked twice: by AirEvalChain, which launches
+// air_kernel over the Q local evaluation cosets, and by AirCheckChain, which launches air_check_kernel over the trace rows.
+struct AirEvalChain {
+    dst_ctx* c; const AirArgs& a; uint32_t Q;
+    template <int CL, int LL, int SD, int SLCAP, int SECT, uint32_t GROUPS, int FLAGS> void run() const { launch_air<CL, LL, SD, SLCAP, SECT, GROUPS, FLAGS>(c, a, Q); }
+    template <int CL, int LL, int SD, int SLCAP> void boundary() const { launch_air_boundary<CL, LL, SD, SLCAP>(c, a, Q); }
+};
+struct AirCheckChain {
+    dst_ctx* c; const AirArgs& a; hipStream_t stream;
+    template <int CL, int LL, int SD, int SLCAP, int SECT, uint32_t GROUPS, int FLAGS> void run() const { launch_air_check<CL, LL, SD, SLCAP, SECT, GROUPS, FLAGS>(c, a, stream); }
+    template <int CL, int LL, int SD, int SLCAP> void boundary() const {}
+};
 // instances live in their own translation units (compile time): Fibonacci shape, small stacks, fully generic
 void air_launch_sd4(dst_ctx* c, const AirArgs& a, uint32_t Q);      // cl <= 2, ll <= 1, stack_depth == 4
 void air_launch_small(dst_ctx* c, const AirArgs& a, uint32_t Q);    // cl <= 2, ll <= 1, stack_depth <= 8
 void air_launch_deep(dst_ctx* c, const AirArgs& a, uint32_t Q);     // anything the VM can produce, nested sums + flag sums for slots >= 8
 void air_launch_generic(dst_ctx* c, const AirArgs& a, uint32_t Q);  // anything the VM can produce, per-operation formulation (DISTAFF_AIR=generic)
+// the check chains of the same sets (a.ev: the chain's own arrays), queued on `stream`
+void air_check_sd4(dst_ctx* c, const AirArgs& a, hipStream_t stream);
+void air_check_small(dst_ctx* c, const AirArgs& a, hipStream_t stream);
+void air_check_deep(dst_ctx* c, const AirArgs& a, hipStream_t stream);      // also behind the per-operation set (kernels_air.hip k_air_check)

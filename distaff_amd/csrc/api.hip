@@ -66,6 +66,9 @@ static void free_all(dst_ctx* c) {
         if (c->fri_leaves[d]) hipFree(c->fri_leaves[d]);
         if (c->fri_nodes[d]) hipFree(c->fri_nodes[d]);
     }
+    if (c->check_partials) hipFree(c->check_partials);
+    if (c->check_ev) hipEventDestroy(c->check_ev);
+    if (c->check_stream) hipStreamDestroy(c->check_stream);
     for (hipEvent_t e : c->upload_done) hipEventDestroy(e);
     if (c->upload_stream) hipStreamDestroy(c->upload_stream);
     for (hipEvent_t e : c->comm_events) hipEventDestroy(e);
@@ -145,6 +148,7 @@ static int ctx_init(dst_ctx* c) {
     if ((r = dev_alloc(c, &c->trace_nodes, Nl))) return r;
     if ((r = dev_alloc(c, &c->ceval, 3 * 8 * n))) return r;
     if ((r = dev_alloc(c, &c->cwork, 8 * 8 * n))) return r;
+    if (c->j0 == 0 && (r = dev_alloc(c, &c->check_partials, k_air_check_partials(c) * n))) return r;     // the owner of coset 0 checks the trace rows (kernels_air.hip k_air_check)
     if ((r = dev_alloc(c, &c->cpoly, 8 * n))) return r;
     if ((r = dev_alloc(c, &c->cevals, Nl))) return r;
     if ((r = dev_alloc(c, &c->cnodes, Nl / 2))) return r;
@@ -176,8 +180,10 @@ static int ctx_init(dst_ctx* c) {
 static const fe* as_fe(const uint8_t* p) { return reinterpret_cast<const fe*>(p); }
 static std::vector<fe> copy_fe(const uint8_t* p, size_t count) { std::vector<fe> v(count); memcpy(v.data(), p, count * 16); return v; }
 
-// an asynchronous upload still in flight writes the same buffer from upload_stream: drain it before another upload starts
+// an asynchronous upload still in flight writes the same buffer from upload_stream: drain it before another upload starts.  So does
+// whatever else may still touch the trace buffer beside the main stream.
 static int drain_pending_upload(dst_ctx* c) {
+    { const int r = k_air_check_drain(c); if (r) return r; }    // a check of the trace rows on the side stream still reads that buffer
     if (c->upload_pending && c->upload_stream) HIP_TRY(c, hipStreamSynchronize(c->upload_stream));
     c->upload_pending = false;
     return DST_OK;
@@ -196,7 +202,8 @@ int dst_ctx_create(const dst_params* params, dst_ctx** out) {
     *out = c;
     return DST_OK;
 }
-void dst_ctx_destroy(dst_ctx* c) { if (!c) return; hipSetDevice(c->device); free_all(c); delete c; }
+void dst_ctx_destroy(dst_ctx* c) { if (!c) return; hipSetDevice(c->device); (void)k_air_check_drain(c); free_all(c); delete c; }
+int64_t dst_last_bad_step(const dst_ctx* c) { return (!c || c->air_flag_host == ~0ull) ? -1 : (int64_t)c->air_flag_host; }
 const char* dst_last_error(const dst_ctx* c) { return c ? c->err.c_str() : g_create_error.c_str(); }
 int dst_phase_ms(const dst_ctx* c, double out_ms[9]) { if (!c || !out_ms) return DST_ERR_ARG; for (int i = 0; i < 9; i++) out_ms[i] = c->phase_ms[i]; return DST_OK; }
 
@@ -317,7 +324,12 @@ int dst_commit_trace(dst_ctx* c, uint8_t trace_root[32]) {
 
 // ---- steps 3-5 ------------------------------------------------------------------------------------------------------------------
 // (the evaluation and combine_polys are stated in host/steps_impl.h, for this driver and the sharded ones)
+static int eval_constraints_phase(dst_ctx* c, const dst_public* pub, const uint8_t* coeffs, uint8_t constraint_root[32], int64_t* bad_step, bool check_here);
 int dst_eval_constraints(dst_ctx* c, const dst_public* pub, const uint8_t* coeffs, uint8_t constraint_root[32], int64_t* bad_step) {
+    return eval_constraints_phase(c, pub, coeffs, constraint_root, bad_step, true);
+}
+// check_here = false (dst_prove): the check of the trace rows is queued by the caller, who also reports its verdict
+static int eval_constraints_phase(dst_ctx* c, const dst_public* pub, const uint8_t* coeffs, uint8_t constraint_root[32], int64_t* bad_step, bool check_here) {
     if (!c || !pub || !coeffs || !constraint_root) return DST_ERR_ARG;
     if (!c->committed) { c->err = "dst_eval_constraints: trace not committed"; return DST_ERR_STATE; }
     if (pub->num_inputs > 8 || pub->num_outputs > 8) { c->err = "too many public inputs / outputs"; return DST_ERR_ARG; }
@@ -328,7 +340,7 @@ int dst_eval_constraints(dst_ctx* c, const dst_public* pub, const uint8_t* coeff
     // The host does not wait for the evaluation's verdict (evaluator.rs:152-158) before it queues the combination: the flag travels back
     // with the constraint root, and a trace that fails is reported then (the work queued behind it is wasted only in that case).
     const bool steps = dst_internal_combine_by_steps(c);
-    int r = step::eval_constraints(c, pub, coeffs, bad_step, /*defer_check=*/!steps);
+    int r = step::eval_constraints(c, pub, coeffs, bad_step, /*defer_check=*/!steps, check_here);
     if (r != DST_OK) return r;
     HIP_TRY(c, hipEventRecord(c->ph_ev[1], c->stream));
     if ((r = step::combine(c, 3))) return r;
@@ -340,7 +352,7 @@ int dst_eval_constraints(dst_ctx* c, const dst_public* pub, const uint8_t* coeff
     HIP_TRY(c, hipEventRecord(c->ph_ev[3], c->stream));
     HIP_TRY(c, hipStreamSynchronize(c->stream));
     HIP_TRY(c, hipGetLastError());
-    if (!steps) {
+    if (!steps && check_here) {
         c->air_flag_host = *reinterpret_cast<unsigned long long*>(c->h_stage + HS_AIR_FLAG);
         if ((r = k_constraint_check(c, bad_step)) != DST_OK) { c->err = "transition constraints were not satisfied"; return r; }
     }
@@ -525,21 +537,48 @@ static int fri_commit_all(dst_ctx* c, bool chained) {
 }
 
 // ---- the whole prover -----------------------------------------------------------------------------------------------------------
+// Where dst_prove queues the check of the trace rows (DISTAFF_AIR_CHECK, test build; the product library runs the default).  The verdict
+// depends on the trace alone and nothing of the proof waits for it, so it need not stand on the main stream in the middle of the
+// VALU-bound evaluation: on the side stream it runs beside the serial tail of the proof -- the small FRI layers, the proof of work, the
+// openings -- where most of the device is idle.  profiles/air_trace_check.md has the measurements behind the default.
+enum AirCheckPlace { AIR_CHECK_INLINE, AIR_CHECK_TRACE, AIR_CHECK_FRI, AIR_CHECK_POW, AIR_CHECK_OPEN };
+static AirCheckPlace air_check_place(const dst_ctx* c) {
+    if (c->sw_is("DISTAFF_AIR_CHECK", "inline")) return AIR_CHECK_INLINE;
+    if (c->sw_is("DISTAFF_AIR_CHECK", "trace")) return AIR_CHECK_TRACE;
+    if (c->sw_is("DISTAFF_AIR_CHECK", "fri")) return AIR_CHECK_FRI;
+    if (c->sw_is("DISTAFF_AIR_CHECK", "open")) return AIR_CHECK_OPEN;
+    return AIR_CHECK_POW;
+}
+static int prove_impl(dst_ctx* c, const dst_public* pub, uint8_t* proof_out, size_t cap, size_t* proof_len);
 int dst_prove(dst_ctx* c, const dst_public* pub, uint8_t* proof_out, size_t cap, size_t* proof_len) {
     if (!c || !pub || !proof_len) return DST_ERR_ARG;
+    int rc = prove_impl(c, pub, proof_out, cap, proof_len);
+    // a check chain on the side stream: waited for on every path out of the proof, reported when nothing else failed first
+    const bool aside = c->check_pending;
+    const double t0 = wall_ms();
+    const int rd = k_air_check_drain(c);
+    if (aside) c->phase_ms[8] += wall_ms() - t0;
+    if (rc == DST_OK && rd != DST_OK) rc = rd;
+    if (rc == DST_OK && aside && k_constraint_check(c, nullptr) != DST_OK) { c->err = "transition constraints were not satisfied"; *proof_len = 0; rc = DST_ERR_AIR; }
+    return rc;
+}
+static int prove_impl(dst_ctx* c, const dst_public* pub, uint8_t* proof_out, size_t cap, size_t* proof_len) {
     int rc;
     uint8_t trace_root[32], constraint_root[32];
+    const AirCheckPlace place = air_check_place(c);
     if ((rc = dst_commit_trace(c, trace_root))) return rc;
+    if (place == AIR_CHECK_TRACE && (rc = k_air_check_side(c))) return rc;          // the trace is all the check reads
     std::vector<fe> coef(344);
     prng_vector(trace_root, 344, coef.data());                   // ConstraintCoefficients::new (coefficients.rs:66)
     int64_t bad = -1;
-    if ((rc = dst_eval_constraints(c, pub, (const uint8_t*)coef.data(), constraint_root, &bad))) return rc;
+    if ((rc = eval_constraints_phase(c, pub, (const uint8_t*)coef.data(), constraint_root, &bad, /*check_here=*/place == AIR_CHECK_INLINE))) return rc;
     std::vector<fe> draws(516);
     prng_vector(constraint_root, 516, draws.data());             // z = draw 0; CompositionCoefficients (coefficients.rs:82)
     // the DEEP values are not needed before the openings: the host queues the composition and goes on to the first FRI layer
     std::vector<uint8_t> z1(c->W * 16), z2(c->W * 16);
     const double t_compose = wall_ms();
     if ((rc = compose_impl(c, (const uint8_t*)draws.data(), z1.data(), z2.data(), false))) return rc;
+    if (place == AIR_CHECK_FRI && (rc = k_air_check_side(c))) return rc;            // behind the composition, beside the commit phase that is queued next
     {
         const char* ce = c->sw("DISTAFF_FRI_CHAIN");
         if ((rc = fri_commit_all(c, !(ce && ce[0] == '0')))) return rc;
@@ -548,11 +587,14 @@ int dst_prove(dst_ctx* c, const dst_public* pub, uint8_t* proof_out, size_t cap,
         if (dev > 0 && dev < both) { c->phase_ms[5] = dev; c->phase_ms[6] = both - dev; }
         else { c->phase_ms[6] = both > c->phase_ms[5] ? both - c->phase_ms[5] : 0.0; }
     }
+    // the commit phase has been waited for: from here to the gather of the openings the device has the proof-of-work search and nothing else
+    if (place == AIR_CHECK_POW && (rc = k_air_check_side(c))) return rc;
     double t0 = wall_ms();
     uint64_t nonce = 0;
     std::vector<uint64_t> positions;
     if ((rc = step::query_seed(c, &nonce, positions))) return rc;
     c->phase_ms[7] = wall_ms() - t0;
+    if (place == AIR_CHECK_OPEN && (rc = k_air_check_side(c))) return rc;           // beside the host's opening plan
     return dst_build_proof(c, positions.data(), (uint32_t)positions.size(), nonce, proof_out, cap, proof_len);
 }
 

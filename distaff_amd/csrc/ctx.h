@@ -54,6 +54,7 @@ static const dst_switch_def DST_SWITCHES[] = {
     {"DISTAFF_LOCAL_TRANSPORT",    true,  "blocking",        "in-process transport (dst_comm_init_local, dst_prove_sharded_local): drain every rank's stream around each collective instead of the stream-ordered form (events between the ranks' streams, nothing waited for)"},
     {"DISTAFF_TMP_REGS",           true,  "4..W",            "registers per transform launch = size of the staging array (default: as many as 12 GiB hold, at most W)"},
     {"DISTAFF_AIR",                false, "small|deep|generic", "force a more general constraint-kernel instance set than the trace shape needs (generic = per-operation formulation)"},
+    {"DISTAFF_AIR_CHECK",          false, "inline|trace|fri|pow|open", "dst_prove: where the check of the trace rows is queued -- inline: on the main stream behind the evaluation; else on the low-priority side stream, from the end of the trace commitment on (trace), from the first FRI layer on (fri), from the proof of work on (pow), from the openings on (open)"},
     {"DISTAFF_BOUNDARY",           false, "eval",            "boundary combinations by evaluation on the 8n domain (the reference's route) instead of coefficient form"},
     {"DISTAFF_COMBINE",            false, "steps",           "combine_polys / DEEP composition as the reference's sequence of whole-array steps instead of the fused passes"},
     {"DISTAFF_NTT",                false, "pre|pre_a|3pass|reg|lds|row", "force a transform plan family (pre_a: a register pre-stage in the first pass only; row: the default plan with row-major staging array and tables)"},
@@ -243,6 +244,14 @@ struct dst_ctx {
     uint8_t *d_fri_chain = nullptr;                   // dst_prove's FRI commit phase without host round trips: [24] roots (32 B) then [24] draws (16 B)
     uint8_t *h_stage = nullptr;                       // page-locked host staging (HS_TOTAL bytes, layout HS_* above): small uploads / read-backs that must not make the host wait
     unsigned long long air_flag_host = ~0ull;         // read-back of the AIR failure flag (deferred check)
+    // The check of the trace rows (air_kernel.h air_check_kernel) beside the proof's later phases: dst_prove queues it on a stream of the
+    // lowest priority behind an event of the main stream; the partial stack values of the chain have arrays of their own (nothing else
+    // writes them).  While check_pending, the side stream may still READ the trace (coset 0 of `lde`): whoever writes or frees that buffer
+    // drains it first (k_air_check_drain).
+    hipStream_t check_stream = nullptr;
+    hipEvent_t check_ev = nullptr;
+    fe *check_partials = nullptr;                     // [k_air_check_partials][n]: 6 arrays for the depth-4 set (96 MiB at n = 2^20), 10 otherwise
+    bool check_pending = false;
     hipEvent_t ph_ev[6] = {nullptr};                  // phase boundaries on the stream (phase times without host waits)
     uint8_t *d_stage = nullptr;                       // staging buffer for gathers
     size_t stage_bytes = 0;
@@ -297,16 +306,18 @@ struct dst_ctx {
 // multiply-adds (v_mad_u64_u32) the launch executes per the kernel's arithmetic (0 where not counted)
 struct KScope {
     dst_ctx* c; bool on;
+    hipStream_t s;                         // the stream the launch goes to: the context's, unless the caller names another (the check chain's)
     dst_ctx::KEvent ev;
-    KScope(dst_ctx* ctx, const char* name, double bytes, bool heavy = false, double mads = 0.0) : c(ctx), on(ctx->profile == 1 || (ctx->profile == 2 && heavy)) {
+    KScope(dst_ctx* ctx, const char* name, double bytes, bool heavy = false, double mads = 0.0, hipStream_t stream = nullptr)
+        : c(ctx), on(ctx->profile == 1 || (ctx->profile == 2 && heavy)), s(stream ? stream : ctx->stream) {
         if (!on) return;
         ev.name = name; ev.bytes = bytes; ev.mads = mads;
         // events come from a pool that dst_kernel_stats refills: creating two per launch would be host time inside the timed region
         if (c->event_pool.size() >= 2) { ev.e0 = c->event_pool.back(); c->event_pool.pop_back(); ev.e1 = c->event_pool.back(); c->event_pool.pop_back(); }
         else if (hipEventCreate(&ev.e0) != hipSuccess || hipEventCreate(&ev.e1) != hipSuccess) { on = false; return; }
-        (void)hipEventRecord(ev.e0, c->stream);
+        (void)hipEventRecord(ev.e0, s);
     }
-    ~KScope() { if (on) { (void)hipEventRecord(ev.e1, c->stream); c->kpending.push_back(ev); } }
+    ~KScope() { if (on) { (void)hipEventRecord(ev.e1, s); c->kpending.push_back(ev); } }
 };
 
 #define HIP_TRY(ctx, expr)                                                                          \
@@ -356,7 +367,13 @@ void k_constraint_tree(dst_ctx* c);                                             
 void k_fri_leaves_layer0(dst_ctx* c);
 void k_fri_leaves(dst_ctx* c, int layer);
 // AIR
-int k_eval_constraints(dst_ctx* c, const fe* coeffs_dev, const fe* tc_dev, int64_t* bad_step, bool defer_check = false);   // defer_check: no host wait; k_constraint_check reads the flag later
+// defer_check: no host wait; k_constraint_check reads the flag later.  check_here = false: the evaluation alone -- the caller queues the check of
+// the trace rows, which is where the verdict comes from, itself (k_air_check_side)
+int k_eval_constraints(dst_ctx* c, const fe* coeffs_dev, const fe* tc_dev, int64_t* bad_step, bool defer_check = false, bool check_here = true);
+int k_air_check(dst_ctx* c, hipStream_t stream);                                       // queues the check chain and the read-back of its verdict on `stream` (the context's, or k_air_check_side's)
+int k_air_check_side(dst_ctx* c);                                                      // the same on the side stream, behind everything queued on the main stream so far
+size_t k_air_check_partials(const dst_ctx* c);                                         // arrays of n elements the chain of this context's instance set needs for its partial stack values
+int k_air_check_drain(dst_ctx* c);                                                     // host wait for a check chain on the side stream, if one is pending
 int k_constraint_check(dst_ctx* c, int64_t* bad_step);                                  // after a stream synchronisation: the failing step recorded by the last evaluation, if any
 // polynomial helpers
 void k_syn_div(dst_ctx* c, fe* a, size_t len, fe b);                                    // polynom.rs:190 semantics, in place

@@ -42,7 +42,8 @@ static_assert(ScratchTail::DRAWS + ScratchTail::MAX_TC <= ScratchTail::ELEMS && 
 // ---- steps 3-5 ------------------------------------------------------------------------------------------------------------------------
 // Step 3: remembers the 344 constraint coefficients (dst_ctx::air_draws), uploads them with the transition coefficients and queues the
 // AIR evaluation.  defer_check: the host does not wait for the verdict (k_constraint_check / the device word c->d_u64 later).
-int eval_constraints(dst_ctx* c, const dst_public* pub, const uint8_t* coeffs, int64_t* bad_step, bool defer_check);
+// check_here = false: the evaluation alone; the caller queues the check of the trace rows, the source of the verdict, itself (dst_prove).
+int eval_constraints(dst_ctx* c, const dst_public* pub, const uint8_t* coeffs, int64_t* bad_step, bool defer_check, bool check_here = true);
 // the two boundary combinations in coefficient form (ip / fp: 8n coefficients each; or the four n-coefficient pieces o0 .. o3), and the
 // n-coefficient quotients of them that the fused combination reads
 int boundary_polys(dst_ctx* c, const fe* draws344, fe* ip, fe* fp, fe* o0 = nullptr, fe* o1 = nullptr, fe* o2 = nullptr, fe* o3 = nullptr);

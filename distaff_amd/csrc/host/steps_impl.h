@@ -27,7 +27,7 @@ static void transition_coefficients(const dst_ctx* c, const fe* draws344, std::v
             if (deg[k] == d) { tc[k] = cc[2 * i]; tc[nc + k] = cc[2 * i + 1]; i++; }
 }
 
-int step::eval_constraints(dst_ctx* c, const dst_public* pub, const uint8_t* coeffs, int64_t* bad_step, bool defer_check) {
+int step::eval_constraints(dst_ctx* c, const dst_public* pub, const uint8_t* coeffs, int64_t* bad_step, bool defer_check, bool check_here) {
     c->pub = *pub;
     c->air_draws.resize(344);
     memcpy(c->air_draws.data(), coeffs, 344 * sizeof(fe));
@@ -43,7 +43,7 @@ int step::eval_constraints(dst_ctx* c, const dst_public* pub, const uint8_t* coe
     memcpy(h + 344, tc.data(), tc.size() * sizeof(fe));
     HIP_TRY(c, hipMemcpyAsync(tail.coef(), h, 344 * sizeof(fe), hipMemcpyHostToDevice, c->stream));
     HIP_TRY(c, hipMemcpyAsync(tail.tc(), h + 344, tc.size() * sizeof(fe), hipMemcpyHostToDevice, c->stream));
-    const int r = k_eval_constraints(c, tail.coef(), tail.tc(), bad_step, defer_check);      // prover.rs:53-64
+    const int r = k_eval_constraints(c, tail.coef(), tail.tc(), bad_step, defer_check, check_here);      // prover.rs:53-64
     if (r == DST_ERR_AIR) c->err = "transition constraints were not satisfied";
     return r;
 }

@@ -49,7 +49,7 @@ BUF = {"polys": 0, "lde": 1, "trace_leaves": 2, "trace_nodes": 3, "ceval_i": 4, 
 
 EXPORTS = ["dst_ctx_create", "dst_ctx_destroy", "dst_last_error", "dst_phase_ms", "dst_trace_upload", "dst_trace_upload_contiguous", "dst_trace_upload_owned",
            "dst_commit_trace", "dst_eval_constraints", "dst_compose", "dst_fri_commit_layer", "dst_fri_fold", "dst_pow_grind",
-           "dst_build_proof", "dst_prove", "dst_prng_vector", "dst_query_positions", "dst_blake3", "dst_fibonacci_trace",
+           "dst_build_proof", "dst_prove", "dst_last_bad_step", "dst_prng_vector", "dst_query_positions", "dst_blake3", "dst_fibonacci_trace",
            "dst_read_buffer", "dst_bench_mulmod", "dst_bench_mad", "dst_bench_code", "dst_trace_upload_async", "dst_pinned_alloc", "dst_pinned_free", "dst_set_profiling", "dst_kernel_stats", "dst_field_op",
            "dst_shard_commit_trace", "dst_shard_eval_constraints", "dst_shard_combine", "dst_shard_fri_layer", "dst_shard_fri_fold",
            "dst_shard_export_size", "dst_shard_export", "dst_shard_import", "dst_shard_read", "dst_shard_fri_begin", "dst_shard_fri_end", "dst_shard_fri_roots", "dst_shard_open", "dst_shard_assemble", "dst_shard_info",
@@ -122,6 +122,9 @@ def _open(path):
     lib = ctypes.CDLL(path)
     lib.dst_last_error.restype = ctypes.c_char_p
     lib.dst_last_error.argtypes = [ctypes.c_void_p]
+    if hasattr(lib, "dst_last_bad_step"):                              # a library named by DISTAFF_HIP_LIB may predate it
+        lib.dst_last_bad_step.restype = ctypes.c_int64
+        lib.dst_last_bad_step.argtypes = [ctypes.c_void_p]
     return lib
 
 
@@ -834,7 +837,10 @@ class Context:
         pub = make_public(inputs, outputs)
         buf = ctypes.create_string_buffer(cap)
         ln = ctypes.c_size_t(0)
-        self._check(self.lib.dst_prove(self._h, ctypes.byref(pub), buf, ctypes.c_size_t(cap), ctypes.byref(ln)))
+        r = self.lib.dst_prove(self._h, ctypes.byref(pub), buf, ctypes.c_size_t(cap), ctypes.byref(ln))
+        if hasattr(self.lib, "dst_last_bad_step"):                     # a library named by DISTAFF_HIP_LIB may predate it
+            self.bad_step = self.lib.dst_last_bad_step(self._h)
+        self._check(r)
         return buf.raw[:ln.value]
 
     def phase_ms(self):

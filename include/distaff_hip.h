@@ -121,6 +121,10 @@ DST_API int dst_build_proof(dst_ctx* ctx, const uint64_t* positions, uint32_t nu
 
 /* ---- the whole of stark::prove (prover.rs:17-168) on a trace already uploaded with dst_trace_upload ------------------- */
 DST_API int dst_prove(dst_ctx* ctx, const dst_public* pub, uint8_t* proof_out, size_t cap, size_t* proof_len);
+/* After DST_ERR_AIR from dst_prove (which has no bad_step argument) or dst_eval_constraints: the first trace step whose transition
+ * constraints do not vanish, as the last check of the trace rows on this context found it; -1 when that check found none.  dst_prove
+ * checks the rows beside the later phases of the proof and reports when the proof is otherwise complete. */
+DST_API int64_t dst_last_bad_step(const dst_ctx* ctx);
 
 /* ---- the other half of the reference's public pair: stark::verify (src/lib.rs:72, src/stark/verifier.rs:11) ------------
  * Host only: no context, no device, no HIP call -- it works on a machine without a GPU.  Returns DST_OK and *accepted = 1 for a valid

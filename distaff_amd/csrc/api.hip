@@ -5,7 +5,7 @@
 #include <cstdio>
 #include <cstdlib>
 #include "ctx.h"
-#include "host/ctx_tables.h"     // root powers and uploads, shared with k_ntt_init (kernels_ntt.hip)
+#include "host/ctx_tables.h"     // root powers, shared with k_ntt_init (kernels_ntt.hip)
 #include "host/steps.h"
 #include "host_proof.h"
 #include "host_util.h"
@@ -48,39 +48,6 @@ static std::vector<fe> build_periodic_table() {
     return out;
 }
 
-static void free_all(dst_ctx* c) {
-    void* ptrs[] = {c->tw_lo, c->tw_hi, c->itw_lo, c->itw_hi, c->prescale, c->dit_last, c->tw4_lde, c->tw4_fwd, c->tw4_inv, c->tw4_row_fwd, c->tw4_row_inv, c->tmp2, c->periodic, c->trace == c->lde ? nullptr : c->trace, c->polys, c->lde, c->tmp,
-                    c->trace_leaves, c->trace_nodes, c->air_consts, c->ceval, c->cwork, c->cpoly, c->cevals, c->cnodes, c->comp_poly, c->comp, c->scratch, c->d_u64, c->d_stage, c->d_fri_chain};
-    for (void* p : ptrs) if (p) hipFree(p);
-    for (auto& pass : c->ntt_stage_tw) for (fe_tw* p : pass) if (p) hipFree(p);
-    for (auto& pass : c->ntt_pre_tw) for (fe_tw* p : pass) if (p) hipFree(p);
-    for (auto& e : c->kpending) { hipEventDestroy(e.e0); hipEventDestroy(e.e1); }
-    for (hipEvent_t e : c->event_pool) hipEventDestroy(e);
-    if (c->gather_buf) hipFree(c->gather_buf);
-    if (c->trace_upper) hipFree(c->trace_upper);
-    if (c->c_upper) hipFree(c->c_upper);
-    for (int d = 0; d < DST_MAX_FRI_LAYERS; d++) if (c->fri_upper[d]) hipFree(c->fri_upper[d]);
-    if (c->fri_nat0) hipFree(c->fri_nat0);
-    for (int d = 0; d < DST_MAX_FRI_LAYERS; d++) {
-        if (d > 0 && c->fri_e[d]) hipFree(c->fri_e[d]);
-        if (c->fri_leaves[d]) hipFree(c->fri_leaves[d]);
-        if (c->fri_nodes[d]) hipFree(c->fri_nodes[d]);
-    }
-    if (c->check_partials) hipFree(c->check_partials);
-    if (c->check_ev) hipEventDestroy(c->check_ev);
-    if (c->check_stream) hipStreamDestroy(c->check_stream);
-    for (hipEvent_t e : c->upload_done) hipEventDestroy(e);
-    if (c->upload_stream) hipStreamDestroy(c->upload_stream);
-    for (hipEvent_t e : c->comm_events) hipEventDestroy(e);
-    if (c->comm_stream) hipStreamDestroy(c->comm_stream);
-    if (c->d_status) hipFree(c->d_status);
-    if (c->h_stage) hipHostFree(c->h_stage);
-    for (hipEvent_t e : c->ph_ev) if (e) hipEventDestroy(e);
-    for (hipEvent_t e : c->sh_ev) if (e) hipEventDestroy(e);
-    for (auto& ce : c->coll_ev) { hipEventDestroy(ce.e0); hipEventDestroy(ce.e1); }
-    if (c->stream) hipStreamDestroy(c->stream);
-}
-
 static int ctx_init(dst_ctx* c) {
     c->read_switches();                                  // the DISTAFF_* variables as they are NOW; nothing reads the environment after this
     const dst_params& p = c->prm;
@@ -101,15 +68,15 @@ static int ctx_init(dst_ctx* c) {
     if (c->stack_depth > 32) { c->err = "user stack deeper than 32 registers"; return DST_ERR_ARG; }
     c->device = p.device;
     HIP_TRY(c, hipSetDevice(c->device));
-    HIP_TRY(c, hipStreamCreate(&c->stream));
-    HIP_TRY(c, hipHostMalloc((void**)&c->h_stage, HS_TOTAL, hipHostMallocDefault));
-    for (hipEvent_t& e : c->ph_ev) HIP_TRY(c, hipEventCreate(&e));
+    int r;
+    if ((r = ctx_stream(c, &c->stream))) return r;
+    if ((r = ctx_pinned(c, &c->h_stage, HS_TOTAL))) return r;
+    for (hipEvent_t& e : c->ph_ev) if ((r = ctx_event(c, &e))) return r;
 
     // twiddle tables
     fe wN = h_root_of_unity(c->log_N), wN_inv = h_inv(wN);
     c->tw_lo_bits = (c->log_N + 1) / 2;
     uint32_t hi_bits = c->log_N - c->tw_lo_bits;
-    int r;
     if ((r = dev_upload(c, &c->tw_lo, h_powers(wN, (size_t)1 << c->tw_lo_bits)))) return r;
     if ((r = dev_upload(c, &c->tw_hi, h_powers(h_pow(wN, (u128)1 << c->tw_lo_bits), (size_t)1 << hi_bits)))) return r;
     if ((r = dev_upload(c, &c->itw_lo, h_powers(wN_inv, (size_t)1 << c->tw_lo_bits)))) return r;
@@ -180,12 +147,19 @@ static int ctx_init(dst_ctx* c) {
 static const fe* as_fe(const uint8_t* p) { return reinterpret_cast<const fe*>(p); }
 static std::vector<fe> copy_fe(const uint8_t* p, size_t count) { std::vector<fe> v(count); memcpy(v.data(), p, count * 16); return v; }
 
-// an asynchronous upload still in flight writes the same buffer from upload_stream: drain it before another upload starts.  So does
-// whatever else may still touch the trace buffer beside the main stream.
-static int drain_pending_upload(dst_ctx* c) {
+// How every upload entry point opens: an asynchronous upload still in flight writes the same buffer from upload_stream, so it is drained
+// before another upload starts.  So is whatever else may still touch the trace buffer beside the main stream.
+static int upload_begin(dst_ctx* c) {
+    HIP_TRY(c, hipSetDevice(c->device));
     { const int r = k_air_check_drain(c); if (r) return r; }    // a check of the trace rows on the side stream still reads that buffer
     if (c->upload_pending && c->upload_stream) HIP_TRY(c, hipStreamSynchronize(c->upload_stream));
     c->upload_pending = false;
+    return DST_OK;
+}
+// ... and how it closes: where the trace is now, and that nothing has been derived from it yet
+static int upload_end(dst_ctx* c, bool pending, bool owned_only) {
+    c->upload_pending = pending; c->trace_owned_only = owned_only;
+    c->have_trace = true; c->committed = c->constraints_done = c->composed = false;
     return DST_OK;
 }
 
@@ -209,37 +183,28 @@ int dst_phase_ms(const dst_ctx* c, double out_ms[9]) { if (!c || !out_ms) return
 
 int dst_trace_upload(dst_ctx* c, const uint8_t* const* cols) {
     if (!c || !cols) return DST_ERR_ARG;
-    HIP_TRY(c, hipSetDevice(c->device));
-    { int rd = drain_pending_upload(c); if (rd) return rd; }
+    { const int r = upload_begin(c); if (r) return r; }
     for (size_t i = 0; i < c->W; i++) HIP_TRY(c, hipMemcpyAsync(c->trace + i * c->trace_stride, cols[i], c->n * 16, hipMemcpyHostToDevice, c->stream));
     HIP_TRY(c, hipStreamSynchronize(c->stream));
-    c->upload_pending = false; c->trace_owned_only = false;
-    c->have_trace = true; c->committed = c->constraints_done = c->composed = false;
-    return DST_OK;
+    return upload_end(c, false, false);
 }
 // Sharded contexts: uploads only the registers this rank interpolates, r = rank (mod world) -- 1/world of the trace per GPU instead of
 // all of it.  cols[r] of the other registers is not read (may be NULL).  Only dst_prove_sharded accepts a context in this state.
 int dst_trace_upload_owned(dst_ctx* c, const uint8_t* const* cols) {
     if (!c || !cols) return DST_ERR_ARG;
-    HIP_TRY(c, hipSetDevice(c->device));
-    { int rd = drain_pending_upload(c); if (rd) return rd; }
+    { const int r = upload_begin(c); if (r) return r; }
     for (size_t i = c->prm.rank; i < c->W; i += c->prm.world) {
         if (!cols[i]) { c->err = "dst_trace_upload_owned: register " + std::to_string(i) + " belongs to this rank but has no data"; return DST_ERR_ARG; }
         HIP_TRY(c, hipMemcpyAsync(c->trace + i * c->trace_stride, cols[i], c->n * 16, hipMemcpyHostToDevice, c->stream));
     }
     HIP_TRY(c, hipStreamSynchronize(c->stream));
-    c->upload_pending = false; c->trace_owned_only = c->prm.world > 1;
-    c->have_trace = true; c->committed = c->constraints_done = c->composed = false;
-    return DST_OK;
+    return upload_end(c, false, c->prm.world > 1);
 }
 int dst_trace_upload_contiguous(dst_ctx* c, const uint8_t* cols) {
     if (!c || !cols) return DST_ERR_ARG;
-    HIP_TRY(c, hipSetDevice(c->device));
-    { int rd = drain_pending_upload(c); if (rd) return rd; }
+    { const int r = upload_begin(c); if (r) return r; }
     for (size_t i = 0; i < c->W; i++) HIP_TRY(c, hipMemcpy(c->trace + i * c->trace_stride, cols + i * c->n * 16, c->n * 16, hipMemcpyHostToDevice));
-    c->upload_pending = false; c->trace_owned_only = false;
-    c->have_trace = true; c->committed = c->constraints_done = c->composed = false;
-    return DST_OK;
+    return upload_end(c, false, false);
 }
 
 // Pinned host memory for the trace: the reference hands stark::prove a host-resident TraceTable (prover.rs:17, trace_table.rs:10); from
@@ -255,9 +220,8 @@ int dst_pinned_free(void* p) { return (!p || hipHostFree(p) == hipSuccess) ? DST
 // group's transfer is exposed.  The host buffers must stay valid until that call returns.
 int dst_trace_upload_async(dst_ctx* c, const uint8_t* const* cols) {
     if (!c || !cols) return DST_ERR_ARG;
-    HIP_TRY(c, hipSetDevice(c->device));
-    if (!c->upload_stream) HIP_TRY(c, hipStreamCreateWithFlags(&c->upload_stream, hipStreamNonBlocking));
-    { int rd = drain_pending_upload(c); if (rd) return rd; }
+    { const int r = upload_begin(c); if (r) return r; }
+    if (!c->upload_stream) { const int r = ctx_stream(c, &c->upload_stream, hipStreamNonBlocking); if (r) return r; }
     // the previous proof's kernels may still read the buffer on c->stream (coset 0 of the extension IS the trace buffer)
     HIP_TRY(c, hipStreamSynchronize(c->stream));
     // groups of 4 registers (one extension launch, see k_lde_columns) -- except that the first group is ONE register: its transfer is the
@@ -266,15 +230,13 @@ int dst_trace_upload_async(dst_ctx* c, const uint8_t* const* cols) {
     for (size_t first = 0; first < c->W;) { c->upload_bounds.push_back(first); first += (first == 0 && c->W > 4) ? (c->W % 4 ? c->W % 4 : 1) : 4; }
     c->upload_bounds.push_back(c->W);
     const size_t groups = c->upload_bounds.size() - 1;
-    while (c->upload_done.size() < groups) { hipEvent_t e; HIP_TRY(c, hipEventCreateWithFlags(&e, hipEventDisableTiming)); c->upload_done.push_back(e); }
+    while (c->upload_done.size() < groups) { hipEvent_t e; const int r = ctx_event(c, &e, hipEventDisableTiming); if (r) return r; c->upload_done.push_back(e); }
     for (size_t g = 0; g < groups; g++) {
         for (size_t i = c->upload_bounds[g]; i < c->upload_bounds[g + 1]; i++)
             HIP_TRY(c, hipMemcpyAsync(c->trace + i * c->trace_stride, cols[i], c->n * 16, hipMemcpyHostToDevice, c->upload_stream));
         HIP_TRY(c, hipEventRecord(c->upload_done[g], c->upload_stream));
     }
-    c->upload_pending = true; c->trace_owned_only = false;
-    c->have_trace = true; c->committed = c->constraints_done = c->composed = false;
-    return DST_OK;
+    return upload_end(c, true, false);
 }
 
 // ---- steps 1-2 ------------------------------------------------------------------------------------------------------------------

@@ -161,9 +161,17 @@ struct NttPlan {
     const NttPass& at(uint32_t i, bool lde) const { return (i == 0 && lde) ? first_lde : pass[i]; }
 };
 
+// Everything a context acquired from the runtime.  Only ctx_dev_bytes, ctx_pinned, ctx_event and ctx_stream (below) add to it, only free_all takes from
+// it: the pointer members of dst_ctx that kernels and launchers read are views of these, and an alias (trace == lde, fri_e[0] == comp) is in here once.
+struct dst_owned {
+    std::vector<void*> dev, pinned;                  // hipMalloc, hipHostMalloc
+    std::vector<hipEvent_t> events; std::vector<hipStream_t> streams;      // streams in order of creation: the main stream first
+};
+
 struct dst_ctx {
     dst_params prm{};
     std::string err;
+    dst_owned own;
     // the DISTAFF_* switches as they were when the context was created (see DST_SWITCHES); sw() returns nullptr for an unset one
     std::map<std::string, std::string> sw_values;
     const char* sw(const char* name) const { auto it = sw_values.find(name); return it == sw_values.end() ? nullptr : it->second.c_str(); }
@@ -302,6 +310,72 @@ struct dst_ctx {
     std::map<std::string, KStat> kstats;
 };
 
+#define HIP_TRY(ctx, expr)                                                                          \
+    do {                                                                                            \
+        hipError_t _e = (expr);                                                                     \
+        if (_e != hipSuccess) {                                                                     \
+            (ctx)->err = std::string(#expr) + ": " + hipGetErrorString(_e);                          \
+            return DST_ERR_HIP;                                                                     \
+        }                                                                                           \
+    } while (0)
+
+// ---- the only places that acquire a runtime resource for a context, and the one that releases them.  Each helper fails the way HIP_TRY
+//      does (c->err, DST_ERR_HIP) and leaves its target null then; what it made is the context's until free_all ---------------------------
+inline int ctx_dev_bytes(dst_ctx* c, void** p, size_t bytes) {
+    void* q = *p = nullptr;
+    HIP_TRY(c, hipMalloc(&q, bytes));
+    c->own.dev.push_back(*p = q);
+    return DST_OK;
+}
+template <class T> static int dev_alloc(dst_ctx* c, T** p, size_t count) { return ctx_dev_bytes(c, (void**)p, count * sizeof(T) > 0 ? count * sizeof(T) : 16); }
+template <class T> static int dev_upload(dst_ctx* c, T** p, const std::vector<T>& v) {
+    if (const int r = dev_alloc(c, p, v.size())) return r;
+    HIP_TRY(c, hipMemcpy(*p, v.data(), v.size() * sizeof(T), hipMemcpyHostToDevice));
+    return DST_OK;
+}
+inline int ctx_pinned(dst_ctx* c, uint8_t** p, size_t bytes) {              // a page-locked host block
+    void* q = *p = nullptr;
+    HIP_TRY(c, hipHostMalloc(&q, bytes, hipHostMallocDefault));
+    c->own.pinned.push_back(q); *p = (uint8_t*)q;
+    return DST_OK;
+}
+inline int ctx_event(dst_ctx* c, hipEvent_t* e, unsigned flags = 0) {
+    hipEvent_t q = *e = nullptr;
+    HIP_TRY(c, hipEventCreateWithFlags(&q, flags));
+    c->own.events.push_back(*e = q);
+    return DST_OK;
+}
+// lowest: at the lowest priority the device has (the host build of the tests: launches are synchronous there, its runtime has no priorities)
+inline int ctx_stream(dst_ctx* c, hipStream_t* s, unsigned flags = 0, bool lowest = false) {
+    hipStream_t q = *s = nullptr;
+#ifndef DISTAFF_EMULATED
+    int least = 0, greatest = 0;
+    if (lowest) { HIP_TRY(c, hipDeviceGetStreamPriorityRange(&least, &greatest)); HIP_TRY(c, hipStreamCreateWithPriority(&q, flags, least)); } else
+#endif
+    HIP_TRY(c, hipStreamCreateWithFlags(&q, flags));
+    c->own.streams.push_back(*s = q);
+    return DST_OK;
+}
+inline void free_all(dst_ctx* c) {            // allocations and events before the streams, the main stream last
+    for (void* p : c->own.dev) (void)hipFree(p);
+    for (void* p : c->own.pinned) (void)hipHostFree(p);
+    for (hipEvent_t e : c->own.events) (void)hipEventDestroy(e);
+    for (auto s = c->own.streams.rbegin(); s != c->own.streams.rend(); ++s) (void)hipStreamDestroy(*s);
+    c->own = dst_owned{};
+}
+// A timing event from the pool of recycled profiling events (dst_kernel_stats refills it), made when the pool is empty: creating two per
+// launch would be host time inside a timed region.  TimerPair: two of them for one function's own measurement, back in the pool on every way out.
+inline int ctx_timer_event(dst_ctx* c, hipEvent_t* e) {
+    if (c->event_pool.empty()) return ctx_event(c, e);
+    *e = c->event_pool.back(); c->event_pool.pop_back();
+    return DST_OK;
+}
+struct TimerPair {
+    dst_ctx* c; hipEvent_t e0 = nullptr, e1 = nullptr; int rc;
+    explicit TimerPair(dst_ctx* ctx) : c(ctx) { rc = ctx_timer_event(c, &e0); if (!rc) rc = ctx_timer_event(c, &e1); }
+    ~TimerPair() { for (hipEvent_t e : {e0, e1}) if (e) c->event_pool.push_back(e); }
+};
+
 // brackets one kernel launch with events when profiling is on; `bytes` = algorithmic HBM bytes of that launch, `mads` = 32x32+64
 // multiply-adds (v_mad_u64_u32) the launch executes per the kernel's arithmetic (0 where not counted)
 struct KScope {
@@ -312,22 +386,11 @@ struct KScope {
         : c(ctx), on(ctx->profile == 1 || (ctx->profile == 2 && heavy)), s(stream ? stream : ctx->stream) {
         if (!on) return;
         ev.name = name; ev.bytes = bytes; ev.mads = mads;
-        // events come from a pool that dst_kernel_stats refills: creating two per launch would be host time inside the timed region
-        if (c->event_pool.size() >= 2) { ev.e0 = c->event_pool.back(); c->event_pool.pop_back(); ev.e1 = c->event_pool.back(); c->event_pool.pop_back(); }
-        else if (hipEventCreate(&ev.e0) != hipSuccess || hipEventCreate(&ev.e1) != hipSuccess) { on = false; return; }
+        if (ctx_timer_event(c, &ev.e0) || ctx_timer_event(c, &ev.e1)) { on = false; return; }     // (a lone first event stays the context's: released with it)
         (void)hipEventRecord(ev.e0, s);
     }
     ~KScope() { if (on) { (void)hipEventRecord(ev.e1, s); c->kpending.push_back(ev); } }
 };
-
-#define HIP_TRY(ctx, expr)                                                                          \
-    do {                                                                                            \
-        hipError_t _e = (expr);                                                                     \
-        if (_e != hipSuccess) {                                                                     \
-            (ctx)->err = std::string(#expr) + ": " + hipGetErrorString(_e);                          \
-            return DST_ERR_HIP;                                                                     \
-        }                                                                                           \
-    } while (0)
 
 // host wait for the context's stream: bounded while a communicator is attached (comm.hip), hipStreamSynchronize otherwise
 int ctx_sync(dst_ctx* c, const char* what);

@@ -1,5 +1,5 @@
-// Host helpers of context creation: powers of roots of unity on the host field and their upload.  Shared by ctx_init (api.hip: domain
-// tables, periodic constants) and k_ntt_init (kernels_ntt.hip: every table of the transform plan).  Host code only.
+// Host helpers of context creation: powers of roots of unity on the host field (ctx.h's dev_upload takes them to the device).  Shared by
+// ctx_init (api.hip: domain tables, periodic constants) and k_ntt_init (kernels_ntt.hip: every table of the transform plan).  Host code only.
 #pragma once
 #include <vector>
 #include "../ctx.h"
@@ -25,16 +25,3 @@ static std::vector<fe_tw> h_powers_tw(fe base, size_t count) {     // table pair
 }
 static fe h_inv(fe a) { return dsth::fe_from_u128(dsth::hf_pow(dsth::fe_to_u128(a), dsth::FIELD_P - 2)); }
 static fe h_pow(fe a, dsth::u128 e) { return dsth::fe_from_u128(dsth::hf_pow(dsth::fe_to_u128(a), e)); }
-
-template <class T>
-static int dev_alloc(dst_ctx* c, T** p, size_t count) {
-    HIP_TRY(c, hipMalloc((void**)p, count * sizeof(T) > 0 ? count * sizeof(T) : 16));
-    return DST_OK;
-}
-template <class T>
-static int dev_upload(dst_ctx* c, T** p, const std::vector<T>& v) {
-    int r = dev_alloc(c, p, v.size());
-    if (r) return r;
-    HIP_TRY(c, hipMemcpy(*p, v.data(), v.size() * sizeof(T), hipMemcpyHostToDevice));
-    return DST_OK;
-}

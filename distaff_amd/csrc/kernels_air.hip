@@ -40,7 +40,7 @@ static int air_shape_args(dst_ctx* c, AirArgs& a) {
         AirConsts h;
         memcpy(h.sponge_mds, SPONGE_MDS, sizeof(h.sponge_mds)); memcpy(h.sponge_inv_mds, SPONGE_INV_MDS, sizeof(h.sponge_inv_mds));
         memcpy(h.hasher_mds, HASHER_MDS, sizeof(h.hasher_mds)); memcpy(h.hasher_inv_mds, HASHER_INV_MDS, sizeof(h.hasher_inv_mds));
-        HIP_TRY(c, hipMalloc(&c->air_consts, sizeof(AirConsts)));
+        { const int r = ctx_dev_bytes(c, &c->air_consts, sizeof(AirConsts)); if (r) return r; }
         HIP_TRY(c, hipMemcpy(c->air_consts, &h, sizeof(AirConsts), hipMemcpyHostToDevice));
     }
     a.lde = c->lde; a.periodic = c->periodic; a.consts = (const AirConsts*)c->air_consts;
@@ -129,16 +129,8 @@ int k_air_check(dst_ctx* c, hipStream_t stream) {
 // later on the main stream waits for it; the caller drains it (k_air_check_drain) before it reports, and so does whoever writes or frees the
 // trace buffer.
 int k_air_check_side(dst_ctx* c) {
-    if (!c->check_stream) {
-#ifdef DISTAFF_EMULATED      // the host build of the tests: launches are synchronous there and its runtime has no stream priorities
-        HIP_TRY(c, hipStreamCreateWithFlags(&c->check_stream, hipStreamNonBlocking));
-#else
-        int least = 0, greatest = 0;
-        HIP_TRY(c, hipDeviceGetStreamPriorityRange(&least, &greatest));
-        HIP_TRY(c, hipStreamCreateWithPriority(&c->check_stream, hipStreamNonBlocking, least));
-#endif
-        HIP_TRY(c, hipEventCreateWithFlags(&c->check_ev, hipEventDisableTiming));
-    }
+    if (!c->check_stream) { const int r = ctx_stream(c, &c->check_stream, hipStreamNonBlocking, /*lowest=*/true); if (r) return r; }
+    if (!c->check_ev) { const int r = ctx_event(c, &c->check_ev, hipEventDisableTiming); if (r) return r; }
     HIP_TRY(c, hipEventRecord(c->check_ev, c->stream));
     HIP_TRY(c, hipStreamWaitEvent(c->check_stream, c->check_ev, 0));
     c->check_pending = true;                                           // from the first thing queued on: a failure below leaves work on the stream

@@ -695,17 +695,16 @@ int k_bench_mulmod(dst_ctx* c, uint64_t lanes, uint32_t iters, double* ms) {
     iters &= 0x7FFFFFFFu;
     if (lanes > c->scratch_elems || lanes < PT) { c->err = "dst_bench_mulmod: lanes must be in [256, 2^21]"; return DST_ERR_ARG; }
     lanes = lanes / PT * PT;
-    hipEvent_t e0, e1;
-    HIP_TRY(c, hipEventCreate(&e0)); HIP_TRY(c, hipEventCreate(&e1));
+    TimerPair t(c);                                           // two timing events of the context: no way out leaks one
+    if (t.rc) return t.rc;
     { KScope ks_(c, "mulmod_bench_kernel", 0.0); hipLaunchKernelGGL(mulmod_bench_kernel<0>, dim3((unsigned)(lanes / PT)), dim3(PT), 0, c->stream, c->scratch, 4u); }   // warm-up
-    HIP_TRY(c, hipEventRecord(e0, c->stream));
+    HIP_TRY(c, hipEventRecord(t.e0, c->stream));
     if (portable) { KScope ks_(c, "mulmod_bench_kernel", 0.0); hipLaunchKernelGGL(mulmod_bench_kernel<1>, dim3((unsigned)(lanes / PT)), dim3(PT), 0, c->stream, c->scratch, iters); }
     else { KScope ks_(c, "mulmod_bench_kernel", 0.0); hipLaunchKernelGGL(mulmod_bench_kernel<0>, dim3((unsigned)(lanes / PT)), dim3(PT), 0, c->stream, c->scratch, iters); }
-    HIP_TRY(c, hipEventRecord(e1, c->stream));
-    HIP_TRY(c, hipEventSynchronize(e1));
-    float f = 0; HIP_TRY(c, hipEventElapsedTime(&f, e0, e1));
+    HIP_TRY(c, hipEventRecord(t.e1, c->stream));
+    HIP_TRY(c, hipEventSynchronize(t.e1));
+    float f = 0; HIP_TRY(c, hipEventElapsedTime(&f, t.e0, t.e1));
     *ms = f;
-    hipEventDestroy(e0); hipEventDestroy(e1);
     return DST_OK;
 }
 
@@ -768,16 +767,15 @@ __global__ void __launch_bounds__(PT) mad_peak_kernel(uint64_t* out, uint32_t it
 int k_bench_mad(dst_ctx* c, uint64_t lanes, uint32_t iters, double* ms) {
     if (lanes > c->scratch_elems * 2 || lanes < PT) { c->err = "dst_bench_mad: lanes must be in [256, 2^22]"; return DST_ERR_ARG; }
     lanes = lanes / PT * PT;
-    hipEvent_t e0, e1;
-    HIP_TRY(c, hipEventCreate(&e0)); HIP_TRY(c, hipEventCreate(&e1));
+    TimerPair t(c);                                           // two timing events of the context: no way out leaks one
+    if (t.rc) return t.rc;
     hipLaunchKernelGGL(mad_peak_kernel, dim3((unsigned)(lanes / PT)), dim3(PT), 0, c->stream, (uint64_t*)c->scratch, 4u);
-    HIP_TRY(c, hipEventRecord(e0, c->stream));
+    HIP_TRY(c, hipEventRecord(t.e0, c->stream));
     hipLaunchKernelGGL(mad_peak_kernel, dim3((unsigned)(lanes / PT)), dim3(PT), 0, c->stream, (uint64_t*)c->scratch, iters);
-    HIP_TRY(c, hipEventRecord(e1, c->stream));
-    HIP_TRY(c, hipEventSynchronize(e1));
-    float f = 0; HIP_TRY(c, hipEventElapsedTime(&f, e0, e1));
+    HIP_TRY(c, hipEventRecord(t.e1, c->stream));
+    HIP_TRY(c, hipEventSynchronize(t.e1));
+    float f = 0; HIP_TRY(c, hipEventElapsedTime(&f, t.e0, t.e1));
     *ms = f;
-    hipEventDestroy(e0); hipEventDestroy(e1);
     return DST_OK;
 }
 

@@ -36,18 +36,17 @@ static int run_probe(dst_ctx* c, double* ms) {
     const size_t lanes = (size_t)8 << 20;                     // the constraint kernels' grid at 2^20 steps
     const int lds = 40 * 1024 * (THREADS / 128);
     HIP_TRY(c, hipFuncSetAttribute((const void*)code_probe_kernel<KIB, THREADS, CONVOY>, hipFuncAttributeMaxDynamicSharedMemorySize, lds));
-    hipEvent_t e0, e1;
-    HIP_TRY(c, hipEventCreate(&e0)); HIP_TRY(c, hipEventCreate(&e1));
+    TimerPair t(c);                                           // two timing events of the context: no way out leaks one
+    if (t.rc) return t.rc;
     double best = 1e30;
     for (int rep = 0; rep < 3; rep++) {
-        HIP_TRY(c, hipEventRecord(e0, c->stream));
+        HIP_TRY(c, hipEventRecord(t.e0, c->stream));
         hipLaunchKernelGGL((code_probe_kernel<KIB, THREADS, CONVOY>), dim3((unsigned)(lanes / THREADS)), dim3(THREADS), lds, c->stream, (uint64_t*)c->scratch, 3u, 5u);
-        HIP_TRY(c, hipEventRecord(e1, c->stream));
-        HIP_TRY(c, hipEventSynchronize(e1));
-        float f = 0; HIP_TRY(c, hipEventElapsedTime(&f, e0, e1));
+        HIP_TRY(c, hipEventRecord(t.e1, c->stream));
+        HIP_TRY(c, hipEventSynchronize(t.e1));
+        float f = 0; HIP_TRY(c, hipEventElapsedTime(&f, t.e0, t.e1));
         if (rep > 0 && f < best) best = f;
     }
-    hipEventDestroy(e0); hipEventDestroy(e1);
     *ms = best;
     return DST_OK;
 }

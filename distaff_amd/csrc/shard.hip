@@ -86,24 +86,23 @@ static const digest* tree_boundary(dst_ctx* c, const ShardTree& t) {
 // locally at proving time (no trace uploaded, a bad argument) can still take part in every exchange and report its status through
 // them, instead of leaving its peers in a collective it never enters.
 int ensure_shard_buffers(dst_ctx* c) {
-    if (c->gather_buf && c->d_status) return DST_OK;
-    if (c->gather_buf) { HIP_TRY(c, hipMalloc((void**)&c->d_status, 1024)); return DST_OK; }
     const size_t n = c->n, G = c->prm.world;
     c->fri_rep_from = fri_replicated_from(c);
     size_t need = 32 * n * G;
     if (384 * n > need) need = 384 * n;
     if (c->fri_size[c->fri_rep_from] * 16 > need) need = c->fri_size[c->fri_rep_from] * 16;      // the gathered evaluations of the first replicated layer
-    if (c->fri_rep_from == 0) HIP_TRY(c, hipMalloc((void**)&c->fri_nat0, c->fri_size[0] * sizeof(fe)));
-    HIP_TRY(c, hipMalloc((void**)&c->gather_buf, need));
-    c->gather_bytes = need;
-    HIP_TRY(c, hipMalloc((void**)&c->trace_upper, 2 * n * G * sizeof(digest)));
-    HIP_TRY(c, hipMalloc((void**)&c->c_upper, 2 * n * G * sizeof(digest)));
+    int r = DST_OK;
+    const auto have = [&](auto*& p, size_t count) { return r == DST_OK && !p && (r = dev_alloc(c, &p, count)); };      // a buffer that is there already stays
+    if (c->fri_rep_from == 0) have(c->fri_nat0, c->fri_size[0]);
+    have(c->gather_buf, need);
+    if (c->gather_buf) c->gather_bytes = need;
+    for (digest** upper : {&c->trace_upper, &c->c_upper}) have(*upper, 2 * n * G);
     for (int d = 0; d < c->num_fri_layers; d++) {
         size_t nb = c->fri_size[d] / c->B / 4;             // boundary nodes per rank = rows per coset
-        HIP_TRY(c, hipMalloc((void**)&c->fri_upper[d], (2 * nb * G > 2 ? 2 * nb * G : 2) * sizeof(digest)));
+        have(c->fri_upper[d], 2 * nb * G > 2 ? 2 * nb * G : 2);
     }
-    HIP_TRY(c, hipMalloc((void**)&c->d_status, 1024));     // status records of dst_prove_sharded (one per rank)
-    return DST_OK;
+    have(c->d_status, 1024);                               // status records of dst_prove_sharded (one per rank)
+    return r;
 }
 static int copy_in(dst_ctx* c, void* dst, const void* src, size_t bytes, int src_is_device) {
     if (src_is_device && dst == src) return DST_OK;              // dst_prove_sharded gathers straight into the landing buffer
@@ -667,8 +666,8 @@ struct Sharded {
         if (c->coll_used < c->coll_ev.size()) ev = &c->coll_ev[c->coll_used];
         else if (c->coll_ev.size() < 256) {
             dst_ctx::CollEv n{nullptr, nullptr, 0};
-            if (hipEventCreate(&n.e0) == hipSuccess && hipEventCreate(&n.e1) == hipSuccess) { c->coll_ev.push_back(n); ev = &c->coll_ev.back(); }
-            else { if (n.e0) hipEventDestroy(n.e0); (void)hipGetLastError(); }
+            if (ctx_event(c, &n.e0) == DST_OK && ctx_event(c, &n.e1) == DST_OK) { c->coll_ev.push_back(n); ev = &c->coll_ev.back(); }
+            else (void)hipGetLastError();
         }
         c->exchange_ms[6] += 1;
         if (ev && hipEventRecord(ev->e0, stream) != hipSuccess) { (void)hipGetLastError(); ev = nullptr; }
@@ -783,8 +782,8 @@ void commit_trace_columns(Sharded& S) {
     });
     const bool overlap = S.side_stream();                      // the all-gathers of round k + 1 beside the extension of round k
     if (overlap) S.local([&]() -> int {
-        if (!c->comm_stream) HIP_TRY(c, hipStreamCreateWithFlags(&c->comm_stream, hipStreamNonBlocking));
-        while (c->comm_events.size() < 2 * rounds) { hipEvent_t e; HIP_TRY(c, hipEventCreateWithFlags(&e, hipEventDisableTiming)); c->comm_events.push_back(e); }
+        if (!c->comm_stream) { const int r = ctx_stream(c, &c->comm_stream, hipStreamNonBlocking); if (r) return r; }
+        while (c->comm_events.size() < 2 * rounds) { hipEvent_t e; const int r = ctx_event(c, &e, hipEventDisableTiming); if (r) return r; c->comm_events.push_back(e); }
         return DST_OK;
     });
     const bool use_side = overlap && S.rc == DST_OK;
@@ -953,7 +952,7 @@ int dst_prove_sharded(dst_ctx* c, dst_comm* comm, const dst_public* pub, uint8_t
     // ENQUEUES between two waits, so its own clock says nothing about where the device's time went.  sh_ev: 0 start, 1 end of the
     // extension, 2 / 3 around the constraint evaluation, 4 end of the combination.
     bool timed = true;
-    for (int i = 0; i < 5 && timed; i++) if (!c->sh_ev[i] && hipEventCreate(&c->sh_ev[i]) != hipSuccess) { (void)hipGetLastError(); c->sh_ev[i] = nullptr; timed = false; }
+    for (int i = 0; i < 5 && timed; i++) if (!c->sh_ev[i] && ctx_event(c, &c->sh_ev[i])) { (void)hipGetLastError(); timed = false; }
     auto ev_ms = [&](int a, int b) { return timed ? event_ms(c->sh_ev[a], c->sh_ev[b]) : -1.0; };
     // steps 1-2.  Nothing waits for the extension on the host (the tree exchange is queued behind it)
     timed = timed && hipEventRecord(c->sh_ev[0], c->stream) == hipSuccess;

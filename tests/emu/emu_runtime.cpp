@@ -12,6 +12,7 @@
 #include <cstdlib>
 #include <functional>
 #include <mutex>
+#include <set>
 #include <thread>
 #include <vector>
 #include <sys/mman.h>
@@ -191,6 +192,55 @@ unsigned emu_atomic_add_u32(unsigned* p, unsigned v) { return reinterpret_cast<s
 struct emu_stream { int unused; };
 struct emu_event { std::chrono::steady_clock::time_point t; };
 
+// The ledger of what is live, for the tests of what a context leaves behind (tests/test_ctx_lifetime_gpu.py): every acquisition enters its
+// kind's set, every release leaves it; a release of something that is not live -- a second release, a pointer never acquired -- is counted
+// and otherwise ignored.  The tests read it and make an acquisition fail through the two exported functions below; the library under test
+// knows nothing of them.
+namespace {
+enum Kind { K_DEVICE, K_PINNED, K_EVENT, K_STREAM, K_KINDS };
+struct Ledger {
+    std::mutex mu;                               // thread-ranks acquire concurrently
+    std::set<const void*> live[K_KINDS];
+    long bad_releases = 0;
+    long fail_in = -1;                           // the acquisition that many from now fails; -1: none
+};
+Ledger& ledger() { static Ledger* l = new Ledger; return *l; }       // never destroyed: handles may be closed at process exit
+// false: this acquisition is the one that was asked to fail
+bool acquire(Kind k, const std::function<const void*()>& make) {
+    Ledger& l = ledger();
+    std::lock_guard<std::mutex> lk(l.mu);
+    if (l.fail_in >= 0 && l.fail_in-- == 0) return false;
+    const void* p = make();
+    if (!p) return false;
+    l.live[k].insert(p);
+    return true;
+}
+bool release(Kind k, const void* p) {            // true: p was live and is the caller's to free
+    Ledger& l = ledger();
+    std::lock_guard<std::mutex> lk(l.mu);
+    if (l.live[k].erase(p)) return true;
+    l.bad_releases++;
+    return false;
+}
+hipError_t allocate(Kind k, void** p, size_t bytes) {
+    *p = nullptr;
+    return acquire(k, [&]() -> const void* { return posix_memalign(p, 256, bytes ? bytes : 256) ? nullptr : *p; }) ? hipSuccess : hipErrorOutOfMemory;
+}
+}  // namespace
+// out[0..3]: live device allocations, page-locked allocations, events, streams; out[4]: releases of something that was not live
+extern "C" void emu_live_counts(long out[5]) {
+    Ledger& l = ledger();
+    std::lock_guard<std::mutex> lk(l.mu);
+    for (int k = 0; k < K_KINDS; k++) out[k] = (long)l.live[k].size();
+    out[4] = l.bad_releases;
+}
+// the k-th next acquisition of any kind (k = 0: the next one) fails with hipErrorOutOfMemory; k < 0: none does
+extern "C" void emu_fail_acquisition(long k) {
+    Ledger& l = ledger();
+    std::lock_guard<std::mutex> lk(l.mu);
+    l.fail_in = k;
+}
+
 const char* hipGetErrorString(hipError_t e) { return e == hipSuccess ? "no error" : e == hipErrorOutOfMemory ? "out of memory (emulated)" : "error (emulated)"; }
 hipError_t hipGetLastError() { return hipSuccess; }
 hipError_t hipGetDeviceCount(int* n) { *n = 1; return hipSuccess; }
@@ -203,14 +253,10 @@ hipError_t hipGetDeviceProperties(hipDeviceProp_t* p, int) {
     return hipSuccess;
 }
 hipError_t hipDeviceSynchronize() { return hipSuccess; }
-hipError_t hipMalloc(void** p, size_t bytes) {
-    *p = nullptr;
-    if (posix_memalign(p, 256, bytes ? bytes : 256)) return hipErrorOutOfMemory;
-    return hipSuccess;
-}
-hipError_t hipFree(void* p) { free(p); return hipSuccess; }
-hipError_t hipHostMalloc(void** p, size_t bytes, unsigned) { return hipMalloc(p, bytes); }
-hipError_t hipHostFree(void* p) { free(p); return hipSuccess; }
+hipError_t hipMalloc(void** p, size_t bytes) { return allocate(K_DEVICE, p, bytes); }
+hipError_t hipFree(void* p) { if (p && release(K_DEVICE, p)) free(p); return hipSuccess; }
+hipError_t hipHostMalloc(void** p, size_t bytes, unsigned) { return allocate(K_PINNED, p, bytes); }
+hipError_t hipHostFree(void* p) { if (p && release(K_PINNED, p)) free(p); return hipSuccess; }
 hipError_t hipMemGetInfo(size_t* f, size_t* t) { *f = *t = (size_t)8 << 30; return hipSuccess; }
 hipError_t hipMemcpy(void* dst, const void* src, size_t bytes, hipMemcpyKind) { memmove(dst, src, bytes); return hipSuccess; }
 hipError_t hipMemcpyAsync(void* dst, const void* src, size_t bytes, hipMemcpyKind, hipStream_t) { memmove(dst, src, bytes); return hipSuccess; }
@@ -220,12 +266,12 @@ hipError_t hipMemcpy2DAsync(void* dst, size_t dpitch, const void* src, size_t sp
 }
 hipError_t hipMemset(void* dst, int value, size_t bytes) { memset(dst, value, bytes); return hipSuccess; }
 hipError_t hipMemsetAsync(void* dst, int value, size_t bytes, hipStream_t) { memset(dst, value, bytes); return hipSuccess; }
-hipError_t hipStreamCreate(hipStream_t* s) { *s = new emu_stream{0}; return hipSuccess; }
+hipError_t hipStreamCreate(hipStream_t* s) { *s = nullptr; return acquire(K_STREAM, [&] { return *s = new emu_stream{0}; }) ? hipSuccess : hipErrorOutOfMemory; }
 hipError_t hipStreamCreateWithFlags(hipStream_t* s, unsigned) { return hipStreamCreate(s); }
-hipError_t hipStreamDestroy(hipStream_t s) { delete s; return hipSuccess; }
+hipError_t hipStreamDestroy(hipStream_t s) { if (release(K_STREAM, s)) delete s; return hipSuccess; }
 hipError_t hipStreamSynchronize(hipStream_t) { return hipSuccess; }
-hipError_t hipEventCreate(hipEvent_t* e) { *e = new emu_event{}; return hipSuccess; }
-hipError_t hipEventDestroy(hipEvent_t e) { delete e; return hipSuccess; }
+hipError_t hipEventCreate(hipEvent_t* e) { *e = nullptr; return acquire(K_EVENT, [&] { return *e = new emu_event{}; }) ? hipSuccess : hipErrorOutOfMemory; }
+hipError_t hipEventDestroy(hipEvent_t e) { if (release(K_EVENT, e)) delete e; return hipSuccess; }
 hipError_t hipEventRecord(hipEvent_t e, hipStream_t) { e->t = std::chrono::steady_clock::now(); return hipSuccess; }
 hipError_t hipEventSynchronize(hipEvent_t) { return hipSuccess; }
 hipError_t hipEventElapsedTime(float* ms, hipEvent_t a, hipEvent_t b) { *ms = std::chrono::duration<float, std::milli>(b->t - a->t).count(); return hipSuccess; }

@@ -490,3 +490,9 @@ int k_rescue_stree_level(hipStream_t stream, fe* nodes, const uint64_t* pref, co
 int k_rescue_stree_carry(hipStream_t stream, fe* dst, const fe* src, const uint32_t* from /* device */, size_t count);     // dst[j] = src[from[j]] unless from[j] == STREE_NEW
 // out[(i * (depth + 1) + k) ..] = node k of the path of indices[i], stored or empty; levels = (start, length) per level, empties = 2 elements per level (device)
 int k_rescue_stree_open(hipStream_t stream, const fe* nodes, const uint64_t* pref, const uint64_t* levels, const fe* empties, const uint64_t* indices, fe* out, size_t count, uint32_t depth);
+// ordered writes (host/tree_sequence.h): the versions vin of one level -> vout, those of the level above, for `count` operations; src / own = this
+// level's source words, idx = the operations' indices, paths = count paths of n nodes or nullptr (all device); k = the path node the siblings
+// are; nodes = the tree before the call; empty = the value of an empty child (host)
+int k_rescue_seq_level(hipStream_t stream, const fe* nodes, const fe* vin, fe* vout, const uint32_t* src, const uint32_t* own, const uint64_t* idx, fe* paths, size_t count, uint32_t k, uint32_t n,
+                       const fe* empty);
+int k_rescue_tree_scatter_from(hipStream_t stream, fe* nodes, const uint32_t* pos, const fe* vals, const uint32_t* from /* device */, size_t count);      // nodes[pos[i]] = vals[from[i]]

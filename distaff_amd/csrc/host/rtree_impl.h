@@ -5,6 +5,7 @@
 #include <memory>
 #include "../ctx.h"
 #include "../host_rescue.h"
+#include "tree_sequence.h"
 
 struct dst_rtree {
     int device = -1;                      // < 0: the nodes live in `host`
@@ -12,7 +13,7 @@ struct dst_rtree {
     fe* dev = nullptr;                    // node array on the device: 2 elements per node, nodes[1] = root, nodes[leaves ..) = the leaves
     std::vector<u128> host;
     double device_ms = 0;                 // events around the level launches of the build
-    double update_ms = 0;                 // ... and of the last dst_rtree_update
+    double update_ms = 0;                 // ... and of the last dst_rtree_update / dst_rtree_apply
     bool broken = false;                  // a HIP error inside dst_rtree_update: the nodes are in an unknown state, only destroy / last_error remain
     // what the build, the updates and the openings of a device tree run on: rtree_stage creates the stream and the events with the build and
     // grows the staging buffer as calls need it (openings of a const tree too, hence mutable); they live as long as the tree
@@ -305,9 +306,101 @@ static int rtree_tapes(const dst_rtree* t, const uint64_t* indices, size_t count
     } catch (const std::bad_alloc&) { return rt_fail(t, DST_ERR_HIP, "out of host memory"); }
     return DST_OK;
 }
+// generate_program_inputs over paths the caller holds (the witnesses of dst_rtree_apply / dst_stree_apply, or anyone's): no tree, no device
+int dst_rescue_path_tapes(const uint8_t* paths, uint32_t n, const uint64_t* indices, size_t count, uint32_t what, uint8_t* tape_a, uint8_t* tape_b, size_t cap_elems_each, size_t* elems_each) {
+    if (!elems_each || what < 1 || what > 3) { g_rtree_error = "elems_each missing, or what outside 1..3"; return DST_ERR_ARG; }
+    if (n < 2 || n > TSEQ_MAX_DEPTH + 1) { g_rtree_error = "a path has 2 .. 64 nodes"; return DST_ERR_ARG; }
+    if (!indices && count) { g_rtree_error = "null pointer"; return DST_ERR_ARG; }
+    if (count > ((size_t)1 << 40)) { g_rtree_error = "too many indices"; return DST_ERR_ARG; }
+    const size_t each = ((what & 1u) ? 2 * (size_t)n - 1 : 0) + ((what & 2u) ? (size_t)n - 1 : 0);
+    *elems_each = each;
+    for (size_t i = 0; i < count; i++) if (indices[i] >> (n - 1)) { g_rtree_error = "leaf index past the end"; return DST_ERR_ARG; }
+    if (!tape_a && !tape_b) return DST_OK;                                                 // size query
+    if (!tape_a || !tape_b || cap_elems_each < each) { g_rtree_error = "tape buffers missing or too small"; return DST_ERR_ARG; }
+    if (count == 0) return DST_OK;
+    if (!paths) { g_rtree_error = "null pointer"; return DST_ERR_ARG; }
+    if (!all_below_p(paths, 2 * (size_t)n * count)) { g_rtree_error = "a path element is not below the modulus"; return DST_ERR_ARG; }
+    try {
+        std::vector<u128> v(2 * (size_t)n * count);                                        // the caller's buffer needs only byte alignment
+        memcpy(v.data(), paths, 32 * (size_t)n * count);
+        tapes_from_paths(v.data(), n, indices, count, what, each, tape_a, tape_b);
+    } catch (const std::bad_alloc&) { g_rtree_error = "out of host memory"; return DST_ERR_HIP; }
+    return DST_OK;
+}
 int dst_rtree_tapes(const dst_rtree* t, uint64_t index, uint32_t what, uint8_t* tape_a, uint8_t* tape_b, size_t cap_elems, size_t* elems) {
     return rtree_tapes(t, &index, 1, what, tape_a, tape_b, cap_elems, elems, "elems");
 }
 int dst_rtree_tapes_many(const dst_rtree* t, const uint64_t* indices, size_t count, uint32_t what, uint8_t* tape_a, uint8_t* tape_b, size_t cap_elems_each, size_t* elems_each) {
     return rtree_tapes(t, indices, count, what, tape_a, tape_b, cap_elems_each, elems_each, "elems_each");
+}
+
+// ---- ordered writes (tree_sequence.h) --------------------------------------------------------------------------------------------------
+// the level launches of an apply on a device tree (T: dst_rtree, dst_stree): `nodes` is the tree before the call, `empties` a sparse tree's E_l
+// (nullptr: dense), spos the node-array positions of p's touched nodes when their last versions are to be written into `nodes` (dense), empty
+// otherwise.  Staging: [the leaves = the versions of level D][indices][source words][spos][the touched nodes' last operations] -- one upload --
+// [the versions of level D - 1]: the levels take the two version areas by turns; then [paths].  The last versions of level l + 1 go into the node
+// array behind the launch of level l, which reads that level's nodes as they were.  One synchronisation; ms: events around the launches.
+template <class T>
+static int tseq_run_device(const T* t, fe* nodes, const u128* empties, const tseq_plan& p, const std::vector<uint32_t>& spos, const uint64_t* indices, const uint8_t* leaves,
+                           uint8_t* paths, uint8_t* roots, double* ms) {
+    const size_t K = p.count, D = p.depth, n = D + 1, S = spos.size();
+    const size_t o_idx = 32 * K, o_src = o_idx + 8 * K, o_pos = o_src + 4 * K * n, o_from = o_pos + 4 * S, up_bytes = o_from + 4 * S;
+    const size_t o_other = (up_bytes + 15) & ~(size_t)15, o_paths = o_other + 32 * K, total = o_paths + (paths ? 32 * K * n : 0);
+    std::vector<uint8_t> up(up_bytes);                                // the last host allocation: nothing is queued yet
+    memcpy(up.data(), leaves, 32 * K);
+    memcpy(up.data() + o_idx, indices, 8 * K);
+    memcpy(up.data() + o_src, p.src.data(), 4 * K * n);
+    if (S) { memcpy(up.data() + o_pos, spos.data(), 4 * S); memcpy(up.data() + o_from, p.tlast.data(), 4 * S); }
+    if (int r = rtree_stage(t, total)) return r;
+    uint8_t* st = t->stage;
+    fe* const ver[2] = {reinterpret_cast<fe*>(st), reinterpret_cast<fe*>(st + o_other)};             // level l: ver[(D - l) & 1]
+    const uint64_t* d_idx = reinterpret_cast<const uint64_t*>(st + o_idx);
+    const uint32_t *d_src = reinterpret_cast<const uint32_t*>(st + o_src), *d_pos = reinterpret_cast<const uint32_t*>(st + o_pos), *d_from = reinterpret_cast<const uint32_t*>(st + o_from);
+    fe* d_paths = paths ? reinterpret_cast<fe*>(st + o_paths) : nullptr;
+    static const u128 none[2] = {0, 0};
+    auto scatter = [&](size_t l) {                                     // level l's last versions -> nodes
+        return S && k_rescue_tree_scatter_from(t->stream, nodes, d_pos + p.toff[l], ver[(D - l) & 1], d_from + p.toff[l], p.tcnt[l]);
+    };
+    RT_HIP(t->err, hipMemcpyAsync(st, up.data(), up_bytes, hipMemcpyHostToDevice, t->stream));
+    RT_HIP(t->err, hipEventRecord(t->ev[0], t->stream));
+    for (size_t l = D; l-- > 0;) {
+        const uint32_t k = (uint32_t)(D - l);
+        if (k_rescue_seq_level(t->stream, nodes, ver[(k - 1) & 1], ver[k & 1], d_src + k * K, k == 1 ? d_src : nullptr, d_idx, d_paths, K, k, (uint32_t)n,
+                               reinterpret_cast<const fe*>(empties ? empties + 2 * (l + 1) : none))) { t->err = "rescue_seq_level_kernel: launch failed"; return DST_ERR_HIP; }
+        if (scatter(l + 1)) { t->err = "rescue_tree_scatter_from_kernel: launch failed"; return DST_ERR_HIP; }
+    }
+    if (scatter(0)) { t->err = "rescue_tree_scatter_from_kernel: launch failed"; return DST_ERR_HIP; }
+    RT_HIP(t->err, hipEventRecord(t->ev[1], t->stream));
+    if (paths) RT_HIP(t->err, hipMemcpyAsync(paths, d_paths, 32 * K * n, hipMemcpyDeviceToHost, t->stream));
+    if (roots) RT_HIP(t->err, hipMemcpyAsync(roots, ver[D & 1], 32 * K, hipMemcpyDeviceToHost, t->stream));
+    RT_HIP(t->err, hipStreamSynchronize(t->stream));
+    return rtree_elapsed(t, ms);
+}
+// operations (indices[i], leaves[i]) applied in order, indices may repeat: paths[i] opens indices[i] in the tree as operations 0 .. i-1 left it,
+// roots[i] is the root after operation i; afterwards the tree is the one built from the final leaves
+int dst_rtree_apply(dst_rtree* t, const uint64_t* indices, const uint8_t* leaves, size_t count, uint8_t* paths, uint8_t* roots) {
+    if (int r = rt_enter(t)) return r;
+    if (count == 0) return DST_OK;
+    if (!indices || !leaves) return rt_fail(t, DST_ERR_ARG, "null pointer");
+    if (count >= ((size_t)1 << 31)) return rt_fail(t, DST_ERR_ARG, "2^31 operations or more");
+    if (!all_leaf_indices(t, indices, count)) return rt_fail(t, DST_ERR_ARG, "leaf index past the end");
+    if (!all_below_p(leaves, 2 * count)) return rt_fail(t, DST_ERR_ARG, "a leaf element is not below the modulus");
+    const size_t n = t->log_leaves + 1;
+    if (t->device < 0) {                                               // one after the other: open, update, root
+        for (size_t i = 0; i < count; i++) {
+            if (paths) { if (int r = rtree_paths(t, indices + i, 1, paths + 32 * n * i)) return r; }
+            if (int r = dst_rtree_update(t, indices + i, leaves + 32 * i, 1)) return r;
+            if (roots) memcpy(roots + 32 * i, t->host.data() + 2, 32);
+        }
+        return DST_OK;
+    }
+    try {
+        const tseq_plan p = tseq_plan_make(t->log_leaves, indices, count, [](uint32_t l, uint64_t q) { return (uint32_t)(((uint64_t)1 << l) + q); });
+        std::vector<uint32_t> spos(p.touched());
+        for (uint32_t l = 0; l <= t->log_leaves; l++)
+            for (size_t j = p.toff[l]; j < p.toff[l] + p.tcnt[l]; j++) spos[j] = (uint32_t)(((uint64_t)1 << l) + p.tpref[j]);
+        const int r = tseq_run_device(t, t->dev, nullptr, p, spos, indices, leaves, paths, roots, &t->update_ms);
+        if (r != DST_OK) { t->broken = true; t->err += "; the sequence did not complete, the tree is unusable"; }
+        return r;
+    } catch (const std::bad_alloc&) { return rt_fail(t, DST_ERR_HIP, "out of host memory"); }      // thrown before anything was queued
 }

@@ -232,3 +232,45 @@ int dst_stree_tapes_many(const dst_stree* t, const uint64_t* indices, size_t cou
     } catch (const std::bad_alloc&) { return st_fail(t, DST_ERR_HIP, "out of host memory"); }
     return DST_OK;
 }
+
+// ---- ordered writes (tree_sequence.h): dst_rtree_apply's semantics; a key that is not stored has the leaf E_depth --------------------------------
+// On a device tree the witnesses are computed against the generation as it is (tseq_run_device: the level launches read it, nothing writes it),
+// then the distinct keys with the value that stays go through dst_stree_set, which states the structure changes.  Source words hold flat
+// positions below TSEQ_EMPTY, so such a tree may store at most 2^31 - 2 nodes.
+int dst_stree_apply(dst_stree* t, const uint64_t* indices, const uint8_t* leaves, size_t count, uint8_t* paths, uint8_t* roots) {
+    if (int r = st_enter(t)) return r;
+    if (count == 0) return DST_OK;
+    if (!indices || !leaves) return st_fail(t, DST_ERR_ARG, "null pointer");
+    if (count >= ((size_t)1 << 31)) return st_fail(t, DST_ERR_ARG, "2^31 operations or more");
+    if (t->shape.total() + count * (t->depth + 1) >= (t->device < 0 ? STREE_NEW : TSEQ_EMPTY)) return st_fail(t, DST_ERR_ARG, "too many stored nodes");
+    if (!all_keys(t, indices, count)) return st_fail(t, DST_ERR_ARG, "index past the end");
+    if (!all_below_p(leaves, 2 * count)) return st_fail(t, DST_ERR_ARG, "a leaf element is not below the modulus");
+    const size_t D = t->depth, n = D + 1;
+    if (t->device < 0) {                                               // one after the other: open, set, root
+        uint64_t digests = 0;
+        for (size_t i = 0; i < count; i++) {
+            if (paths) { if (int r = stree_paths(t, indices + i, 1, paths + 32 * n * i)) return r; }
+            if (int r = dst_stree_set(t, indices + i, leaves + 32 * i, 1)) return r;
+            if (roots) memcpy(roots + 32 * i, t->host.data() + 2 * t->shape.start[0], 32);
+            digests += t->last_digests;
+        }
+        t->last_digests = digests;
+        return DST_OK;
+    }
+    try {
+        const stree_shape& sh = t->shape;
+        const tseq_plan p = tseq_plan_make(t->depth, indices, count, [&](uint32_t l, uint64_t q) {
+            const size_t at = stree_find(sh.pref.data() + sh.start[l], sh.cnt[l], q);
+            return at == STREE_ABSENT ? TSEQ_EMPTY : (uint32_t)(sh.start[l] + at);
+        });
+        const size_t m = p.tcnt[D];                                    // the distinct keys, sorted, and the leaf that stays at each
+        std::vector<uint8_t> last(32 * m);
+        for (size_t j = 0; j < m; j++) memcpy(&last[32 * j], leaves + 32 * (size_t)p.tlast[p.toff[D] + j], 32);
+        double ms = 0;
+        if (int r = tseq_run_device(t, t->dev_nodes(), t->empties, p, {}, indices, leaves, paths, roots, &ms)) return r;      // the tree is as it was
+        if (int r = dst_stree_set(t, p.tpref.data() + p.toff[D], last.data(), m)) return r;
+        t->last_digests += (uint64_t)count * D;
+        t->last_ms += ms;
+        return DST_OK;
+    } catch (const std::bad_alloc&) { return st_fail(t, DST_ERR_HIP, "out of host memory"); }
+}

@@ -9,6 +9,7 @@
 #include "blake3_dev.h"
 #include "rescue_dev.h"
 #include "host/stree_levels.h"
+#include "host/tree_sequence.h"
 #include "host/merkle_plan.h"
 
 #define HASH_THREADS 256
@@ -495,5 +496,80 @@ int k_rescue_stree_carry(hipStream_t stream, fe* dst, const fe* src, const uint3
 int k_rescue_stree_open(hipStream_t stream, const fe* nodes, const uint64_t* pref, const uint64_t* levels, const fe* empties, const uint64_t* indices, fe* out, size_t count, uint32_t depth) {
     const size_t lanes = 2 * count * (depth + 1);
     hipLaunchKernelGGL(rescue_stree_open_kernel, dim3((unsigned)((lanes + HASH_THREADS - 1) / HASH_THREADS)), dim3(HASH_THREADS), 0, stream, nodes, pref, levels, empties, indices, out, count, depth);
+    return hipGetLastError() == hipSuccess ? 0 : -1;
+}
+
+// ---- ordered leaf writes (dst_rtree_apply, dst_stree_apply; host/tree_sequence.h): operation i of `count` has, per level, a version -- the value of
+//      its leaf's ancestor there once operations 0 .. i are applied.  One launch turns the versions of a level (vin, 2 elements each) into those
+//      of the level above (vout): version i = digest of vin[i] and its sibling, which the source word src[i] places -- the version of an earlier
+//      operation in vin, a node of the tree as it was before the call (nodes; read only, a dense node array or a sparse tree's flat array), or
+//      (e0, e1), an empty subtree of the child level.  Bit k - 1 of idx[i] says which child vin[i] is.  The sibling is node k of operation i's
+//      authentication path of n nodes (paths, when asked for); the launch of the leaf level (own != nullptr) also stores node 0, the leaf's value
+//      before operation i, found by own[i] in the same way.  The host has validated the leaves and made every source word. ----------------------
+__device__ __forceinline__ fe rescue_seq_read(const fe* __restrict__ nodes, const fe* __restrict__ vin, uint32_t w, uint32_t elem, fe v /* of an empty subtree */) {
+    if (w != TSEQ_EMPTY) v = *((w & TSEQ_VERSION) ? vin + 2 * (size_t)(w & ~TSEQ_VERSION) + elem : nodes + 2 * (size_t)w + elem);
+    return v;
+}
+// one lane per digest: the lookups and the loads first, only the four inputs live across the digest
+__global__ void __launch_bounds__(RESCUE_THREADS) rescue_seq_level_kernel(const fe* __restrict__ nodes, const fe* __restrict__ vin, fe* __restrict__ vout, const uint32_t* __restrict__ src,
+                                                                         const uint32_t* __restrict__ own, const uint64_t* __restrict__ idx, fe* __restrict__ paths, size_t count,
+                                                                         uint32_t k, uint32_t n, fe e0, fe e1) {
+    const size_t i = (size_t)blockIdx.x * RESCUE_THREADS + threadIdx.x;
+    if (i >= count) return;
+    if (own && paths) {
+        const uint32_t w = own[i];
+        paths[2 * i * n] = rescue_seq_read(nodes, vin, w, 0u, e0);
+        paths[2 * i * n + 1] = rescue_seq_read(nodes, vin, w, 1u, e1);
+    }
+    const uint32_t w = src[i];
+    const bool right = (idx[i] >> (k - 1u)) & 1u;                      // this operation's node is the right child: the sibling goes first
+    const fe s0 = rescue_seq_read(nodes, vin, w, 0u, e0), s1 = rescue_seq_read(nodes, vin, w, 1u, e1);
+    const fe c0 = vin[2 * i], c1 = vin[2 * i + 1];
+    if (paths) { paths[2 * (i * n + k)] = s0; paths[2 * (i * n + k) + 1] = s1; }
+    fe d0, d1;
+    rescue_digest4(rescue_pick(right, s0, c0), rescue_pick(right, s1, c1), rescue_pick(right, c0, s0), rescue_pick(right, c1, s1), d0, d1);
+    vout[2 * i] = d0; vout[2 * i + 1] = d1;
+}
+// the six-lanes-of-eight form (rescue_parent_spread): lanes 5, 4 hold l0, l1 and lanes 3, 2 hold r0, r1, each from the sibling or from vin[i]; lanes
+// 7, 6 of the leaf level's launch copy the old leaf.  A group past the end is given operation 0, keeps the barriers and stores nothing.
+__global__ void __launch_bounds__(RESCUE_THREADS) rescue_seq_level_spread_kernel(const fe* __restrict__ nodes, const fe* __restrict__ vin, fe* __restrict__ vout, const uint32_t* __restrict__ src,
+                                                                                const uint32_t* __restrict__ own, const uint64_t* __restrict__ idx, fe* __restrict__ paths, size_t count,
+                                                                                uint32_t k, uint32_t n, fe e0, fe e1) {
+    __shared__ fe xch[RESCUE_THREADS];
+    const size_t g = (size_t)blockIdx.x * (RESCUE_THREADS / 8u) + (threadIdx.x >> 3);
+    const bool live = g < count;
+    const size_t i = live ? g : 0;
+    const uint32_t e = threadIdx.x & 7u, elem = 1u - (e & 1u);
+    fe v = fe_zero();                                                  // state after hasher.rs:18: (0, 0, r1, r0, l1, l0)
+    if (e >= 6u) {
+        if (live && own && paths) paths[2 * i * n + (e - 6u)] = rescue_seq_read(nodes, vin, own[i], e - 6u, rescue_pick(e == 6u, e0, e1));
+    } else if (e >= 2u) {
+        const bool right = (idx[i] >> (k - 1u)) & 1u;
+        if ((e >= 4u) == right) {                                      // this lane's side is the sibling's
+            v = rescue_seq_read(nodes, vin, src[i], elem, rescue_pick(elem != 0u, e1, e0));
+            if (live && paths) paths[2 * (i * n + k) + elem] = v;
+        } else v = vin[2 * i + elem];
+    }
+    rescue_permute_lane(v, e, xch + (threadIdx.x & ~7u));
+    if (live && (e == 5u || e == 4u)) vout[2 * i + (5u - e)] = v;
+}
+// nodes[pos[i]] = vals[from[i]]: the last versions of a level into a dense node array, two lanes per node
+__global__ void rescue_tree_scatter_from_kernel(fe* __restrict__ nodes, const uint32_t* __restrict__ pos, const fe* __restrict__ vals, const uint32_t* __restrict__ from, size_t count) {
+    const size_t t = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (t >= 2 * count) return;
+    nodes[2 * (size_t)pos[t >> 1] + (t & 1)] = vals[2 * (size_t)from[t >> 1] + (t & 1)];
+}
+
+int k_rescue_seq_level(hipStream_t stream, const fe* nodes, const fe* vin, fe* vout, const uint32_t* src, const uint32_t* own, const uint64_t* idx, fe* paths, size_t count, uint32_t k, uint32_t n,
+                       const fe* empty) {
+    const bool spread = count <= RESCUE_SPREAD_MAX;
+    const size_t per_block = spread ? RESCUE_THREADS / 8 : RESCUE_THREADS;
+    const dim3 grid((unsigned)((count + per_block - 1) / per_block)), block(RESCUE_THREADS);
+    if (spread) hipLaunchKernelGGL(rescue_seq_level_spread_kernel, grid, block, 0, stream, nodes, vin, vout, src, own, idx, paths, count, k, n, empty[0], empty[1]);
+    else hipLaunchKernelGGL(rescue_seq_level_kernel, grid, block, 0, stream, nodes, vin, vout, src, own, idx, paths, count, k, n, empty[0], empty[1]);
+    return hipGetLastError() == hipSuccess ? 0 : -1;
+}
+int k_rescue_tree_scatter_from(hipStream_t stream, fe* nodes, const uint32_t* pos, const fe* vals, const uint32_t* from, size_t count) {
+    hipLaunchKernelGGL(rescue_tree_scatter_from_kernel, dim3((unsigned)((2 * count + HASH_THREADS - 1) / HASH_THREADS)), dim3(HASH_THREADS), 0, stream, nodes, pos, vals, from, count);
     return hipGetLastError() == hipSuccess ? 0 : -1;
 }

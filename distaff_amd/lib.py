@@ -59,7 +59,7 @@ EXPORTS = ["dst_ctx_create", "dst_ctx_destroy", "dst_last_error", "dst_phase_ms"
            "dst_rescue_digest_many", "dst_rtree_build", "dst_rtree_root", "dst_rtree_path", "dst_rtree_tapes", "dst_rtree_read_nodes", "dst_rtree_build_ms",
            "dst_rtree_destroy", "dst_rtree_last_error", "dst_rtree_update", "dst_rtree_update_ms", "dst_rtree_paths", "dst_rtree_tapes_many",
            "dst_stree_create", "dst_stree_set", "dst_stree_root", "dst_stree_paths", "dst_stree_tapes_many", "dst_stree_read_level", "dst_stree_info",
-           "dst_stree_destroy", "dst_stree_last_error"]
+           "dst_stree_destroy", "dst_stree_last_error", "dst_rtree_apply", "dst_stree_apply", "dst_rescue_path_tapes"]
 
 
 class DistaffError(RuntimeError):
@@ -285,6 +285,49 @@ def rescue_digest(values, device=0, lib=None):
     return out
 
 
+def path_tapes(paths, indices, what=3, lib=None):
+    """RescueTree.tapes_many over paths the caller holds (dst_rescue_path_tapes; host only, no tree): `paths` as paths() or apply() return them
+    -- a list with one list of n pairs of ints per index -- or uint64 words [count, n, 2, 2] -> a list of (A, B)"""
+    lib = lib or load()
+    idx, ip = RescueTree._indices(indices)
+    if isinstance(paths, np.ndarray) and paths.dtype == np.uint64 and paths.ndim == 4:
+        w = np.ascontiguousarray(paths)
+    else:
+        rows = [list(path) for path in paths]
+        if len({len(r) for r in rows}) > 1:
+            raise DistaffError(DST_ERR_ARG, "paths of one length")
+        if not rows and not idx.size:
+            return []
+        w = _elements([node for r in rows for node in r], 2).reshape(len(rows), -1, 2, 2)
+    if w.shape[0] != idx.size:
+        raise DistaffError(DST_ERR_ARG, "as many paths as indices")
+    nodes = ctypes.c_uint32(w.shape[1])
+    n = ctypes.c_size_t(0)
+    r = lib.dst_rescue_path_tapes(_ptr(w) if idx.size else None, nodes, ip, ctypes.c_size_t(idx.size), ctypes.c_uint32(what), None, None, ctypes.c_size_t(0), ctypes.byref(n))
+    if r == DST_OK:
+        each = n.value
+        a = np.zeros((max(idx.size * each, 1), 2), dtype=np.uint64)
+        b = np.zeros((max(idx.size * each, 1), 2), dtype=np.uint64)
+        r = lib.dst_rescue_path_tapes(_ptr(w) if idx.size else None, nodes, ip, ctypes.c_size_t(idx.size), ctypes.c_uint32(what), _ptr(a), _ptr(b), ctypes.c_size_t(each), ctypes.byref(n))
+    if r != DST_OK:
+        raise DistaffError(r, _rtree_error(lib) or "dst_rescue_path_tapes failed")
+    va, vb = arr_to_ints(a[:idx.size * each]), arr_to_ints(b[:idx.size * each])
+    return [(va[i * each:(i + 1) * each], vb[i * each:(i + 1) * each]) for i in range(idx.size)]
+
+
+def _apply(tree, call, n, indices, leaves):
+    """(paths, roots) of an ordered batch of writes: paths in the shape paths() returns, roots a list of pairs of ints"""
+    idx, ip = RescueTree._indices(indices)
+    a = _elements(leaves, 2)
+    if a.shape[0] != idx.size:
+        raise DistaffError(DST_ERR_ARG, "as many leaves as indices")
+    paths = np.zeros((max(idx.size, 1) * n, 2, 2), dtype=np.uint64)
+    roots = np.zeros((max(idx.size, 1), 2, 2), dtype=np.uint64)
+    tree._check(call(tree._h, ip, _ptr(a) if idx.size else None, ctypes.c_size_t(idx.size), _ptr(paths), _ptr(roots)))
+    v, r = arr_to_ints(paths[:idx.size * n]), arr_to_ints(roots[:idx.size])
+    return ([[(v[2 * (i * n + k)], v[2 * (i * n + k) + 1]) for k in range(n)] for i in range(idx.size)], [(r[2 * i], r[2 * i + 1]) for i in range(idx.size)])
+
+
 class RescueTree:
     """A Merkle tree of the kind the VM's smpath.n / pmpath.n authenticate (``dst_rtree``): nodes of two field elements, parent =
     hasher::digest(l0, l1, r0, r1).  `leaves`: a sequence of 2^k pairs of ints or uint64 words [2^k, 2, 2], 1 <= k <= 26.  device >= 0 builds
@@ -362,9 +405,15 @@ class RescueTree:
             raise DistaffError(DST_ERR_ARG, "as many leaves as indices")
         self._check(self.lib.dst_rtree_update(self._h, ip, _ptr(a) if idx.size else None, ctypes.c_size_t(idx.size)))
 
+    def apply(self, indices, leaves):
+        """the writes leaf indices[i] <- leaves[i] one after the other, indices may repeat (dst_rtree_apply) -> (paths, roots): paths[i] opens
+        indices[i] in the tree as the earlier writes left it (its first node is the old leaf), roots[i] is the root after write i.  On a device
+        tree all writes are hashed together, one launch per level."""
+        return _apply(self, self.lib.dst_rtree_apply, self.log_leaves + 1, indices, leaves)
+
     @property
     def update_ms(self):
-        """device milliseconds of the level launches of the last update (0 for a host tree)"""
+        """device milliseconds of the level launches of the last update or apply (0 for a host tree)"""
         ms = ctypes.c_double(0)
         self._check(self.lib.dst_rtree_update_ms(self._h, ctypes.byref(ms)))
         return ms.value
@@ -444,6 +493,11 @@ class SparseRescueTree:
         if a.shape[0] != idx.size:
             raise DistaffError(DST_ERR_ARG, "as many leaves as indices")
         self._check(self.lib.dst_stree_set(self._h, ip, _ptr(a) if idx.size else None, ctypes.c_size_t(idx.size)))
+
+    def apply(self, indices, leaves):
+        """RescueTree.apply on keys below 2^depth, stored or not (dst_stree_apply) -> (paths, roots); the old leaf of a key that is not stored is
+        the empty leaf.  Afterwards the tree is set()'s of the distinct keys with the later value of each."""
+        return _apply(self, self.lib.dst_stree_apply, self.depth + 1, indices, leaves)
 
     @property
     def root(self):

@@ -181,7 +181,7 @@ DST_API int dst_rtree_build_ms(const dst_rtree* t, double* device_ms);
  * is queued, so the tree is unchanged after DST_ERR_ARG.  count = 0: DST_OK, nothing happens.  A HIP error during the update leaves the tree
  * unusable: dst_rtree_last_error says so, and every later call on it except dst_rtree_destroy and dst_rtree_last_error returns DST_ERR_STATE. */
 DST_API int dst_rtree_update(dst_rtree* t, const uint64_t* indices, const uint8_t* leaves, size_t count);
-/* device milliseconds of the level launches of the last dst_rtree_update (events on the library's stream, as dst_rtree_build_ms; 0 for a host tree) */
+/* device milliseconds of the level launches of the last dst_rtree_update or dst_rtree_apply (events on the library's stream, as dst_rtree_build_ms; 0 for a host tree) */
 DST_API int dst_rtree_update_ms(const dst_rtree* t, double* device_ms);
 /* authentication paths of `count` leaves, (log_leaves + 1) * 32 bytes each, in the order of `indices` (repeats allowed); the layout of each is
  * dst_rtree_path's (merkle.rs:98-145).  On a device tree: one upload of the node positions, one gather launch, one copy back, whatever count is. */
@@ -190,8 +190,25 @@ DST_API int dst_rtree_paths(const dst_rtree* t, const uint64_t* indices, size_t 
  * block i for indices[i]; cap_elems_each >= *elems_each; tape_a = tape_b = NULL: size query */
 DST_API int dst_rtree_tapes_many(const dst_rtree* t, const uint64_t* indices, size_t count, uint32_t what,
                                  uint8_t* tape_a, uint8_t* tape_b, size_t cap_elems_each, size_t* elems_each);
+/* An ORDERED batch of leaf writes, what a host that keeps state performs: operation i replaces leaf indices[i] by leaves[i] in the tree as
+ * operations 0 .. i-1 left it; indices may repeat and come in any order.  paths[i] (may be NULL) is the authentication path of indices[i] in the
+ * tree BEFORE operation i, in dst_rtree_path's layout: its first node is the old leaf, and its siblings are those of the path after the write
+ * too, so the one path serves "old leaf under the previous root" and "new leaf under roots[i]".  roots[i] (may be NULL) is the root after
+ * operation i; the root before operation 0 is dst_rtree_root before the call.  Afterwards every node equals that of a tree built from the final
+ * leaves.  On a device tree all operations are hashed together, one launch per level: log_leaves level launches and as many scatters, one
+ * upload, one synchronisation, whatever count is (dst_rtree_update_ms then reports these launches).  A host tree applies them one after the
+ * other.  DST_ERR_ARG -- a null pointer with count > 0, an index past the end, a leaf element not below p, count >= 2^31 -- is found on the host
+ * before anything is queued and leaves the tree unchanged; count = 0: DST_OK, nothing happens; a HIP error leaves the tree unusable as in
+ * dst_rtree_update. */
+DST_API int dst_rtree_apply(dst_rtree* t, const uint64_t* indices, const uint8_t* leaves /* count*32 */, size_t count,
+                            uint8_t* paths /* count*(log_leaves+1)*32, or NULL */, uint8_t* roots /* count*32, or NULL */);
+/* host only, no tree: dst_rtree_tapes_many (generate_program_inputs, merkle.rs:63-94) over `count` paths of n nodes each that the caller holds
+ * -- the witnesses of dst_rtree_apply / dst_stree_apply, or paths from anywhere; 2 <= n <= 64, indices[i] below 2^(n-1).  The same `what`, the
+ * same size query.  Errors are reported by dst_rtree_last_error(NULL). */
+DST_API int dst_rescue_path_tapes(const uint8_t* paths /* count*n*32 */, uint32_t n, const uint64_t* indices, size_t count, uint32_t what,
+                                  uint8_t* tape_a, uint8_t* tape_b, size_t cap_elems_each, size_t* elems_each);
 DST_API void dst_rtree_destroy(dst_rtree* t);
-DST_API const char* dst_rtree_last_error(const dst_rtree* t);     /* t may be NULL: the error of the calling thread's last failed dst_rtree_build / dst_rescue_digest_many */
+DST_API const char* dst_rtree_last_error(const dst_rtree* t);     /* t may be NULL: the error of the calling thread's last failed dst_rtree_build / dst_rescue_digest_many / dst_rescue_path_tapes */
 
 /* ---- sparse Rescue Merkle trees: a set addressed by keys of up to 63 bits (accounts, notes, nullifiers) ------------------------------------
  * A sparse tree of depth D, 1 <= D <= 63, IS the dense tree above over 2^D leaves in which every leaf that was never set holds the tree's empty
@@ -219,6 +236,13 @@ DST_API int dst_stree_root(const dst_stree* t, uint8_t root[32]);
  * not stored is the E_l of its level; a path whose leaf is E_depth proves that the key is empty.  On a device tree: one upload, one launch, one
  * copy back, whatever count is. */
 DST_API int dst_stree_paths(const dst_stree* t, const uint64_t* indices, size_t count, uint8_t* paths /* count*(depth+1)*32 */);
+/* dst_rtree_apply on a sparse tree: ordered writes to keys below 2^depth, stored or not, repeats allowed; paths of depth + 1 nodes.  The old leaf
+ * of a key that is not stored before operation i is E_depth, a sibling subtree without keys the E_l of its level.  Afterwards the tree is what
+ * dst_stree_set makes of the distinct keys with the later value of each (a key written with the empty value stays stored).  On a device tree: depth
+ * level launches compute every witness against the stored generation, then that one set runs; last_digests = count * depth + the set's digests,
+ * last_device_ms the sum of both.  DST_ERR_ARG as dst_rtree_apply, and a device tree that would pass 2^31 - 2 stored nodes. */
+DST_API int dst_stree_apply(dst_stree* t, const uint64_t* indices, const uint8_t* leaves /* count*32 */, size_t count,
+                            uint8_t* paths /* count*(depth+1)*32, or NULL */, uint8_t* roots /* count*32, or NULL */);
 /* dst_rtree_tapes_many with n = depth + 1: the same `what`, the same size query */
 DST_API int dst_stree_tapes_many(const dst_stree* t, const uint64_t* indices, size_t count, uint32_t what,
                                  uint8_t* tape_a, uint8_t* tape_b, size_t cap_elems_each, size_t* elems_each);
@@ -230,7 +254,7 @@ typedef struct dst_stree_info_t {
     uint32_t depth;
     int32_t device;                     /* -1: a host tree */
     uint64_t keys, nodes;               /* stored keys; stored nodes of all levels, the leaves included */
-    uint64_t last_digests;              /* digests computed by the last dst_stree_set */
+    uint64_t last_digests;              /* digests computed by the last dst_stree_set / dst_stree_apply */
     double last_device_ms;              /* events around that call's level launches, as dst_rtree_update_ms; 0 on a host tree */
 } dst_stree_info_t;
 DST_API int dst_stree_info(const dst_stree* t, dst_stree_info_t* out);

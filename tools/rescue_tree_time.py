@@ -4,6 +4,8 @@ device's own modular-multiplication rate sets.
     python tools/rescue_tree_time.py [--host-log 12] [--lib path/to/another/build.so] [log_leaves ...]        (default 12 16 20)
     python tools/rescue_tree_time.py --update        updates in place and batched openings on the 2^20 tree instead (dst_rtree_update_ms)
     python tools/rescue_tree_time.py --sparse        sparse trees of depth 63 instead (dst_stree_set, dst_stree_paths), beside a dense 2^20 build
+    python tools/rescue_tree_time.py --sequence      ordered writes with a witness each (dst_rtree_apply on the 2^20 tree, dst_stree_apply on a depth-63 tree
+                                                     of 2^20 keys), beside the loop of single-leaf updates and single paths they replace
 One digest is counted as 9 180 field multiplications, the reference's own count per hasher::digest: ten rounds of 6 x 2 for the cubes, 6 x 139
 for x^INV_ALPHA by the addition chain (127 squarings + 12 multiplications) and 2 x 36 for the two MDS products."""
 import argparse
@@ -24,6 +26,7 @@ ap.add_argument("--lib", default=None, help="another build of the library (a dif
 ap.add_argument("--runs", type=int, default=5)
 ap.add_argument("--update", action="store_true", help="time dst_rtree_update (k = 1, 256, 65 536 leaves) and dst_rtree_paths on the 2^20 tree instead of builds")
 ap.add_argument("--sparse", action="store_true", help="time dst_stree_set (2^12, 2^16, 2^20 keys into an empty depth-63 tree; 1, 256, 65 536 keys into the 2^20-key tree) and dst_stree_paths")
+ap.add_argument("--sequence", action="store_true", help="time dst_rtree_apply / dst_stree_apply (1, 256, 4 096, 65 536 ordered writes) and, for 256, the loop of update + path calls")
 ap.add_argument("sizes", nargs="*", type=int)
 args = ap.parse_args()
 lib = D.lib._open(os.path.abspath(args.lib)) if args.lib else None       # through the binding: one HIP runtime per process
@@ -157,6 +160,83 @@ if args.sparse:
     t0 = time.perf_counter(); w = big.paths_words(idx); s_many = time.perf_counter() - t0
     print("dst_stree_paths of %d indices (half stored, half absent) on the %d-key tree: %.3f ms wall (%d nodes of %d searched levels each)" % (idx.size, big.info()["keys"], s_many * 1e3, DEPTH + 1, DEPTH + 1))
     big.close()
+    sys.exit(0)
+if args.sequence:
+    import ctypes
+    SEQUENCE_SEED, DEPTH = 3030, 63
+    vp = lambda x: x.ctypes.data_as(ctypes.c_void_p)  # noqa: E731
+
+    def operations(rng, count, draw):
+        """`count` indices from draw(count), about a tenth of them replaced by an earlier index of the same sequence, and as many leaves"""
+        idx = draw(count)
+        again = np.nonzero(rng.random(count) < 0.1)[0]
+        again = again[again > 0]
+        idx[again] = idx[(rng.random(again.size) * again).astype(np.int64)]
+        new = rng.integers(0, 1 << 64, size=(count, 2, 2), dtype=np.uint64)
+        new[..., 1] >>= np.uint64(1)
+        return np.ascontiguousarray(idx), new
+
+    def time_applies(name, tree, apply, n, draw, device_ms, note=lambda: ""):
+        """the C call alone: wall = the host clock around it (plan, upload, launches, copy back of count * n nodes and count roots)"""
+        rng = np.random.default_rng(SEQUENCE_SEED)
+        for count in (1, 256, 4096, 65536):
+            ms, wall = [], []
+            for _ in range(1 + args.runs):          # the first is the warm-up: staging buffer, code
+                idx, new = operations(rng, count, draw)
+                paths, roots = np.zeros((count, n, 2, 2), dtype=np.uint64), np.zeros((count, 2, 2), dtype=np.uint64)
+                t0 = time.perf_counter()
+                r = apply(tree._h, vp(idx), vp(new), ctypes.c_size_t(count), vp(paths), vp(roots))
+                wall.append((time.perf_counter() - t0) * 1e3)
+                assert r == 0 and tuple(D.arr_to_ints(roots[-1])) == tree.root
+                ms.append(device_ms())
+            ms, wall = ms[1:], wall[1:]
+            print("%s: apply of %d ordered writes (%d distinct indices): %.3f ms on the device (min of %d after one warm-up; all: %s) = %.3f ms per level; %.2f ms wall (min; all: %s)%s"
+                  % (name, count, np.unique(idx).size, min(ms), len(ms), " ".join("%.3f" % v for v in ms), min(ms) / (n - 1), min(wall), " ".join("%.2f" % v for v in wall), note()))
+
+    def time_loop(name, count, idx, new, one_write, one_path, n):
+        """the baseline: per operation one path of one leaf, then one write of one leaf, through the calls that existed before"""
+        path = np.zeros((n, 2, 2), dtype=np.uint64)
+        t0 = time.perf_counter()
+        r = 0
+        for j in range(count):
+            r |= one_path(idx[j:j + 1], path)
+            r |= one_write(idx[j:j + 1], new[j:j + 1])
+        wall = (time.perf_counter() - t0) * 1e3
+        assert r == 0
+        print("%s: the loop of %d x (single path + single-leaf write): %.1f ms wall, %.3f ms per operation" % (name, count, wall, wall / count))
+
+    log_leaves = 20
+    a = leaves(log_leaves)
+    t = D.RescueTree(a, device=0, lib=lib)
+    L = t.lib
+    rng = np.random.default_rng(SEQUENCE_SEED + 1)
+    dense_draw = lambda count: rng.integers(0, 1 << log_leaves, size=count).astype(np.uint64)  # noqa: E731
+    time_applies("dense 2^%d leaves" % log_leaves, t, L.dst_rtree_apply, log_leaves + 1, dense_draw, lambda: t.update_ms)
+    idx, new = operations(rng, 256, dense_draw)
+    time_loop("dense 2^%d leaves" % log_leaves, 256, idx, new, lambda i, v: L.dst_rtree_update(t._h, vp(i), vp(v), ctypes.c_size_t(1)),
+              lambda i, out: L.dst_rtree_path(t._h, ctypes.c_uint64(int(i[0])), vp(out)), log_leaves + 1)
+    t.close()
+    keys = np.unique(rng.integers(0, 1 << DEPTH, size=(1 << 20) + (1 << 17), dtype=np.uint64))
+    rng.shuffle(keys)
+    keys = keys[:1 << 20]
+    v = rng.integers(0, 1 << 64, size=(keys.size, 2, 2), dtype=np.uint64)
+    v[..., 1] >>= np.uint64(1)
+    s = D.SparseRescueTree(DEPTH, device=0, lib=lib)
+    s.set(keys, v)
+    print("sparse depth %d: %d keys, %d stored nodes" % (DEPTH, s.info()["keys"], s.info()["nodes"]))
+
+    def sparse_draw(count):                         # half stored keys, half new ones
+        idx = rng.integers(0, 1 << DEPTH, size=count, dtype=np.uint64)
+        stored = np.nonzero(rng.random(count) < 0.5)[0]
+        idx[stored] = keys[rng.integers(0, keys.size, size=stored.size)]
+        return idx
+
+    time_applies("sparse depth %d, 2^20 keys" % DEPTH, s, L.dst_stree_apply, DEPTH + 1, sparse_draw, lambda: s.info()["last_device_ms"],
+                lambda: "; %d digests: 63 per write, then one dst_stree_set of the distinct keys, whose 63 level launches the device time includes" % s.info()["last_digests"])
+    idx, new = operations(rng, 256, sparse_draw)
+    time_loop("sparse depth %d, 2^20 keys" % DEPTH, 256, idx, new, lambda i, w: L.dst_stree_set(s._h, vp(i), vp(w), ctypes.c_size_t(1)),
+              lambda i, out: L.dst_stree_paths(s._h, vp(i), ctypes.c_size_t(1), vp(out)), DEPTH + 1)
+    s.close()
     sys.exit(0)
 for log_leaves in args.sizes or [12, 16, 20]:
     a = leaves(log_leaves)

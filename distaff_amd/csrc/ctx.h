@@ -496,3 +496,8 @@ int k_rescue_stree_open(hipStream_t stream, const fe* nodes, const uint64_t* pre
 int k_rescue_seq_level(hipStream_t stream, const fe* nodes, const fe* vin, fe* vout, const uint32_t* src, const uint32_t* own, const uint64_t* idx, fe* paths, size_t count, uint32_t k, uint32_t n,
                        const fe* empty);
 int k_rescue_tree_scatter_from(hipStream_t stream, fe* nodes, const uint32_t* pos, const fe* vals, const uint32_t* from /* device */, size_t count);      // nodes[pos[i]] = vals[from[i]]
+// compute_merkle_root (src/examples/merkle.rs:112-145) of `count` paths of n nodes (all device): ONE launch for every level of every chain.  mode:
+// the paths with their own leaves, with alt_leaves[i] as the first node instead, or both -- 2 count chains over one copy of the paths, out[0 .. count)
+// the own-leaf roots and out[count .. 2 count) the substitute-leaf roots
+enum { RESCUE_PATH_OWN = 0, RESCUE_PATH_ALT = 1, RESCUE_PATH_BOTH = 2 };
+int k_rescue_path_roots(hipStream_t stream, const fe* paths, uint32_t n, const uint64_t* indices, size_t count, const fe* alt_leaves, uint32_t mode, fe* out /* 2 per chain */, uint32_t* bad);

@@ -49,7 +49,8 @@ static bool all_leaf_indices(const dst_rtree* t, const uint64_t* indices, size_t
 }
 struct rt_scratch {                                    // the stream and the device buffer of a call without a tree
     hipStream_t s = nullptr; uint8_t* p = nullptr;
-    ~rt_scratch() { if (p) hipFree(p); if (s) hipStreamDestroy(s); }
+    hipEvent_t ev[2] = {nullptr, nullptr};             // around the launch, where the call reports device milliseconds
+    ~rt_scratch() { if (p) hipFree(p); for (hipEvent_t e : ev) if (e) hipEventDestroy(e); if (s) hipStreamDestroy(s); }
 };
 
 // utils::hasher::digest (src/utils/hasher.rs:12)

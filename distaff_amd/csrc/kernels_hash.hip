@@ -573,3 +573,81 @@ int k_rescue_tree_scatter_from(hipStream_t stream, fe* nodes, const uint32_t* po
     hipLaunchKernelGGL(rescue_tree_scatter_from_kernel, dim3((unsigned)((2 * count + HASH_THREADS - 1) / HASH_THREADS)), dim3(HASH_THREADS), 0, stream, nodes, pos, vals, from, count);
     return hipGetLastError() == hipSuccess ? 0 : -1;
 }
+
+// ---- checking paths (dst_rescue_path_roots, dst_rescue_verify_paths, dst_rescue_verify_writes; host/path_verify.h): a chain is compute_merkle_root
+//      (src/examples/merkle.rs:112-145) of one path of n nodes and one index -- n - 1 dependent digests, the first over (leaf, path[1]) ordered by
+//      bit 0 of the index, digest k over the running value and path[k] ordered by bit k - 1.  All chains of a call are independent: ONE launch runs
+//      every level of every chain.  `mode` says which chains there are: the `count` paths with their own first node as the leaf
+//      (RESCUE_PATH_OWN), with alt[i] in its place (RESCUE_PATH_ALT), or both over one copy of the paths (RESCUE_PATH_BOTH: chain c < count is
+//      path c with its own leaf, chain count + i path i with alt[i]).  out[c] = what chain c resolves to; `bad` receives 1 when an element a
+//      chain reads -- its leaf, every sibling -- is not below p. ---------------------------------------------------------------------------------
+// the six-lanes-of-eight form (rescue_parent_spread): lanes 5, 4 hold l0, l1 and lanes 3, 2 hold r0, r1.  After the permutation the digest sits in
+// lanes 5, 4; it reaches the side bit k - 1 of the index names through the group's LDS slots 5, 4, and the other side loads path[k].  A group past
+// the end is given chain 0, keeps the barriers and stores nothing.
+__global__ void __launch_bounds__(RESCUE_THREADS) rescue_path_root_spread_kernel(const fe* __restrict__ paths, uint32_t n, const uint64_t* __restrict__ indices, size_t count,
+                                                                                const fe* __restrict__ alt, uint32_t mode, size_t chains, fe* __restrict__ out, uint32_t* __restrict__ bad) {
+    __shared__ fe xch[RESCUE_THREADS];
+    const size_t g = (size_t)blockIdx.x * (RESCUE_THREADS / 8u) + (threadIdx.x >> 3);
+    const bool live = g < chains;
+    const size_t c = live ? g : 0, i = c < count ? c : c - count;
+    const bool sub = mode == RESCUE_PATH_ALT || c >= count;
+    const uint32_t e = threadIdx.x & 7u, elem = 1u - (e & 1u);
+    const bool works = e >= 2u && e < 6u;
+    fe* const xs = xch + (threadIdx.x & ~7u);
+    const fe* const path = paths + 2 * i * n;
+    const uint64_t idx = indices[i];
+    fe v = fe_zero();                                                  // state after hasher.rs:18: (0, 0, r1, r0, l1, l0)
+    if (works) {
+        const bool right = idx & 1u;                                   // the leaf is the right child: the sibling goes first
+        v = (e >= 4u) == right ? path[2 + elem] : sub ? alt[2 * i + elem] : path[elem];
+        if (live && !rescue_canonical(v)) *bad = 1u;
+    }
+    rescue_permute_lane(v, e, xs);
+#pragma unroll 1
+    for (uint32_t k = 2; k < n; k++) {
+        if (e == 5u || e == 4u) xs[e] = v;
+        __syncthreads();
+        v = fe_zero();
+        if (works) {
+            const bool right = (idx >> (k - 1u)) & 1u;
+            if ((e >= 4u) == right) {
+                v = path[2 * k + elem];
+                if (live && !rescue_canonical(v)) *bad = 1u;
+            } else v = xs[4u + (e & 1u)];
+        }
+        __syncthreads();                                               // the digest has been read before the permutation writes the slots again
+        rescue_permute_lane(v, e, xs);
+    }
+    if (live && (e == 5u || e == 4u)) out[2 * c + (5u - e)] = v;
+}
+// one chain per lane, for more chains than RESCUE_SPREAD_MAX: the digest is stated once, in a loop over the levels; only the running digest, the
+// index and the chain's base address live across it.  Lanes read their paths n * 32 bytes apart: a level is milliseconds of arithmetic.
+__global__ void __launch_bounds__(RESCUE_THREADS) rescue_path_root_kernel(const fe* __restrict__ paths, uint32_t n, const uint64_t* __restrict__ indices, size_t count,
+                                                                         const fe* __restrict__ alt, uint32_t mode, size_t chains, fe* __restrict__ out, uint32_t* __restrict__ bad) {
+    const size_t c = (size_t)blockIdx.x * RESCUE_THREADS + threadIdx.x;
+    if (c >= chains) return;
+    const size_t i = c < count ? c : c - count;
+    const fe* const path = paths + 2 * i * n;
+    const fe* const leaf = (mode == RESCUE_PATH_ALT || c >= count) ? alt + 2 * i : path;
+    const uint64_t idx = indices[i];
+    fe d0 = leaf[0], d1 = leaf[1];
+    if (!(rescue_canonical(d0) && rescue_canonical(d1))) *bad = 1u;
+#pragma unroll 1
+    for (uint32_t k = 1; k < n; k++) {
+        const fe s0 = path[2 * k], s1 = path[2 * k + 1];
+        if (!(rescue_canonical(s0) && rescue_canonical(s1))) *bad = 1u;
+        const bool right = (idx >> (k - 1u)) & 1u;                     // the running node is the right child: the sibling goes first
+        const fe c0 = d0, c1 = d1;
+        rescue_digest4(rescue_pick(right, s0, c0), rescue_pick(right, s1, c1), rescue_pick(right, c0, s0), rescue_pick(right, c1, s1), d0, d1);
+    }
+    out[2 * c] = d0; out[2 * c + 1] = d1;
+}
+int k_rescue_path_roots(hipStream_t stream, const fe* paths, uint32_t n, const uint64_t* indices, size_t count, const fe* alt_leaves, uint32_t mode, fe* out, uint32_t* bad) {
+    const size_t chains = mode == RESCUE_PATH_BOTH ? 2 * count : count;
+    const bool spread = chains <= RESCUE_SPREAD_MAX;
+    const size_t per_block = spread ? RESCUE_THREADS / 8 : RESCUE_THREADS;
+    const dim3 grid((unsigned)((chains + per_block - 1) / per_block)), block(RESCUE_THREADS);
+    if (spread) hipLaunchKernelGGL(rescue_path_root_spread_kernel, grid, block, 0, stream, paths, n, indices, count, alt_leaves, mode, chains, out, bad);
+    else hipLaunchKernelGGL(rescue_path_root_kernel, grid, block, 0, stream, paths, n, indices, count, alt_leaves, mode, chains, out, bad);
+    return hipGetLastError() == hipSuccess ? 0 : -1;
+}

@@ -59,7 +59,8 @@ EXPORTS = ["dst_ctx_create", "dst_ctx_destroy", "dst_last_error", "dst_phase_ms"
            "dst_rescue_digest_many", "dst_rtree_build", "dst_rtree_root", "dst_rtree_path", "dst_rtree_tapes", "dst_rtree_read_nodes", "dst_rtree_build_ms",
            "dst_rtree_destroy", "dst_rtree_last_error", "dst_rtree_update", "dst_rtree_update_ms", "dst_rtree_paths", "dst_rtree_tapes_many",
            "dst_stree_create", "dst_stree_set", "dst_stree_root", "dst_stree_paths", "dst_stree_tapes_many", "dst_stree_read_level", "dst_stree_info",
-           "dst_stree_destroy", "dst_stree_last_error", "dst_rtree_apply", "dst_stree_apply", "dst_rescue_path_tapes"]
+           "dst_stree_destroy", "dst_stree_last_error", "dst_rtree_apply", "dst_stree_apply", "dst_rescue_path_tapes",
+           "dst_rescue_path_roots", "dst_rescue_verify_paths", "dst_rescue_verify_writes"]
 
 
 class DistaffError(RuntimeError):
@@ -290,18 +291,8 @@ def path_tapes(paths, indices, what=3, lib=None):
     -- a list with one list of n pairs of ints per index -- or uint64 words [count, n, 2, 2] -> a list of (A, B)"""
     lib = lib or load()
     idx, ip = RescueTree._indices(indices)
-    if isinstance(paths, np.ndarray) and paths.dtype == np.uint64 and paths.ndim == 4:
-        w = np.ascontiguousarray(paths)
-    else:
-        rows = [list(path) for path in paths]
-        if len({len(r) for r in rows}) > 1:
-            raise DistaffError(DST_ERR_ARG, "paths of one length")
-        if not rows and not idx.size:
-            return []
-        w = _elements([node for r in rows for node in r], 2).reshape(len(rows), -1, 2, 2)
-    if w.shape[0] != idx.size:
-        raise DistaffError(DST_ERR_ARG, "as many paths as indices")
-    nodes = ctypes.c_uint32(w.shape[1])
+    w, n_nodes = _path_words(paths, idx.size)
+    nodes = ctypes.c_uint32(n_nodes)
     n = ctypes.c_size_t(0)
     r = lib.dst_rescue_path_tapes(_ptr(w) if idx.size else None, nodes, ip, ctypes.c_size_t(idx.size), ctypes.c_uint32(what), None, None, ctypes.c_size_t(0), ctypes.byref(n))
     if r == DST_OK:
@@ -313,6 +304,97 @@ def path_tapes(paths, indices, what=3, lib=None):
         raise DistaffError(r, _rtree_error(lib) or "dst_rescue_path_tapes failed")
     va, vb = arr_to_ints(a[:idx.size * each]), arr_to_ints(b[:idx.size * each])
     return [(va[i * each:(i + 1) * each], vb[i * each:(i + 1) * each]) for i in range(idx.size)]
+
+
+DST_PATH_OK, DST_PATH_BAD_LEAF, DST_PATH_BAD_ROOT, DST_PATH_BAD_NEXT_ROOT = 0, 1, 2, 3      # `why` of verify_paths / verify_writes
+
+
+def _path_words(paths, count):
+    """-> (uint64 words [count, n, 2, 2], n) from paths in either shape path_tapes accepts; no path at all counts as paths of 2 nodes"""
+    if isinstance(paths, np.ndarray) and paths.dtype == np.uint64 and paths.ndim == 4:
+        w = np.ascontiguousarray(paths)
+    else:
+        rows = [list(path) for path in paths]
+        if len({len(r) for r in rows}) > 1:
+            raise DistaffError(DST_ERR_ARG, "paths of one length")
+        w = _elements([node for r in rows for node in r], 2).reshape(len(rows), -1, 2, 2) if rows else np.zeros((0, 2, 2, 2), dtype=np.uint64)
+    if w.shape[0] != count:
+        raise DistaffError(DST_ERR_ARG, "as many paths as indices")
+    return w, w.shape[1]
+
+
+def _nodes_for(values, count, what):
+    """uint64 words [count, 2, 2] of `count` nodes (pairs of ints, or such words)"""
+    a = _elements(values, 2)
+    if a.shape[0] != count:
+        raise DistaffError(DST_ERR_ARG, "as many %s as indices" % what)
+    return a
+
+
+def _pairs(words):
+    v = arr_to_ints(words)
+    return [(v[2 * i], v[2 * i + 1]) for i in range(len(v) // 2)]
+
+
+def path_roots(paths, indices, leaves=None, device=0, lib=None, stats=None):
+    """compute_merkle_root (src/examples/merkle.rs:112-145) of every path with its index (dst_rescue_path_roots) -> a list of pairs of ints: what
+    path i resolves to, or with `leaves` what it resolves to with leaves[i] as its first node.  `paths` as path_tapes takes them, what paths()
+    and apply() return included.  device >= 0: one launch on that GPU for all paths; device < 0: on the host.  stats (a dict) receives device_ms."""
+    lib = lib or load()
+    idx, ip = RescueTree._indices(indices)
+    w, n = _path_words(paths, idx.size)
+    alt = _nodes_for(leaves, idx.size, "leaves") if leaves is not None else None
+    out = np.zeros((max(idx.size, 1), 2, 2), dtype=np.uint64)
+    ms = ctypes.c_double(0)
+    r = lib.dst_rescue_path_roots(ctypes.c_int(device), _ptr(w) if idx.size else None, ctypes.c_uint32(n), ip, ctypes.c_size_t(idx.size),
+                                  _ptr(alt) if alt is not None and idx.size else None, _ptr(out), ctypes.byref(ms))
+    if r != DST_OK:
+        raise DistaffError(r, _rtree_error(lib) or "dst_rescue_path_roots failed")
+    if stats is not None:
+        stats["device_ms"] = ms.value
+    return _pairs(out[:idx.size])
+
+
+def verify_paths(root, paths, indices, leaves=None, device=0, lib=None, stats=None):
+    """membership / absence (dst_rescue_verify_paths) -> (first_bad, why): (-1, DST_PATH_OK) when every path resolves to `root` and, with
+    `leaves`, has leaves[i] as its first node (the empty leaf of a sparse tree: the key is absent); else the lowest failing i and DST_PATH_BAD_LEAF
+    or DST_PATH_BAD_ROOT.  A path that does not verify is a result, not an exception."""
+    lib = lib or load()
+    idx, ip = RescueTree._indices(indices)
+    w, n = _path_words(paths, idx.size)
+    want = _nodes_for(leaves, idx.size, "leaves") if leaves is not None else None
+    r0 = _nodes_for([tuple(root)], 1, "roots")
+    first, why, ms = ctypes.c_int64(-1), ctypes.c_uint32(0), ctypes.c_double(0)
+    r = lib.dst_rescue_verify_paths(ctypes.c_int(device), _ptr(r0), _ptr(w) if idx.size else None, ctypes.c_uint32(n), ip,
+                                    _ptr(want) if want is not None and idx.size else None, ctypes.c_size_t(idx.size), ctypes.byref(first), ctypes.byref(why), ctypes.byref(ms))
+    if r != DST_OK:
+        raise DistaffError(r, _rtree_error(lib) or "dst_rescue_verify_paths failed")
+    if stats is not None:
+        stats["device_ms"] = ms.value
+    return first.value, why.value
+
+
+def verify_writes(root_before, indices, paths, leaves, roots=None, device=0, lib=None, stats=None):
+    """the checker of RescueTree.apply / SparseRescueTree.apply (dst_rescue_verify_writes) -> (first_bad, why, root_after): write i holds when
+    paths[i] resolves to the root before it (root_before, then the root after write i - 1 as computed here) and, with `roots`, resolves to roots[i]
+    with leaves[i] as its first node.  (-1, DST_PATH_OK, the root after the last write) when all hold.  Without `roots` a wrong new leaf shows one
+    write later (DST_PATH_BAD_ROOT), in the last write only in root_after.  On a device all 2 * count chains run in one launch."""
+    lib = lib or load()
+    idx, ip = RescueTree._indices(indices)
+    w, n = _path_words(paths, idx.size)
+    new = _nodes_for(leaves, idx.size, "leaves")
+    claimed = _nodes_for(roots, idx.size, "roots") if roots is not None else None
+    r0 = _nodes_for([tuple(root_before)], 1, "roots")
+    after = np.zeros((2, 2), dtype=np.uint64)
+    first, why, ms = ctypes.c_int64(-1), ctypes.c_uint32(0), ctypes.c_double(0)
+    r = lib.dst_rescue_verify_writes(ctypes.c_int(device), _ptr(r0), _ptr(w) if idx.size else None, ctypes.c_uint32(n), ip, _ptr(new) if idx.size else None,
+                                     _ptr(claimed) if claimed is not None and idx.size else None, ctypes.c_size_t(idx.size), ctypes.byref(first), ctypes.byref(why), _ptr(after),
+                                     ctypes.byref(ms))
+    if r != DST_OK:
+        raise DistaffError(r, _rtree_error(lib) or "dst_rescue_verify_writes failed")
+    if stats is not None:
+        stats["device_ms"] = ms.value
+    return first.value, why.value, tuple(arr_to_ints(after))
 
 
 def _apply(tree, call, n, indices, leaves):

@@ -207,8 +207,36 @@ DST_API int dst_rtree_apply(dst_rtree* t, const uint64_t* indices, const uint8_t
  * same size query.  Errors are reported by dst_rtree_last_error(NULL). */
 DST_API int dst_rescue_path_tapes(const uint8_t* paths /* count*n*32 */, uint32_t n, const uint64_t* indices, size_t count, uint32_t what,
                                   uint8_t* tape_a, uint8_t* tape_b, size_t cap_elems_each, size_t* elems_each);
+/* ---- checking paths and witnesses: the tree-side counterpart of dst_verify.  No tree, no dst_ctx: what a host that holds only a root needs.
+ * DST_ERR_ARG: a null pointer with count > 0, n outside 2 .. 64, an index not below 2^(n-1), count >= 2^31, an element of the paths, leaves or
+ * roots not below p (found on the host for what the host compares, on the device for what the kernel reads).  A path that does not verify is NOT
+ * an error: the call returns DST_OK, first_bad / why say so.  count = 0: DST_OK, *first_bad = -1.  Errors are reported by dst_rtree_last_error(NULL). */
+/* compute_merkle_root (src/examples/merkle.rs:112-145) of `count` paths of n nodes each, 2 <= n <= 64, indices[i] < 2^(n-1).
+ * leaves == NULL: roots[i] is what path i resolves to.  leaves != NULL: what it resolves to with its first node replaced by leaves[i]
+ * (the root after a write that keeps the siblings).  device >= 0: one upload, ONE launch, one copy back whatever count and n are;
+ * device < 0: on the host.  *device_ms (may be NULL): events around the launch, 0 on the host. */
+DST_API int dst_rescue_path_roots(int device, const uint8_t* paths /* count*n*32 */, uint32_t n, const uint64_t* indices, size_t count,
+                                  const uint8_t* leaves /* count*32, or NULL */, uint8_t* roots /* count*32 */, double* device_ms);
+
+enum { DST_PATH_OK = 0, DST_PATH_BAD_LEAF = 1, DST_PATH_BAD_ROOT = 2, DST_PATH_BAD_NEXT_ROOT = 3 };
+
+/* membership / absence: every path resolves to `root`; with leaves != NULL also path i's first node equals leaves[i] (the empty leaf of a
+ * sparse tree: the key is absent).  *first_bad = -1 and *why = DST_PATH_OK when all hold, else the lowest failing i and what failed there
+ * (within one i the leaf is looked at before the root). */
+DST_API int dst_rescue_verify_paths(int device, const uint8_t root[32], const uint8_t* paths, uint32_t n, const uint64_t* indices,
+                                    const uint8_t* leaves /* or NULL */, size_t count, int64_t* first_bad, uint32_t* why, double* device_ms);
+
+/* the checker of dst_rtree_apply / dst_stree_apply: write i is accepted when paths[i] resolves to the root before it (root_before for i = 0,
+ * else the root after write i-1 AS COMPUTED HERE: BAD_ROOT) and, where roots != NULL, the same path with leaves[i] as its first node resolves
+ * to roots[i] (BAD_NEXT_ROOT).  root_after (may be NULL) receives the computed root after the last write, root_before when count = 0: a
+ * client that holds only a root follows the state with it.  All 2*count chains run in one launch.
+ * With roots == NULL nothing states what leaves[i] must resolve to, so a wrong new leaf shows one write LATER, as that write's BAD_ROOT;
+ * in the last write it shows only in root_after, which the caller then holds against the root it expects. */
+DST_API int dst_rescue_verify_writes(int device, const uint8_t root_before[32], const uint8_t* paths, uint32_t n, const uint64_t* indices,
+                                     const uint8_t* leaves /* count*32 */, const uint8_t* roots /* count*32, or NULL */, size_t count,
+                                     int64_t* first_bad, uint32_t* why, uint8_t root_after[32], double* device_ms);
 DST_API void dst_rtree_destroy(dst_rtree* t);
-DST_API const char* dst_rtree_last_error(const dst_rtree* t);     /* t may be NULL: the error of the calling thread's last failed dst_rtree_build / dst_rescue_digest_many / dst_rescue_path_tapes */
+DST_API const char* dst_rtree_last_error(const dst_rtree* t);     /* t may be NULL: the error of the calling thread's last failed dst_rtree_build / dst_rescue_digest_many / dst_rescue_path_tapes / dst_rescue_path_roots / dst_rescue_verify_* */
 
 /* ---- sparse Rescue Merkle trees: a set addressed by keys of up to 63 bits (accounts, notes, nullifiers) ------------------------------------
  * A sparse tree of depth D, 1 <= D <= 63, IS the dense tree above over 2^D leaves in which every leaf that was never set holds the tree's empty

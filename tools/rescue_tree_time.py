@@ -6,6 +6,8 @@ device's own modular-multiplication rate sets.
     python tools/rescue_tree_time.py --sparse        sparse trees of depth 63 instead (dst_stree_set, dst_stree_paths), beside a dense 2^20 build
     python tools/rescue_tree_time.py --sequence      ordered writes with a witness each (dst_rtree_apply on the 2^20 tree, dst_stree_apply on a depth-63 tree
                                                      of 2^20 keys), beside the loop of single-leaf updates and single paths they replace
+    python tools/rescue_tree_time.py --verify        checking the witnesses of those ordered writes (dst_rescue_verify_writes, one launch) beside the apply that
+                                                     made them, the same check on the host for 256 writes, and dst_rescue_verify_paths of 4 096 paths
 One digest is counted as 9 180 field multiplications, the reference's own count per hasher::digest: ten rounds of 6 x 2 for the cubes, 6 x 139
 for x^INV_ALPHA by the addition chain (127 squarings + 12 multiplications) and 2 x 36 for the two MDS products."""
 import argparse
@@ -27,6 +29,7 @@ ap.add_argument("--runs", type=int, default=5)
 ap.add_argument("--update", action="store_true", help="time dst_rtree_update (k = 1, 256, 65 536 leaves) and dst_rtree_paths on the 2^20 tree instead of builds")
 ap.add_argument("--sparse", action="store_true", help="time dst_stree_set (2^12, 2^16, 2^20 keys into an empty depth-63 tree; 1, 256, 65 536 keys into the 2^20-key tree) and dst_stree_paths")
 ap.add_argument("--sequence", action="store_true", help="time dst_rtree_apply / dst_stree_apply (1, 256, 4 096, 65 536 ordered writes) and, for 256, the loop of update + path calls")
+ap.add_argument("--verify", action="store_true", help="time dst_rescue_verify_writes on the witnesses of dst_rtree_apply / dst_stree_apply (256, 4 096, 65 536 writes), on the host for 256, and dst_rescue_verify_paths of 4 096 paths")
 ap.add_argument("sizes", nargs="*", type=int)
 args = ap.parse_args()
 lib = D.lib._open(os.path.abspath(args.lib)) if args.lib else None       # through the binding: one HIP runtime per process
@@ -161,7 +164,7 @@ if args.sparse:
     print("dst_stree_paths of %d indices (half stored, half absent) on the %d-key tree: %.3f ms wall (%d nodes of %d searched levels each)" % (idx.size, big.info()["keys"], s_many * 1e3, DEPTH + 1, DEPTH + 1))
     big.close()
     sys.exit(0)
-if args.sequence:
+if args.sequence or args.verify:
     import ctypes
     SEQUENCE_SEED, DEPTH = 3030, 63
     vp = lambda x: x.ctypes.data_as(ctypes.c_void_p)  # noqa: E731
@@ -193,6 +196,50 @@ if args.sequence:
             print("%s: apply of %d ordered writes (%d distinct indices): %.3f ms on the device (min of %d after one warm-up; all: %s) = %.3f ms per level; %.2f ms wall (min; all: %s)%s"
                   % (name, count, np.unique(idx).size, min(ms), len(ms), " ".join("%.3f" % v for v in ms), min(ms) / (n - 1), min(wall), " ".join("%.2f" % v for v in wall), note()))
 
+    def time_verifies(name, tree, apply, open_paths, n, draw, device_ms, share):
+        """dst_rescue_verify_writes on the witnesses an apply just returned, beside that apply's own device time; `share` of the apply's launches
+        compute the witnesses (the rest of a sparse apply is the set that follows).  Then the same check on the host for 256 writes, and
+        dst_rescue_verify_paths of 4 096 openings against the tree's root."""
+        rng = np.random.default_rng(SEQUENCE_SEED + 2)
+        first, why, dms, after = ctypes.c_int64(0), ctypes.c_uint32(0), ctypes.c_double(0), np.zeros((2, 2), dtype=np.uint64)
+        args_of = lambda device, before, paths, idx, new, roots, count: (ctypes.c_int(device), vp(before), vp(paths), ctypes.c_uint32(n), vp(idx), vp(new), vp(roots), ctypes.c_size_t(count),  # noqa: E731
+                                                                         ctypes.byref(first), ctypes.byref(why), vp(after), ctypes.byref(dms))
+        for count in (256, 4096, 65536):
+            ms, wall, applied = [], [], []
+            for _ in range(1 + args.runs):          # the first is the warm-up: code
+                idx, new = operations(rng, count, draw)
+                paths, roots = np.zeros((count, n, 2, 2), dtype=np.uint64), np.zeros((count, 2, 2), dtype=np.uint64)
+                before = D.ints_to_arr(tree.root)
+                assert apply(tree._h, vp(idx), vp(new), ctypes.c_size_t(count), vp(paths), vp(roots)) == 0
+                applied.append(device_ms())
+                t0 = time.perf_counter()
+                r = L.dst_rescue_verify_writes(*args_of(0, before, paths, idx, new, roots, count))
+                wall.append((time.perf_counter() - t0) * 1e3)
+                assert r == 0 and (first.value, why.value) == (-1, 0) and tuple(D.arr_to_ints(after)) == tree.root
+                ms.append(dms.value)
+            ms, wall, applied = ms[1:], wall[1:], applied[1:]
+            print("%s: verify_writes of %d witnesses (%d chains of %d digests, %s): %.3f ms on the device (min of %d after one warm-up; all: %s) = %.3f ms per level; %.2f ms wall (min; all: %s); "
+                  "the apply that made them: %.3f ms on the device (min; all: %s); verify / (%.2f x apply) = %.2f"
+                  % (name, count, 2 * count, n - 1, "six-lane form" if 2 * count <= (1 << 15) else "one-lane form", min(ms), len(ms), " ".join("%.3f" % v for v in ms), min(ms) / (n - 1),
+                     min(wall), " ".join("%.2f" % v for v in wall), min(applied), " ".join("%.3f" % v for v in applied), share, min(ms) / (share * min(applied))))
+            if count == 256:
+                t0 = time.perf_counter()
+                r = L.dst_rescue_verify_writes(*args_of(-1, before, paths, idx, new, roots, count))
+                host = (time.perf_counter() - t0) * 1e3
+                assert r == 0 and (first.value, why.value) == (-1, 0) and tuple(D.arr_to_ints(after)) == tree.root
+                print("%s: the same %d witnesses on the host (device = -1, one core): %.1f ms wall, %.1f us per digest" % (name, count, host, host * 1e3 / (2 * count * (n - 1))))
+        idx = np.ascontiguousarray(draw(4096))
+        paths, root = open_paths(idx), D.ints_to_arr(tree.root)
+        ms, wall = [], []
+        for _ in range(1 + args.runs):
+            t0 = time.perf_counter()
+            r = L.dst_rescue_verify_paths(ctypes.c_int(0), vp(root), vp(paths), ctypes.c_uint32(n), vp(idx), None, ctypes.c_size_t(idx.size), ctypes.byref(first), ctypes.byref(why), ctypes.byref(dms))
+            wall.append((time.perf_counter() - t0) * 1e3)
+            assert r == 0 and (first.value, why.value) == (-1, 0)
+            ms.append(dms.value)
+        print("%s: verify_paths of %d paths against the root: %.3f ms on the device (min of %d after one warm-up; all: %s); %.2f ms wall (min)"
+              % (name, idx.size, min(ms[1:]), len(ms) - 1, " ".join("%.3f" % v for v in ms[1:]), min(wall[1:])))
+
     def time_loop(name, count, idx, new, one_write, one_path, n):
         """the baseline: per operation one path of one leaf, then one write of one leaf, through the calls that existed before"""
         path = np.zeros((n, 2, 2), dtype=np.uint64)
@@ -211,10 +258,18 @@ if args.sequence:
     L = t.lib
     rng = np.random.default_rng(SEQUENCE_SEED + 1)
     dense_draw = lambda count: rng.integers(0, 1 << log_leaves, size=count).astype(np.uint64)  # noqa: E731
-    time_applies("dense 2^%d leaves" % log_leaves, t, L.dst_rtree_apply, log_leaves + 1, dense_draw, lambda: t.update_ms)
-    idx, new = operations(rng, 256, dense_draw)
-    time_loop("dense 2^%d leaves" % log_leaves, 256, idx, new, lambda i, v: L.dst_rtree_update(t._h, vp(i), vp(v), ctypes.c_size_t(1)),
-              lambda i, out: L.dst_rtree_path(t._h, ctypes.c_uint64(int(i[0])), vp(out)), log_leaves + 1)
+    def dense_paths(idx):
+        out = np.zeros((idx.size, log_leaves + 1, 2, 2), dtype=np.uint64)
+        assert L.dst_rtree_paths(t._h, vp(idx), ctypes.c_size_t(idx.size), vp(out)) == 0
+        return out
+
+    if args.verify:
+        time_verifies("dense 2^%d leaves" % log_leaves, t, L.dst_rtree_apply, dense_paths, log_leaves + 1, dense_draw, lambda: t.update_ms, 1.0)
+    else:
+        time_applies("dense 2^%d leaves" % log_leaves, t, L.dst_rtree_apply, log_leaves + 1, dense_draw, lambda: t.update_ms)
+        idx, new = operations(rng, 256, dense_draw)
+        time_loop("dense 2^%d leaves" % log_leaves, 256, idx, new, lambda i, v: L.dst_rtree_update(t._h, vp(i), vp(v), ctypes.c_size_t(1)),
+                  lambda i, out: L.dst_rtree_path(t._h, ctypes.c_uint64(int(i[0])), vp(out)), log_leaves + 1)
     t.close()
     keys = np.unique(rng.integers(0, 1 << DEPTH, size=(1 << 20) + (1 << 17), dtype=np.uint64))
     rng.shuffle(keys)
@@ -231,6 +286,10 @@ if args.sequence:
         idx[stored] = keys[rng.integers(0, keys.size, size=stored.size)]
         return idx
 
+    if args.verify:                                # the witnesses are 63 of the 126 level launches of a sparse apply
+        time_verifies("sparse depth %d, 2^20 keys" % DEPTH, s, L.dst_stree_apply, s.paths_words, DEPTH + 1, sparse_draw, lambda: s.info()["last_device_ms"], 0.5)
+        s.close()
+        sys.exit(0)
     time_applies("sparse depth %d, 2^20 keys" % DEPTH, s, L.dst_stree_apply, DEPTH + 1, sparse_draw, lambda: s.info()["last_device_ms"],
                 lambda: "; %d digests: 63 per write, then one dst_stree_set of the distinct keys, whose 63 level launches the device time includes" % s.info()["last_digests"])
     idx, new = operations(rng, 256, sparse_draw)

@@ -490,6 +490,10 @@ int k_rescue_stree_level(hipStream_t stream, fe* nodes, const uint64_t* pref, co
 int k_rescue_stree_carry(hipStream_t stream, fe* dst, const fe* src, const uint32_t* from /* device */, size_t count);     // dst[j] = src[from[j]] unless from[j] == STREE_NEW
 // out[(i * (depth + 1) + k) ..] = node k of the path of indices[i], stored or empty; levels = (start, length) per level, empties = 2 elements per level (device)
 int k_rescue_stree_open(hipStream_t stream, const fe* nodes, const uint64_t* pref, const uint64_t* levels, const fe* empties, const uint64_t* indices, fe* out, size_t count, uint32_t depth);
+// out[2 i ..] = the leaf at indices[i] and stored[i] = 1, or the empty leaf and 0: one search of the leaf level [lstart, lstart + lcnt); empty on the host
+int k_rescue_stree_get(hipStream_t stream, const fe* nodes, const uint64_t* pref, size_t lstart, size_t lcnt, const fe* empty, const uint64_t* indices, fe* out, uint8_t* stored, size_t count);
+// flags[i] = whether leaves[i] (2 elements) is the empty leaf (host)
+int k_rescue_stree_empty_leaves(hipStream_t stream, const fe* leaves, const fe* empty, uint8_t* flags, size_t count);
 // ordered writes (host/tree_sequence.h): the versions vin of one level -> vout, those of the level above, for `count` operations; src / own = this
 // level's source words, idx = the operations' indices, paths = count paths of n nodes or nullptr (all device); k = the path node the siblings
 // are; nodes = the tree before the call; empty = the value of an empty child (host)

@@ -1,6 +1,6 @@
 // Sparse Rescue Merkle trees behind dst_stree_*: the dense tree of rtree_impl.h over 2^depth leaves in which every leaf that was never set holds
-// the tree's empty leaf, stored as the nodes with a set leaf below them only (host/stree_levels.h has the layout and the plan of a set; the
-// kernels are in kernels_hash.hip).  Included by api.hip after rtree_impl.h, whose stream / staging / error helpers it shares.
+// the tree's empty leaf, stored as the nodes with a set leaf below them only (host/stree_levels.h has the layout and the plans of a set and of
+// a removal; the kernels are in kernels_hash.hip).  Included by api.hip after rtree_impl.h, whose stream / staging / error helpers it shares.
 #pragma once
 #include "rtree_impl.h"
 #include "stree_levels.h"
@@ -11,10 +11,10 @@ struct dst_stree {
     u128 empties[2 * (STREE_MAX_DEPTH + 1)] = {0};      // E_l, the value of an empty subtree of level l, at empties[2 l ..); E_depth = the empty leaf
     stree_shape shape;                    // every level's prefixes; of a device tree too: sets are planned on the host
     std::vector<u128> host;               // the node values at the shape's flat positions, 2 elements per node
-    uint8_t* dev = nullptr;               // one allocation per set: [nodes 32 * total][empties 32 * 64][levels 16 * 64][prefixes 8 * total]
+    uint8_t* dev = nullptr;               // one allocation per generation: [nodes 32 * total][empties 32 * 64][levels 16 * 64][prefixes 8 * total]
     uint64_t last_digests = 0;
-    double last_ms = 0;                   // events around the level launches of the last set
-    bool broken = false;                  // a HIP error inside dst_stree_set: only destroy / last_error remain
+    double last_ms = 0;                   // events around the level launches of the last set / remove / compact
+    bool broken = false;                  // a HIP error inside a call that changes the tree: only destroy / last_error remain
     mutable hipStream_t stream = nullptr;
     mutable hipEvent_t ev[2] = {nullptr, nullptr};
     mutable uint8_t* stage = nullptr; mutable size_t stage_bytes = 0;
@@ -39,13 +39,14 @@ static bool all_keys(const dst_stree* t, const uint64_t* indices, size_t count) 
     for (size_t i = 0; i < count; i++) if (indices[i] >> t->depth) return false;
     return true;
 }
-struct st_generation {                                 // a device allocation that is freed unless the set completes
+struct st_generation {                                 // a device allocation that is freed unless the plan completes
     uint8_t* p = nullptr;
     ~st_generation() { if (p) hipFree(p); }
 };
 
 // the plan on the device: the next generation's allocation, the uploads (prefixes and level table into the generation; new leaves, carry-over
-// sources and dirty lists into the staging buffer), one carry-over launch, one scatter of the new leaves, one launch per level, one synchronisation
+// sources and dirty lists into the staging buffer), one carry-over launch, one scatter of the new leaves if there are any (a removal has none),
+// one launch per level that has dirty parents, one synchronisation.  A generation without nodes (creation, the last key removed) launches nothing.
 static int stree_apply_device(dst_stree* t, const stree_plan& p, const uint8_t* leaves /* in the order of the sorted keys */, size_t count) {
     const stree_shape& nx = p.next;
     const size_t total = nx.total(), D = t->depth;
@@ -56,28 +57,29 @@ static int stree_apply_device(dst_stree* t, const stree_plan& p, const uint8_t* 
     uint64_t* levels = reinterpret_cast<uint64_t*>(g.p + 32 * total + 2048), *pref = levels + 128;
     uint64_t lv[128] = {0};
     for (size_t l = 0; l <= D; l++) { lv[2 * l] = nx.start[l]; lv[2 * l + 1] = nx.cnt[l]; }
+    const fe* d_leaves = reinterpret_cast<const fe*>(t->stage);
+    uint32_t *d_src = reinterpret_cast<uint32_t*>(t->stage + 32 * count), *d_dirty = d_src + total;
     RT_HIP(t->err, hipMemcpyAsync(g.p + 32 * total, t->empties, 2048, hipMemcpyHostToDevice, t->stream));
     RT_HIP(t->err, hipMemcpyAsync(levels, lv, 1024, hipMemcpyHostToDevice, t->stream));
-    if (count) {
-        const fe* d_leaves = reinterpret_cast<const fe*>(t->stage);
-        uint32_t *d_src = reinterpret_cast<uint32_t*>(t->stage + 32 * count), *d_dirty = d_src + total;
+    if (total) {
         RT_HIP(t->err, hipMemcpyAsync(pref, nx.pref.data(), 8 * total, hipMemcpyHostToDevice, t->stream));
-        RT_HIP(t->err, hipMemcpyAsync(t->stage, leaves, 32 * count, hipMemcpyHostToDevice, t->stream));
         RT_HIP(t->err, hipMemcpyAsync(d_src, p.src.data(), 4 * total, hipMemcpyHostToDevice, t->stream));
-        RT_HIP(t->err, hipMemcpyAsync(d_dirty, p.dirty.data(), 4 * p.dirty.size(), hipMemcpyHostToDevice, t->stream));
-        if (k_rescue_stree_carry(t->stream, nodes, t->dev_nodes(), d_src, total)) return st_fail(t, DST_ERR_HIP, "rescue_stree_carry_kernel: launch failed");
-        if (k_rescue_tree_scatter(t->stream, nodes, d_dirty + p.doff[D], d_leaves, count)) return st_fail(t, DST_ERR_HIP, "rescue_tree_scatter_kernel: launch failed");
-        RT_HIP(t->err, hipEventRecord(t->ev[0], t->stream));
-        for (size_t l = D; l-- > 0;) {
-            const bool whole = p.dcnt[l] == nx.cnt[l];
-            if (k_rescue_stree_level(t->stream, nodes, pref, whole ? nullptr : d_dirty + p.doff[l], p.dcnt[l], nx.start[l], nx.start[l + 1], nx.cnt[l + 1],
-                                     reinterpret_cast<const fe*>(t->empties + 2 * (l + 1))))
-                return st_fail(t, DST_ERR_HIP, "rescue_stree_level_kernel: launch failed");
-        }
-        RT_HIP(t->err, hipEventRecord(t->ev[1], t->stream));
     }
+    if (count) RT_HIP(t->err, hipMemcpyAsync(t->stage, leaves, 32 * count, hipMemcpyHostToDevice, t->stream));
+    if (!p.dirty.empty()) RT_HIP(t->err, hipMemcpyAsync(d_dirty, p.dirty.data(), 4 * p.dirty.size(), hipMemcpyHostToDevice, t->stream));
+    if (total && k_rescue_stree_carry(t->stream, nodes, t->dev_nodes(), d_src, total)) return st_fail(t, DST_ERR_HIP, "rescue_stree_carry_kernel: launch failed");
+    if (count && k_rescue_tree_scatter(t->stream, nodes, d_dirty + p.doff[D], d_leaves, count)) return st_fail(t, DST_ERR_HIP, "rescue_tree_scatter_kernel: launch failed");
+    RT_HIP(t->err, hipEventRecord(t->ev[0], t->stream));
+    for (size_t l = D; l-- > 0;) {
+        if (p.dcnt[l] == 0) continue;
+        const bool whole = p.dcnt[l] == nx.cnt[l];
+        if (k_rescue_stree_level(t->stream, nodes, pref, whole ? nullptr : d_dirty + p.doff[l], p.dcnt[l], nx.start[l], nx.start[l + 1], nx.cnt[l + 1],
+                                 reinterpret_cast<const fe*>(t->empties + 2 * (l + 1))))
+            return st_fail(t, DST_ERR_HIP, "rescue_stree_level_kernel: launch failed");
+    }
+    RT_HIP(t->err, hipEventRecord(t->ev[1], t->stream));
     RT_HIP(t->err, hipStreamSynchronize(t->stream));
-    if (count) { if (int r = rtree_elapsed(t, &t->last_ms)) return r; }
+    if (int r = rtree_elapsed(t, &t->last_ms)) return r;
     if (t->dev) hipFree(t->dev);
     t->dev = g.p; g.p = nullptr;
     return DST_OK;
@@ -86,13 +88,16 @@ static int stree_apply_device(dst_stree* t, const stree_plan& p, const uint8_t* 
 static void stree_apply_host(dst_stree* t, const stree_plan& p, const uint8_t* leaves, size_t count) {
     const stree_shape& nx = p.next;
     const size_t D = t->depth;
-    std::vector<u128> nn(2 * nx.total()), in(4 * count), out(2 * count);          // no level has more dirty parents than there are new leaves
+    size_t most = 0;                                                               // the longest dirty list of parents
+    for (size_t l = 0; l < D; l++) most = std::max(most, p.dcnt[l]);
+    std::vector<u128> nn(2 * nx.total()), in(4 * most), out(2 * most);
     for (size_t j = 0; j < nx.total(); j++) if (p.src[j] != STREE_NEW) memcpy(&nn[2 * j], &t->host[2 * (size_t)p.src[j]], 32);
     for (size_t i = 0; i < count; i++) memcpy(&nn[2 * (size_t)p.dirty[p.doff[D] + i]], leaves + 32 * i, 32);
     for (size_t l = D; l-- > 0;) {
         const uint32_t* list = p.dirty.data() + p.doff[l];
         const size_t m = p.dcnt[l], cstart = nx.start[l + 1];
         const u128* e = t->empties + 2 * (l + 1);
+        if (m == 0) continue;
         for (size_t g = 0; g < m; g++) {
             size_t left, right;
             stree_children(nx.pref.data() + cstart, nx.cnt[l + 1], nx.pref[list[g]], left, right);
@@ -103,6 +108,24 @@ static void stree_apply_host(dst_stree* t, const stree_plan& p, const uint8_t* l
         for (size_t g = 0; g < m; g++) memcpy(&nn[2 * (size_t)list[g]], &out[2 * g], 32);
     }
     t->host.swap(nn);
+}
+// how set, remove and compact change a tree: the plan runs where the tree lives, then the tree takes the plan's shape.  Everything that can be
+// refused has been refused before; a HIP error here leaves neither generation whole
+static int stree_commit(dst_stree* t, stree_plan& p, const uint8_t* leaves, size_t count, const char* what) {
+    if (t->device < 0) stree_apply_host(t, p, leaves, count);
+    else if (int r = stree_apply_device(t, p, leaves, count)) {
+        t->broken = true; t->err += std::string("; the ") + what + " did not complete, the tree is unusable";
+        return r;
+    }
+    t->shape = std::move(p.next);
+    t->last_digests = p.digests;
+    return DST_OK;
+}
+// `count` indices below 2^depth, sorted; false when one is repeated
+static bool sorted_distinct(const uint64_t* indices, size_t count, std::vector<uint64_t>& keys) {
+    keys.assign(indices, indices + count);
+    std::sort(keys.begin(), keys.end());
+    return std::adjacent_find(keys.begin(), keys.end()) == keys.end();
 }
 
 int dst_stree_create(int device, uint32_t depth, const uint8_t empty_leaf[32], dst_stree** out) {
@@ -120,6 +143,7 @@ int dst_stree_create(int device, uint32_t depth, const uint8_t empty_leaf[32], d
     if (device >= 0) {                                                             // the generation of a tree without keys
         const int r = stree_apply_device(t.get(), stree_plan_set(t->shape, {}), nullptr, 0);
         if (r != DST_OK) { g_stree_error = t->err; return r; }
+        t->last_ms = 0;                                                            // nothing was launched
     }
     *out = t.release();
     return DST_OK;
@@ -145,15 +169,83 @@ int dst_stree_set(dst_stree* t, const uint64_t* indices, const uint8_t* leaves, 
         std::vector<uint8_t> sorted(32 * count);
         for (size_t i = 0; i < count; i++) memcpy(&sorted[32 * i], leaves + 32 * (size_t)order[i], 32);
         stree_plan p = stree_plan_set(t->shape, std::move(keys));
-        if (t->device < 0) stree_apply_host(t, p, sorted.data(), count);
-        else if (int r = stree_apply_device(t, p, sorted.data(), count)) {
-            t->broken = true; t->err += "; the set did not complete, the tree is unusable";
-            return r;
-        }
-        t->shape = std::move(p.next);
-        t->last_digests = p.digests;
-        return DST_OK;
+        return stree_commit(t, p, sorted.data(), count, "set");
     } catch (const std::bad_alloc&) { return st_fail(t, DST_ERR_HIP, "out of host memory"); }      // thrown before anything was queued
+}
+
+// ---- deletion: the stored keys among the indices leave, and every node left without a key below it; what remains is the fresh tree of the
+//      remaining keys.  The surviving ancestors of the removed keys are hashed again (stree_plan_remove), nothing else ------------------------
+int dst_stree_remove(dst_stree* t, const uint64_t* indices, size_t count, uint64_t* removed) {
+    if (int r = st_enter(t)) return r;
+    if (!indices && count) return st_fail(t, DST_ERR_ARG, "null pointer");
+    if (!all_keys(t, indices, count)) return st_fail(t, DST_ERR_ARG, "index past the end");
+    try {
+        std::vector<uint64_t> keys;
+        if (!sorted_distinct(indices, count, keys)) return st_fail(t, DST_ERR_ARG, "an index is repeated");
+        const size_t D = t->depth;
+        const uint64_t* leaf_pref = t->shape.pref.data() + t->shape.start[D];
+        const size_t leaf_cnt = t->shape.cnt[D];
+        size_t at = 0;                                                             // the keys ascend: one walk along the leaf level
+        keys.erase(std::remove_if(keys.begin(), keys.end(), [&](uint64_t k) { at = stree_advance(leaf_pref, leaf_cnt, at, k); return at == leaf_cnt || leaf_pref[at] != k; }), keys.end());
+        if (removed) *removed = keys.size();
+        if (keys.empty()) { t->last_digests = 0; t->last_ms = 0; return DST_OK; }
+        stree_plan p = stree_plan_remove(t->shape, std::move(keys));
+        return stree_commit(t, p, nullptr, 0, "removal");
+    } catch (const std::bad_alloc&) { return st_fail(t, DST_ERR_HIP, "out of host memory"); }
+}
+// the stored keys that hold the empty leaf leave: their ancestors are what they were (a stored empty side and an absent side hash alike), so
+// nothing is hashed.  A device tree flags those leaves in one launch and sends a byte per stored key back; node values stay where they are
+int dst_stree_compact(dst_stree* t, uint64_t* removed) {
+    if (int r = st_enter(t)) return r;
+    const size_t D = t->depth, m = t->shape.cnt[D], lstart = t->shape.start[D];
+    try {
+        std::vector<uint8_t> flags(m);
+        if (t->device < 0) {
+            for (size_t i = 0; i < m; i++) flags[i] = memcmp(&t->host[2 * (lstart + i)], t->empties + 2 * D, 32) == 0;
+        } else if (m) {                                                            // the tree is only read: an error here leaves it usable
+            if (int r = rtree_stage(t, m)) return r;
+            if (k_rescue_stree_empty_leaves(t->stream, t->dev_nodes() + 2 * lstart, reinterpret_cast<const fe*>(t->empties + 2 * D), t->stage, m))
+                return st_fail(t, DST_ERR_HIP, "rescue_stree_empty_leaves_kernel: launch failed");
+            RT_HIP(t->err, hipMemcpyAsync(flags.data(), t->stage, m, hipMemcpyDeviceToHost, t->stream));
+            RT_HIP(t->err, hipStreamSynchronize(t->stream));
+        }
+        std::vector<uint64_t> keys;
+        for (size_t i = 0; i < m; i++) if (flags[i]) keys.push_back(t->shape.pref[lstart + i]);
+        if (removed) *removed = keys.size();
+        if (keys.empty()) { t->last_digests = 0; t->last_ms = 0; return DST_OK; }
+        stree_plan p = stree_plan_remove(t->shape, std::move(keys), false);
+        return stree_commit(t, p, nullptr, 0, "compaction");
+    } catch (const std::bad_alloc&) { return st_fail(t, DST_ERR_HIP, "out of host memory"); }
+}
+// the leaves alone, 32 bytes per index where a path is 32 * (depth + 1)
+int dst_stree_get(const dst_stree* t, const uint64_t* indices, size_t count, uint8_t* leaves, uint8_t* stored) {
+    if (int r = st_enter(t)) return r;
+    if ((!indices || !leaves) && count) return st_fail(t, DST_ERR_ARG, "null pointer");
+    if (count > ((size_t)1 << 40)) return st_fail(t, DST_ERR_ARG, "too many indices");
+    if (!all_keys(t, indices, count)) return st_fail(t, DST_ERR_ARG, "index past the end");
+    if (count == 0) return DST_OK;
+    const size_t D = t->depth, m = t->shape.cnt[D], lstart = t->shape.start[D];
+    if (t->device < 0) {
+        for (size_t i = 0; i < count; i++) {
+            const size_t pos = stree_find(t->shape.pref.data() + lstart, m, indices[i]);
+            memcpy(leaves + 32 * i, pos != STREE_ABSENT ? &t->host[2 * (lstart + pos)] : t->empties + 2 * D, 32);
+            if (stored) stored[i] = pos != STREE_ABSENT;
+        }
+        return DST_OK;
+    }
+    try {
+        std::vector<uint8_t> back(stored ? 33 * count : 0);                        // one copy back: [count leaves][count flags]
+        if (int r = rtree_stage(t, 41 * count + 8)) return r;                      // [count leaves][count flags, padded to 8][count indices]
+        uint8_t* d_stored = t->stage + 32 * count;
+        uint64_t* d_idx = reinterpret_cast<uint64_t*>(t->stage + 32 * count + ((count + 7) & ~(size_t)7));
+        RT_HIP(t->err, hipMemcpyAsync(d_idx, indices, 8 * count, hipMemcpyHostToDevice, t->stream));
+        if (k_rescue_stree_get(t->stream, t->dev_nodes(), t->dev_pref(), lstart, m, reinterpret_cast<const fe*>(t->empties + 2 * D), d_idx, reinterpret_cast<fe*>(t->stage), d_stored, count))
+            return st_fail(t, DST_ERR_HIP, "rescue_stree_get_kernel: launch failed");
+        RT_HIP(t->err, hipMemcpyAsync(stored ? back.data() : leaves, t->stage, stored ? 33 * count : 32 * count, hipMemcpyDeviceToHost, t->stream));
+        RT_HIP(t->err, hipStreamSynchronize(t->stream));
+        if (stored) { memcpy(leaves, back.data(), 32 * count); memcpy(stored, back.data() + 32 * count, count); }
+    } catch (const std::bad_alloc&) { return st_fail(t, DST_ERR_HIP, "out of host memory"); }
+    return DST_OK;
 }
 
 int dst_stree_read_level(const dst_stree* t, uint32_t level, uint64_t first, uint64_t count, uint64_t* prefixes, uint8_t* nodes, uint64_t* level_count) {

@@ -1,8 +1,8 @@
 // Sparse Rescue Merkle trees (dst_stree_*): the integer bookkeeping, free of HIP and of field arithmetic.  A tree of depth D stores, per level
 // l (D = the leaves, 0 = the root), the sorted distinct prefixes key >> (D - l) of its keys; a node is found by a lower-bound search for its
 // prefix.  Here: that search (shared with the kernels of kernels_hash.hip, hence STREE_HD), and the plan of a dst_stree_set -- the merge of the
-// new keys into every level, where each node of the merged level comes from, and which nodes have to be hashed.  The host path and the device
-// path run the same plan.
+// new keys into every level, where each node of the merged level comes from, and which nodes have to be hashed -- and the plan of a removal
+// (dst_stree_remove, dst_stree_compact), the same three things for the pruned levels.  The host path and the device path run the same plan.
 #pragma once
 #include <algorithm>
 #include <cstddef>
@@ -33,6 +33,13 @@ STREE_HD size_t stree_find(const uint64_t* pref, size_t cnt, uint64_t want) {
     const size_t i = stree_lower_bound(pref, cnt, want);
     return i < cnt && pref[i] == want ? i : STREE_ABSENT;
 }
+// stree_lower_bound for a run of ascending wants: the search starts at `from`, a position with only smaller prefixes before it, and gallops
+// forward, so a sorted batch costs a walk along the list, not a search from the top each
+STREE_HD size_t stree_advance(const uint64_t* pref, size_t cnt, size_t from, uint64_t want) {
+    size_t hi = from, step = 1;
+    while (hi < cnt && pref[hi] < want) { from = hi + 1; hi += step; step <<= 1; }
+    return from + stree_lower_bound(pref + from, (hi < cnt ? hi : cnt) - from, want);
+}
 // the children of the parent with prefix q among the child level's prefixes: the positions of 2q and 2q + 1, STREE_ABSENT for an empty side
 STREE_HD void stree_children(const uint64_t* cpref, size_t ccnt, uint64_t q, size_t& left, size_t& right) {
     const size_t i = stree_lower_bound(cpref, ccnt, 2 * q);
@@ -56,9 +63,9 @@ struct stree_shape {
     size_t start[STREE_MAX_DEPTH + 1] = {0}, cnt[STREE_MAX_DEPTH + 1] = {0};
     size_t total() const { return pref.size(); }
 };
-// what a set of sorted distinct keys does to a shape
+// what a set, or a removal, of sorted distinct keys does to a shape
 struct stree_plan {
-    stree_shape next;                                    // the merged levels
+    stree_shape next;                                    // the merged (set) or pruned (removal) levels
     std::vector<uint32_t> src;                           // per flat position of `next`: the flat position in the old shape the node is carried over from, or STREE_NEW
     std::vector<uint32_t> dirty;                         // flat positions in `next` of the touched nodes: level l's, sorted, at dirty[doff[l] .. doff[l] + dcnt[l]);
     size_t doff[STREE_MAX_DEPTH + 1] = {0}, dcnt[STREE_MAX_DEPTH + 1] = {0};      // level depth: the new leaves, in the order of the sorted keys
@@ -86,6 +93,42 @@ inline stree_plan stree_plan_set(const stree_shape& old, std::vector<uint64_t> c
             }
         }
         p.next.cnt[l] = p.next.pref.size() - p.next.start[l];
+        if (l == 0) break;
+        for (auto& v : cur) v >>= 1;
+        cur.erase(std::unique(cur.begin(), cur.end()), cur.end());
+    }
+    return p;
+}
+// the plan of a removal: the stored keys `gone` leave, and with them every node that has no stored key below it any more.  A touched node --
+// an ancestor of a removed key -- that keeps a child on the pruned level below is on its level's dirty list and is written by the plan
+// (src = STREE_NEW) when `rehash`; without `rehash` it is carried over like the untouched ones and nothing is dirty: the removal of keys that
+// hold the empty leaf, whose ancestors do not change (dst_stree_compact).  dcnt[depth] = 0: there are no new leaves.
+inline stree_plan stree_plan_remove(const stree_shape& old, std::vector<uint64_t> cur /* sorted, distinct, stored */, bool rehash = true) {
+    stree_plan p;
+    const uint32_t depth = old.depth;
+    p.next.depth = depth;
+    p.next.pref.reserve(old.total()); p.src.reserve(old.total());
+    if (rehash) p.dirty.reserve(cur.size() * depth);
+    for (uint32_t l = depth;; l--) {                     // cur = the touched prefixes of level l, all of them stored
+        const uint64_t* o = old.pref.data() + old.start[l];
+        const size_t on = old.cnt[l];
+        p.next.start[l] = p.next.pref.size(); p.doff[l] = p.dirty.size();
+        const uint64_t* c = l < depth ? p.next.pref.data() + p.next.start[l + 1] : nullptr;      // the pruned level below, complete
+        const size_t cn = l < depth ? p.next.cnt[l + 1] : 0;
+        for (size_t i = 0, j = 0, at = 0; i < on; i++) {
+            const bool touched = j < cur.size() && cur[j] == o[i];
+            if (touched) {
+                j++;
+                at = stree_advance(c, cn, at, 2 * o[i]);                            // the touched prefixes ascend: one walk along the children
+                if (at == cn || c[at] > 2 * o[i] + 1) continue;                     // nothing stored below it any more: pruned
+                if (rehash) p.dirty.push_back((uint32_t)p.next.pref.size());
+            }
+            p.next.pref.push_back(o[i]);
+            p.src.push_back(touched && rehash ? STREE_NEW : (uint32_t)(old.start[l] + i));
+        }
+        p.next.cnt[l] = p.next.pref.size() - p.next.start[l];
+        p.dcnt[l] = p.dirty.size() - p.doff[l];
+        p.digests += p.dcnt[l];
         if (l == 0) break;
         for (auto& v : cur) v >>= 1;
         cur.erase(std::unique(cur.begin(), cur.end()), cur.end());

@@ -480,6 +480,24 @@ __global__ void rescue_stree_open_kernel(const fe* __restrict__ nodes, const uin
     const size_t start = levels[2 * level], pos = stree_find(pref + start, levels[2 * level + 1], prefix);
     out[t] = pos != STREE_ABSENT ? nodes[2 * (start + pos) + (t & 1)] : empties[2 * level + (t & 1)];
 }
+// the leaves alone (dst_stree_get): one lane per index, one search of the leaf level [lstart, lstart + lcnt); a key that is not stored gives the
+// empty leaf (e0, e1) and stored[i] = 0
+__global__ void rescue_stree_get_kernel(const fe* __restrict__ nodes, const uint64_t* __restrict__ pref, size_t lstart, size_t lcnt, fe e0, fe e1,
+                                        const uint64_t* __restrict__ indices, fe* __restrict__ out, uint8_t* __restrict__ stored, size_t count) {
+    const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= count) return;
+    const size_t pos = stree_find(pref + lstart, lcnt, indices[i]);
+    const bool has = pos != STREE_ABSENT;
+    out[2 * i] = has ? nodes[2 * (lstart + pos)] : e0;
+    out[2 * i + 1] = has ? nodes[2 * (lstart + pos) + 1] : e1;
+    stored[i] = has ? 1 : 0;
+}
+// which stored keys hold the empty leaf (dst_stree_compact): flags[i] = 1 when both elements of leaves[i] equal (e0, e1), one lane per key
+__global__ void rescue_stree_empty_leaves_kernel(const fe* __restrict__ leaves, fe e0, fe e1, uint8_t* __restrict__ flags, size_t count) {
+    const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= count) return;
+    flags[i] = fe_eq(leaves[2 * i], e0) && fe_eq(leaves[2 * i + 1], e1) ? 1 : 0;
+}
 
 int k_rescue_stree_level(hipStream_t stream, fe* nodes, const uint64_t* pref, const uint32_t* list, size_t count, size_t pstart, size_t cstart, size_t ccnt, const fe* empty) {
     const bool spread = count <= RESCUE_SPREAD_MAX;
@@ -496,6 +514,14 @@ int k_rescue_stree_carry(hipStream_t stream, fe* dst, const fe* src, const uint3
 int k_rescue_stree_open(hipStream_t stream, const fe* nodes, const uint64_t* pref, const uint64_t* levels, const fe* empties, const uint64_t* indices, fe* out, size_t count, uint32_t depth) {
     const size_t lanes = 2 * count * (depth + 1);
     hipLaunchKernelGGL(rescue_stree_open_kernel, dim3((unsigned)((lanes + HASH_THREADS - 1) / HASH_THREADS)), dim3(HASH_THREADS), 0, stream, nodes, pref, levels, empties, indices, out, count, depth);
+    return hipGetLastError() == hipSuccess ? 0 : -1;
+}
+int k_rescue_stree_get(hipStream_t stream, const fe* nodes, const uint64_t* pref, size_t lstart, size_t lcnt, const fe* empty, const uint64_t* indices, fe* out, uint8_t* stored, size_t count) {
+    hipLaunchKernelGGL(rescue_stree_get_kernel, dim3((unsigned)((count + HASH_THREADS - 1) / HASH_THREADS)), dim3(HASH_THREADS), 0, stream, nodes, pref, lstart, lcnt, empty[0], empty[1], indices, out, stored, count);
+    return hipGetLastError() == hipSuccess ? 0 : -1;
+}
+int k_rescue_stree_empty_leaves(hipStream_t stream, const fe* leaves, const fe* empty, uint8_t* flags, size_t count) {
+    hipLaunchKernelGGL(rescue_stree_empty_leaves_kernel, dim3((unsigned)((count + HASH_THREADS - 1) / HASH_THREADS)), dim3(HASH_THREADS), 0, stream, leaves, empty[0], empty[1], flags, count);
     return hipGetLastError() == hipSuccess ? 0 : -1;
 }
 

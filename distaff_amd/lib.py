@@ -60,7 +60,8 @@ EXPORTS = ["dst_ctx_create", "dst_ctx_destroy", "dst_last_error", "dst_phase_ms"
            "dst_rtree_destroy", "dst_rtree_last_error", "dst_rtree_update", "dst_rtree_update_ms", "dst_rtree_paths", "dst_rtree_tapes_many",
            "dst_stree_create", "dst_stree_set", "dst_stree_root", "dst_stree_paths", "dst_stree_tapes_many", "dst_stree_read_level", "dst_stree_info",
            "dst_stree_destroy", "dst_stree_last_error", "dst_rtree_apply", "dst_stree_apply", "dst_rescue_path_tapes",
-           "dst_rescue_path_roots", "dst_rescue_verify_paths", "dst_rescue_verify_writes"]
+           "dst_rescue_path_roots", "dst_rescue_verify_paths", "dst_rescue_verify_writes",
+           "dst_stree_remove", "dst_stree_compact", "dst_stree_get"]
 
 
 class DistaffError(RuntimeError):
@@ -580,6 +581,38 @@ class SparseRescueTree:
         """RescueTree.apply on keys below 2^depth, stored or not (dst_stree_apply) -> (paths, roots); the old leaf of a key that is not stored is
         the empty leaf.  Afterwards the tree is set()'s of the distinct keys with the later value of each."""
         return _apply(self, self.lib.dst_stree_apply, self.depth + 1, indices, leaves)
+
+    def remove(self, indices):
+        """deletes the stored keys among the distinct keys `indices` (any order) and every node left without a key below it
+        (dst_stree_remove) -> how many were stored.  The tree then equals a fresh one set with the remaining keys; only the surviving
+        ancestors of the removed keys are hashed.  A repeated key or a key past 2^depth raises DistaffError(DST_ERR_ARG)."""
+        idx, ip = RescueTree._indices(indices)
+        n = ctypes.c_uint64(0)
+        self._check(self.lib.dst_stree_remove(self._h, ip, ctypes.c_size_t(idx.size), ctypes.byref(n)))
+        return n.value
+
+    def compact(self):
+        """deletes every stored key whose leaf is the empty leaf and every node left without a key below it (dst_stree_compact) -> how many
+        keys.  The root and the remaining nodes do not change and nothing is hashed.  apply(keys, empty leaves) + compact() is a removal
+        with a witness per key."""
+        n = ctypes.c_uint64(0)
+        self._check(self.lib.dst_stree_compact(self._h, ctypes.byref(n)))
+        return n.value
+
+    def get_words(self, indices):
+        """get() as (leaves: uint64 words [count, 2, 2], stored: uint8 [count])"""
+        idx, ip = RescueTree._indices(indices)
+        out = np.zeros((idx.size, 2, 2), dtype=np.uint64)
+        stored = np.zeros(idx.size, dtype=np.uint8)
+        self._check(self.lib.dst_stree_get(self._h, ip, ctypes.c_size_t(idx.size), _ptr(out) if idx.size else None, _ptr(stored) if idx.size else None))
+        return out, stored
+
+    def get(self, indices):
+        """the leaves at the keys `indices`, stored or not, repeats allowed, in one call (dst_stree_get) -> (leaves as pairs of ints, stored
+        as a list of bool); a key that is not stored has the empty leaf"""
+        w, stored = self.get_words(indices)
+        v = arr_to_ints(w)
+        return [(v[2 * i], v[2 * i + 1]) for i in range(w.shape[0])], [bool(b) for b in stored]
 
     @property
     def root(self):

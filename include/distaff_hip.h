@@ -244,11 +244,12 @@ DST_API const char* dst_rtree_last_error(const dst_rtree* t);     /* t may be NU
  * n = D + 1 <= 64 authenticate them.  Level D is the leaf level, level 0 the root; E_D = the empty leaf and E_l = digest(E_{l+1}, E_{l+1}) is
  * every empty subtree of level l.  Only nodes with a set leaf below them are stored: per level l a list sorted by prefix, the distinct
  * key >> (D - l) and their node values.  A key set to the empty value stays stored (its nodes then equal the defaults, so roots do not depend
- * on it); there is no deletion.  A tree without keys has root E_0.  The reference has no such structure (it walks "a pseudo-random path
+ * on it) until dst_stree_compact drops it; dst_stree_remove deletes keys outright.  Either way the nodes left without a key below them go too,
+ * and what remains is, level by level, the tree that create + one set of the remaining keys makes.  A tree without keys has root E_0.  The reference has no such structure (it walks "a pseudo-random path
  * through an imaginary tree", src/examples/merkle.rs:96-108).
  * The conventions are dst_rtree's: no dst_ctx; device >= 0 on that GPU with a stream the tree owns, device < 0 on the host with one thread and
- * no HIP call; DST_ERR_ARG is found on the host before anything is queued and leaves the tree unchanged; a HIP error inside dst_stree_set leaves
- * the tree unusable (DST_ERR_STATE from everything but destroy and last_error). */
+ * no HIP call; DST_ERR_ARG is found on the host before anything is queued and leaves the tree unchanged; a HIP error inside a call that changes
+ * the tree (set, apply, remove, compact) leaves it unusable (DST_ERR_STATE from everything but destroy and last_error). */
 typedef struct dst_stree dst_stree;
 DST_API int dst_stree_create(int device, uint32_t depth, const uint8_t empty_leaf[32] /* NULL: (0, 0) */, dst_stree** out);
 /* inserts the keys that are not stored and replaces those that are: `count` distinct indices below 2^depth in any order, count * 32 bytes of
@@ -258,6 +259,25 @@ DST_API int dst_stree_create(int device, uint32_t depth, const uint8_t empty_lea
  * DST_ERR_ARG: a repeated index, an index past the end, an element not below p, a null pointer with count > 0, more than 2^32 - 2 stored nodes.
  * count = 0: DST_OK. */
 DST_API int dst_stree_set(dst_stree* t, const uint64_t* indices, const uint8_t* leaves /* count*32 */, size_t count);
+/* deletes the stored keys among `count` distinct indices below 2^depth (any order) and ignores the others; *removed (may be NULL) = how many
+ * were stored.  A node with no stored key below it is no longer stored; an ancestor of a removed key that still has one is hashed again, a side
+ * without keys being its level's E_l; no other node is hashed.  last_digests = the number of those surviving ancestors.  The root is that of the
+ * dense tree with the empty leaf at the removed positions; removing every key gives the tree without keys (root E_0, 0 nodes), usable again.
+ * On a device tree: one carry-over launch, one level launch per level that keeps a touched parent, one synchronisation; node values never
+ * travel to the host.  DST_ERR_ARG: a repeated index, an index past the end, a null pointer with count > 0.  count = 0, or no index stored:
+ * DST_OK, the tree is unchanged, last_digests = 0. */
+DST_API int dst_stree_remove(dst_stree* t, const uint64_t* indices, size_t count, uint64_t* removed /* may be NULL */);
+/* deletes every stored key whose leaf equals the empty leaf -- what dst_stree_set / dst_stree_apply with the empty value leave behind -- and every
+ * node left without a key below it; *removed (may be NULL) = how many keys.  The root and every remaining node are unchanged (a stored empty
+ * side and an absent side hash alike), so no digest is computed: last_digests = 0.  On a device tree: one launch that flags those leaves, a
+ * copy back of one byte per stored key, one carry-over launch.
+ * WITNESSED REMOVAL is dst_stree_apply with empty leaves -- per write the path and the root after it, which dst_rescue_verify_writes checks --
+ * followed by dst_stree_compact, which frees the nodes. */
+DST_API int dst_stree_compact(dst_stree* t, uint64_t* removed /* may be NULL */);
+/* the leaf at each of `count` indices below 2^depth (repeats allowed): 32 bytes per index where dst_stree_paths returns 32 * (depth + 1).  An
+ * index that is not stored gives the empty leaf and stored[i] = 0.  On a device tree: one upload, one launch, one copy back, whatever count is. */
+DST_API int dst_stree_get(const dst_stree* t, const uint64_t* indices, size_t count,
+                          uint8_t* leaves /* count*32 */, uint8_t* stored /* count bytes of 0 / 1, may be NULL */);
 DST_API int dst_stree_root(const dst_stree* t, uint8_t root[32]);
 /* authentication paths [leaf, sibling, uncle, ...] of `count` indices below 2^depth, stored or not (repeats allowed), (depth + 1) * 32 bytes
  * each in dst_rtree_path's layout: compute_merkle_root (merkle.rs:112-145) of the path and the index gives the root.  A leaf or sibling that is
@@ -282,7 +302,7 @@ typedef struct dst_stree_info_t {
     uint32_t depth;
     int32_t device;                     /* -1: a host tree */
     uint64_t keys, nodes;               /* stored keys; stored nodes of all levels, the leaves included */
-    uint64_t last_digests;              /* digests computed by the last dst_stree_set / dst_stree_apply */
+    uint64_t last_digests;              /* digests computed by the last dst_stree_set / dst_stree_apply / dst_stree_remove / dst_stree_compact */
     double last_device_ms;              /* events around that call's level launches, as dst_rtree_update_ms; 0 on a host tree */
 } dst_stree_info_t;
 DST_API int dst_stree_info(const dst_stree* t, dst_stree_info_t* out);

@@ -4,6 +4,8 @@ device's own modular-multiplication rate sets.
     python tools/rescue_tree_time.py [--host-log 12] [--lib path/to/another/build.so] [log_leaves ...]        (default 12 16 20)
     python tools/rescue_tree_time.py --update        updates in place and batched openings on the 2^20 tree instead (dst_rtree_update_ms)
     python tools/rescue_tree_time.py --sparse        sparse trees of depth 63 instead (dst_stree_set, dst_stree_paths), beside a dense 2^20 build
+    python tools/rescue_tree_time.py --remove        deletion on the depth-63 tree of 2^20 keys that --sparse builds (dst_stree_remove beside a dst_stree_set of the
+                                                     same keys, dst_stree_compact after an apply of empties, dst_stree_get beside dst_stree_paths)
     python tools/rescue_tree_time.py --sequence      ordered writes with a witness each (dst_rtree_apply on the 2^20 tree, dst_stree_apply on a depth-63 tree
                                                      of 2^20 keys), beside the loop of single-leaf updates and single paths they replace
     python tools/rescue_tree_time.py --verify        checking the witnesses of those ordered writes (dst_rescue_verify_writes, one launch) beside the apply that
@@ -28,6 +30,7 @@ ap.add_argument("--lib", default=None, help="another build of the library (a dif
 ap.add_argument("--runs", type=int, default=5)
 ap.add_argument("--update", action="store_true", help="time dst_rtree_update (k = 1, 256, 65 536 leaves) and dst_rtree_paths on the 2^20 tree instead of builds")
 ap.add_argument("--sparse", action="store_true", help="time dst_stree_set (2^12, 2^16, 2^20 keys into an empty depth-63 tree; 1, 256, 65 536 keys into the 2^20-key tree) and dst_stree_paths")
+ap.add_argument("--remove", action="store_true", help="time dst_stree_remove of 1, 256, 65 536 stored keys of the 2^20-key depth-63 tree, each just after a dst_stree_set of the same keys; dst_stree_compact after an apply of 65 536 empties; dst_stree_get of 4 096 keys beside dst_stree_paths")
 ap.add_argument("--sequence", action="store_true", help="time dst_rtree_apply / dst_stree_apply (1, 256, 4 096, 65 536 ordered writes) and, for 256, the loop of update + path calls")
 ap.add_argument("--verify", action="store_true", help="time dst_rescue_verify_writes on the witnesses of dst_rtree_apply / dst_stree_apply (256, 4 096, 65 536 writes), on the host for 256, and dst_rescue_verify_paths of 4 096 paths")
 ap.add_argument("sizes", nargs="*", type=int)
@@ -99,7 +102,7 @@ if args.update:
     print("dst_rtree_paths of %d indices: %.3f ms wall; %d calls of dst_rtree_path: %.2f ms wall (ctypes, no conversion): %.0f x" % (count, c_many * 1e3, count, c_single * 1e3, c_single / c_many))
     t.close()
     sys.exit(0)
-if args.sparse:
+if args.sparse or args.remove:
     DEPTH = 63
 
     def keys_and_leaves(count, seed):
@@ -110,6 +113,63 @@ if args.sparse:
         v[..., 1] >>= np.uint64(1)
         return k[:count], v
 
+if args.remove:
+    import ctypes
+    vp = lambda x: x.ctypes.data_as(ctypes.c_void_p)  # noqa: E731
+    keys, v = keys_and_leaves(1 << 20, 120)         # the 2^20-key tree of --sparse
+    big = D.SparseRescueTree(DEPTH, device=0, lib=lib)
+    big.set(keys, v)
+    L, h = big.lib, big._h
+    print("sparse depth %d: %d keys, %d stored nodes" % (DEPTH, big.info()["keys"], big.info()["nodes"]))
+
+    def timed(call):
+        """the C call alone -> (wall ms, device ms, last_digests)"""
+        t0 = time.perf_counter()
+        r = call()
+        wall = (time.perf_counter() - t0) * 1e3
+        assert r == 0, big._error(h)
+        i = big.info()
+        return wall, i["last_device_ms"], i["last_digests"]
+
+    rng = np.random.default_rng(4040)
+    live = keys.copy()                              # the stored keys, in random order: every run takes the next `count` of them
+    gone = ctypes.c_uint64(0)
+    for count in (1, 256, 65536):
+        sets, removes = [], []
+        for _ in range(1 + args.runs):              # the first is the warm-up: staging buffer, code
+            k, live = np.ascontiguousarray(live[:count]), live[count:]
+            new = rng.integers(0, 1 << 64, size=(count, 2, 2), dtype=np.uint64)
+            new[..., 1] >>= np.uint64(1)
+            sets.append(timed(lambda: L.dst_stree_set(h, vp(k), vp(new), ctypes.c_size_t(count))))      # the yardstick: existing code, the same keys, the same tree
+            removes.append(timed(lambda: L.dst_stree_remove(h, vp(k), ctypes.c_size_t(count), ctypes.byref(gone))))
+            assert gone.value == count
+        sets, removes = sets[1:], removes[1:]
+        s_ms, r_ms, s_wall, r_wall = min(x[1] for x in sets), min(x[1] for x in removes), min(x[0] for x in sets), min(x[0] for x in removes)
+        print("remove of %d stored keys from the 2^20-key tree: %.3f ms on the device (min of %d after one warm-up; all: %s), %d digests, %.1f ms wall (min; all: %s); "
+              "the set of the same keys just before: %.3f ms on the device (all: %s), %d digests, %.1f ms wall (all: %s); remove / set = %.3f on the device, %.3f wall; %d stored nodes left"
+              % (count, r_ms, len(removes), " ".join("%.3f" % x[1] for x in removes), removes[-1][2], r_wall, " ".join("%.1f" % x[0] for x in removes),
+                 s_ms, " ".join("%.3f" % x[1] for x in sets), sets[-1][2], s_wall, " ".join("%.1f" % x[0] for x in sets), r_ms / s_ms, r_wall / s_wall, big.info()["nodes"]))
+    count = 65536
+    k, live = np.ascontiguousarray(live[:count]), live[count:]
+    empties = np.zeros((count, 2, 2), dtype=np.uint64)
+    nodes = big.info()["nodes"]
+    a_wall, a_ms, a_digests = timed(lambda: L.dst_stree_apply(h, vp(k), vp(empties), ctypes.c_size_t(count), None, None))
+    c_wall, c_ms, c_digests = timed(lambda: L.dst_stree_compact(h, ctypes.byref(gone)))
+    assert gone.value == count and c_digests == 0
+    print("compact after an apply of %d empties: %.1f ms wall, %.3f ms on the device between the events (no level launch), %d digests, %d keys and %d of %d stored nodes dropped; "
+          "the apply: %.1f ms wall, %.3f ms on the device, %d digests" % (count, c_wall, c_ms, c_digests, gone.value, nodes - big.info()["nodes"], nodes, a_wall, a_ms, a_digests))
+    idx = np.ascontiguousarray(np.concatenate([live[rng.integers(0, live.size, size=2048)], rng.integers(0, 1 << DEPTH, size=2048, dtype=np.uint64)]))
+    out, flags, paths = np.zeros((idx.size, 2, 2), dtype=np.uint64), np.zeros(idx.size, dtype=np.uint8), np.zeros((idx.size, DEPTH + 1, 2, 2), dtype=np.uint64)
+    g_wall, p_wall = [], []
+    for _ in range(1 + args.runs):
+        g_wall.append(timed(lambda: L.dst_stree_get(h, vp(idx), ctypes.c_size_t(idx.size), vp(out), vp(flags)))[0])
+        p_wall.append(timed(lambda: L.dst_stree_paths(h, vp(idx), ctypes.c_size_t(idx.size), vp(paths)))[0])
+    assert np.array_equal(out, paths[:, 0]) and flags[:2048].all() and not flags[2048:].any()
+    print("dst_stree_get of %d indices (half stored, half absent) on the %d-key tree: %.3f ms wall (min of %d after one warm-up; all: %s), %d bytes back; dst_stree_paths of the same: %.3f ms wall (all: %s), %d bytes back"
+          % (idx.size, big.info()["keys"], min(g_wall[1:]), args.runs, " ".join("%.3f" % x for x in g_wall[1:]), 33 * idx.size, min(p_wall[1:]), " ".join("%.3f" % x for x in p_wall[1:]), 32 * (DEPTH + 1) * idx.size))
+    big.close()
+    sys.exit(0)
+if args.sparse:
     a = leaves(20)
     D.RescueTree(a, device=0, lib=lib).close()      # warm-up
     dense_ms = []

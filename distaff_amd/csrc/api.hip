@@ -627,6 +627,8 @@ int dst_proof_info(const uint8_t* proof, size_t len, dst_proof_info_t* info) {
 #include "host/stree_impl.h"
 // ---- checking paths and the witnesses of ordered writes (dst_rescue_path_roots, dst_rescue_verify_*): no tree, no context -------------------
 #include "host/path_verify_impl.h"
+// ---- compressed batch openings (dst_rescue_multiproof_*, dst_rtree_multiproof, dst_stree_multiproof): every shared ancestor once ------------
+#include "host/multiproof_impl.h"
 
 // ---- inspection --------------------------------------------------------------------------------------------------------------------
 int dst_read_buffer(dst_ctx* c, uint32_t what, uint32_t arg, uint8_t* out, size_t cap, size_t* len) {

@@ -490,6 +490,8 @@ int k_rescue_stree_level(hipStream_t stream, fe* nodes, const uint64_t* pref, co
 int k_rescue_stree_carry(hipStream_t stream, fe* dst, const fe* src, const uint32_t* from /* device */, size_t count);     // dst[j] = src[from[j]] unless from[j] == STREE_NEW
 // out[(i * (depth + 1) + k) ..] = node k of the path of indices[i], stored or empty; levels = (start, length) per level, empties = 2 elements per level (device)
 int k_rescue_stree_open(hipStream_t stream, const fe* nodes, const uint64_t* pref, const uint64_t* levels, const fe* empties, const uint64_t* indices, fe* out, size_t count, uint32_t depth);
+// out[2 s ..] = the node (level[s], prefix[s]), stored or the empty subtree of its level (all device): the nodes of a multiproof
+int k_rescue_stree_lookup(hipStream_t stream, const fe* nodes, const uint64_t* pref, const uint64_t* levels, const fe* empties, const uint64_t* prefix, const uint32_t* level, fe* out, size_t count);
 // out[2 i ..] = the leaf at indices[i] and stored[i] = 1, or the empty leaf and 0: one search of the leaf level [lstart, lstart + lcnt); empty on the host
 int k_rescue_stree_get(hipStream_t stream, const fe* nodes, const uint64_t* pref, size_t lstart, size_t lcnt, const fe* empty, const uint64_t* indices, fe* out, uint8_t* stored, size_t count);
 // flags[i] = whether leaves[i] (2 elements) is the empty leaf (host)
@@ -505,3 +507,6 @@ int k_rescue_tree_scatter_from(hipStream_t stream, fe* nodes, const uint32_t* po
 // the own-leaf roots and out[count .. 2 count) the substitute-leaf roots
 enum { RESCUE_PATH_OWN = 0, RESCUE_PATH_ALT = 1, RESCUE_PATH_BOTH = 2 };
 int k_rescue_path_roots(hipStream_t stream, const fe* paths, uint32_t n, const uint64_t* indices, size_t count, const fe* alt_leaves, uint32_t mode, fe* out /* 2 per chain */, uint32_t* bad);
+// multiproofs (host/multiproof_plan.h): one level of `count` jobs over the pool, pool[out] = digest(pool[left], pool[right]) with the three pool
+// indices of job j at jobs[3 j ..) (device); *bad = 1 for an element >= p in a pool node below `inputs` (the leaves and the supplied nodes)
+int k_rescue_multiproof_level(hipStream_t stream, fe* pool, const uint32_t* jobs, size_t count, uint32_t inputs, uint32_t* bad);

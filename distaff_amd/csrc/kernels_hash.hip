@@ -480,6 +480,17 @@ __global__ void rescue_stree_open_kernel(const fe* __restrict__ nodes, const uin
     const size_t start = levels[2 * level], pos = stree_find(pref + start, levels[2 * level + 1], prefix);
     out[t] = pos != STREE_ABSENT ? nodes[2 * (start + pos) + (t & 1)] : empties[2 * level + (t & 1)];
 }
+// the nodes of a multiproof (dst_stree_multiproof): one lane per (node, element); node s is (level[s], prefix[s]), found in its level's list like a
+// path node above, its level's empty subtree when it is not stored
+__global__ void rescue_stree_lookup_kernel(const fe* __restrict__ nodes, const uint64_t* __restrict__ pref, const uint64_t* __restrict__ levels, const fe* __restrict__ empties,
+                                           const uint64_t* __restrict__ prefix, const uint32_t* __restrict__ level, fe* __restrict__ out, size_t count) {
+    const size_t t = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (t >= 2 * count) return;
+    const size_t s = t >> 1;
+    const uint32_t l = level[s];
+    const size_t start = levels[2 * l], pos = stree_find(pref + start, levels[2 * l + 1], prefix[s]);
+    out[t] = pos != STREE_ABSENT ? nodes[2 * (start + pos) + (t & 1)] : empties[2 * l + (t & 1)];
+}
 // the leaves alone (dst_stree_get): one lane per index, one search of the leaf level [lstart, lstart + lcnt); a key that is not stored gives the
 // empty leaf (e0, e1) and stored[i] = 0
 __global__ void rescue_stree_get_kernel(const fe* __restrict__ nodes, const uint64_t* __restrict__ pref, size_t lstart, size_t lcnt, fe e0, fe e1,
@@ -514,6 +525,10 @@ int k_rescue_stree_carry(hipStream_t stream, fe* dst, const fe* src, const uint3
 int k_rescue_stree_open(hipStream_t stream, const fe* nodes, const uint64_t* pref, const uint64_t* levels, const fe* empties, const uint64_t* indices, fe* out, size_t count, uint32_t depth) {
     const size_t lanes = 2 * count * (depth + 1);
     hipLaunchKernelGGL(rescue_stree_open_kernel, dim3((unsigned)((lanes + HASH_THREADS - 1) / HASH_THREADS)), dim3(HASH_THREADS), 0, stream, nodes, pref, levels, empties, indices, out, count, depth);
+    return hipGetLastError() == hipSuccess ? 0 : -1;
+}
+int k_rescue_stree_lookup(hipStream_t stream, const fe* nodes, const uint64_t* pref, const uint64_t* levels, const fe* empties, const uint64_t* prefix, const uint32_t* level, fe* out, size_t count) {
+    hipLaunchKernelGGL(rescue_stree_lookup_kernel, dim3((unsigned)((2 * count + HASH_THREADS - 1) / HASH_THREADS)), dim3(HASH_THREADS), 0, stream, nodes, pref, levels, empties, prefix, level, out, count);
     return hipGetLastError() == hipSuccess ? 0 : -1;
 }
 int k_rescue_stree_get(hipStream_t stream, const fe* nodes, const uint64_t* pref, size_t lstart, size_t lcnt, const fe* empty, const uint64_t* indices, fe* out, uint8_t* stored, size_t count) {
@@ -675,5 +690,47 @@ int k_rescue_path_roots(hipStream_t stream, const fe* paths, uint32_t n, const u
     const dim3 grid((unsigned)((chains + per_block - 1) / per_block)), block(RESCUE_THREADS);
     if (spread) hipLaunchKernelGGL(rescue_path_root_spread_kernel, grid, block, 0, stream, paths, n, indices, count, alt_leaves, mode, chains, out, bad);
     else hipLaunchKernelGGL(rescue_path_root_kernel, grid, block, 0, stream, paths, n, indices, count, alt_leaves, mode, chains, out, bad);
+    return hipGetLastError() == hipSuccess ? 0 : -1;
+}
+
+// ---- multiproofs (dst_rescue_multiproof_root, dst_rescue_verify_multiproof, dst_rescue_multiproof_paths; host/multiproof_plan.h): the leaves of a
+//      set, the siblings nobody can recompute from them and every digest above them live in one pool of nodes, [leaves | supplied nodes | the
+//      results of the leaf level's parents | ... | the root].  One launch hashes the jobs of one level: job j is pool[out_j] = digest(pool[left_j],
+//      pool[right_j]), three 32-bit pool indices at jobs[3 j ..); every ancestor the paths share is one job, not one per path.  The jobs of a launch
+//      read only what the upload or an earlier launch wrote.  A pool index below `inputs` is a leaf or a supplied node -- each is read by exactly
+//      one job of the call -- and `bad` receives 1 when an element of it is not below p. -------------------------------------------------------------
+__global__ void __launch_bounds__(RESCUE_THREADS) rescue_multiproof_level_kernel(fe* pool, const uint32_t* __restrict__ jobs, size_t count, uint32_t inputs, uint32_t* __restrict__ bad) {
+    const size_t j = (size_t)blockIdx.x * RESCUE_THREADS + threadIdx.x;
+    if (j >= count) return;
+    const uint32_t left = jobs[3 * j], right = jobs[3 * j + 1], out = jobs[3 * j + 2];
+    const fe v0 = pool[2 * (size_t)left], v1 = pool[2 * (size_t)left + 1], v2 = pool[2 * (size_t)right], v3 = pool[2 * (size_t)right + 1];
+    if ((left < inputs && !(rescue_canonical(v0) && rescue_canonical(v1))) || (right < inputs && !(rescue_canonical(v2) && rescue_canonical(v3)))) *bad = 1u;
+    fe d0, d1;
+    rescue_digest4(v0, v1, v2, v3, d0, d1);
+    pool[2 * (size_t)out] = d0; pool[2 * (size_t)out + 1] = d1;
+}
+// the six-lanes-of-eight form (rescue_parent_spread): lanes 5, 4 hold l0, l1 and lanes 3, 2 hold r0, r1.  A group past the end is given job 0,
+// keeps the barriers and stores nothing.
+__global__ void __launch_bounds__(RESCUE_THREADS) rescue_multiproof_level_spread_kernel(fe* pool, const uint32_t* __restrict__ jobs, size_t count, uint32_t inputs, uint32_t* __restrict__ bad) {
+    __shared__ fe xch[RESCUE_THREADS];
+    const size_t g = (size_t)blockIdx.x * (RESCUE_THREADS / 8u) + (threadIdx.x >> 3);
+    const bool live = g < count;
+    const size_t j = live ? g : 0;
+    const uint32_t e = threadIdx.x & 7u;
+    fe v = fe_zero();                                                  // state after hasher.rs:18: (0, 0, r1, r0, l1, l0)
+    if (e >= 2u && e < 6u) {
+        const uint32_t from = jobs[3 * j + (e >= 4u ? 0u : 1u)];
+        v = pool[2 * (size_t)from + (1u - (e & 1u))];
+        if (live && from < inputs && !rescue_canonical(v)) *bad = 1u;
+    }
+    rescue_permute_lane(v, e, xch + (threadIdx.x & ~7u));
+    if (live && (e == 5u || e == 4u)) pool[2 * (size_t)jobs[3 * j + 2] + (5u - e)] = v;
+}
+int k_rescue_multiproof_level(hipStream_t stream, fe* pool, const uint32_t* jobs, size_t count, uint32_t inputs, uint32_t* bad) {
+    const bool spread = count <= RESCUE_SPREAD_MAX;
+    const size_t per_block = spread ? RESCUE_THREADS / 8 : RESCUE_THREADS;
+    const dim3 grid((unsigned)((count + per_block - 1) / per_block)), block(RESCUE_THREADS);
+    if (spread) hipLaunchKernelGGL(rescue_multiproof_level_spread_kernel, grid, block, 0, stream, pool, jobs, count, inputs, bad);
+    else hipLaunchKernelGGL(rescue_multiproof_level_kernel, grid, block, 0, stream, pool, jobs, count, inputs, bad);
     return hipGetLastError() == hipSuccess ? 0 : -1;
 }

@@ -61,7 +61,9 @@ EXPORTS = ["dst_ctx_create", "dst_ctx_destroy", "dst_last_error", "dst_phase_ms"
            "dst_stree_create", "dst_stree_set", "dst_stree_root", "dst_stree_paths", "dst_stree_tapes_many", "dst_stree_read_level", "dst_stree_info",
            "dst_stree_destroy", "dst_stree_last_error", "dst_rtree_apply", "dst_stree_apply", "dst_rescue_path_tapes",
            "dst_rescue_path_roots", "dst_rescue_verify_paths", "dst_rescue_verify_writes",
-           "dst_stree_remove", "dst_stree_compact", "dst_stree_get"]
+           "dst_stree_remove", "dst_stree_compact", "dst_stree_get",
+           "dst_rescue_multiproof_size", "dst_rtree_multiproof", "dst_stree_multiproof", "dst_rescue_multiproof_root", "dst_rescue_verify_multiproof",
+           "dst_rescue_multiproof_paths"]
 
 
 class DistaffError(RuntimeError):
@@ -398,6 +400,91 @@ def verify_writes(root_before, indices, paths, leaves, roots=None, device=0, lib
     return first.value, why.value, tuple(arr_to_ints(after))
 
 
+def multiproof_size(n, indices, lib=None):
+    """(M, digests) of the multiproof of the distinct leaf indices `indices` for paths of n nodes (dst_rescue_multiproof_size; host only, no
+    hashing): how many sibling nodes it supplies and how many parents its check computes"""
+    lib = lib or load()
+    idx, ip = RescueTree._indices(indices)
+    m, d = ctypes.c_size_t(0), ctypes.c_uint64(0)
+    r = lib.dst_rescue_multiproof_size(ctypes.c_uint32(n), ip, ctypes.c_size_t(idx.size), ctypes.byref(m), ctypes.byref(d))
+    if r != DST_OK:
+        raise DistaffError(r, _rtree_error(lib) or "dst_rescue_multiproof_size failed")
+    return m.value, d.value
+
+
+def _multiproof_args(indices, leaves, nodes):
+    idx, ip = RescueTree._indices(indices)
+    a = _nodes_for(leaves, idx.size, "leaves")
+    b = _elements(nodes, 2) if len(nodes) else np.zeros((0, 2, 2), dtype=np.uint64)
+    return idx, ip, a, b
+
+
+def _tree_multiproof(tree, call, indices, words):
+    """(leaves, nodes) of a tree's multiproof through `call`: size query, then the gather"""
+    idx, ip = RescueTree._indices(indices)
+    m = ctypes.c_size_t(0)
+    tree._check(call(tree._h, ip, ctypes.c_size_t(idx.size), None, None, ctypes.c_size_t(0), ctypes.byref(m)))
+    leaves = np.zeros((idx.size, 2, 2), dtype=np.uint64)
+    nodes = np.zeros((m.value, 2, 2), dtype=np.uint64)
+    if idx.size:
+        spare = np.zeros((1, 2, 2), dtype=np.uint64)                     # a set that needs no sibling still asks for the leaves
+        tree._check(call(tree._h, ip, ctypes.c_size_t(idx.size), _ptr(leaves), _ptr(nodes) if m.value else _ptr(spare), ctypes.c_size_t(m.value), ctypes.byref(m)))
+    return (leaves, nodes) if words else (_pairs(leaves), _pairs(nodes))
+
+
+def multiproof_root(n, indices, leaves, nodes, device=0, lib=None, stats=None):
+    """the root a multiproof resolves to (dst_rescue_multiproof_root) -> a pair of ints.  `leaves` in the order of `indices`, `nodes` as
+    RescueTree.multiproof returns them (pairs of ints, or uint64 words [count, 2, 2]).  With other leaves over the same nodes: the root after
+    those unordered writes.  Every shared ancestor is hashed once; stats (a dict) receives digests and device_ms."""
+    lib = lib or load()
+    idx, ip, a, b = _multiproof_args(indices, leaves, nodes)
+    out = np.zeros((2, 2), dtype=np.uint64)
+    d, ms = ctypes.c_uint64(0), ctypes.c_double(0)
+    r = lib.dst_rescue_multiproof_root(ctypes.c_int(device), ctypes.c_uint32(n), ip, _ptr(a) if idx.size else None, ctypes.c_size_t(idx.size), _ptr(b) if b.shape[0] else None,
+                                       ctypes.c_size_t(b.shape[0]), _ptr(out), ctypes.byref(d), ctypes.byref(ms))
+    if r != DST_OK:
+        raise DistaffError(r, _rtree_error(lib) or "dst_rescue_multiproof_root failed")
+    if stats is not None:
+        stats["digests"], stats["device_ms"] = d.value, ms.value
+    return tuple(arr_to_ints(out))
+
+
+def verify_multiproof(root, n, indices, leaves, nodes, device=0, lib=None, stats=None):
+    """whether the multiproof resolves to `root` (dst_rescue_verify_multiproof) -> bool; one that does not is a result, not an exception"""
+    lib = lib or load()
+    idx, ip, a, b = _multiproof_args(indices, leaves, nodes)
+    r0 = _nodes_for([tuple(root)], 1, "roots")
+    ok, ms = ctypes.c_int(0), ctypes.c_double(0)
+    r = lib.dst_rescue_verify_multiproof(ctypes.c_int(device), _ptr(r0), ctypes.c_uint32(n), ip, _ptr(a) if idx.size else None, ctypes.c_size_t(idx.size),
+                                         _ptr(b) if b.shape[0] else None, ctypes.c_size_t(b.shape[0]), ctypes.byref(ok), ctypes.byref(ms))
+    if r != DST_OK:
+        raise DistaffError(r, _rtree_error(lib) or "dst_rescue_verify_multiproof failed")
+    if stats is not None:
+        stats["device_ms"] = ms.value
+    return bool(ok.value)
+
+
+def multiproof_paths(n, indices, leaves, nodes, device=0, lib=None, stats=None, words=False):
+    """the full authentication paths a multiproof stands for (dst_rescue_multiproof_paths) -> (paths, root): paths in the shape
+    RescueTree.paths returns (words=True: uint64 words [count, n, 2, 2]), in the order of `indices` -- what path_tapes, path_roots and
+    verify_paths take -- and the root they resolve to"""
+    lib = lib or load()
+    idx, ip, a, b = _multiproof_args(indices, leaves, nodes)
+    out = np.zeros((max(idx.size, 1), max(n, 1), 2, 2), dtype=np.uint64)
+    root = np.zeros((2, 2), dtype=np.uint64)
+    ms = ctypes.c_double(0)
+    r = lib.dst_rescue_multiproof_paths(ctypes.c_int(device), ctypes.c_uint32(n), ip, _ptr(a) if idx.size else None, ctypes.c_size_t(idx.size), _ptr(b) if b.shape[0] else None,
+                                        ctypes.c_size_t(b.shape[0]), _ptr(out), _ptr(root), ctypes.byref(ms))
+    if r != DST_OK:
+        raise DistaffError(r, _rtree_error(lib) or "dst_rescue_multiproof_paths failed")
+    if stats is not None:
+        stats["device_ms"] = ms.value
+    if words:
+        return out[:idx.size], tuple(arr_to_ints(root))
+    v = arr_to_ints(out[:idx.size])
+    return [[(v[2 * (i * n + k)], v[2 * (i * n + k) + 1]) for k in range(n)] for i in range(idx.size)], tuple(arr_to_ints(root))
+
+
 def _apply(tree, call, n, indices, leaves):
     """(paths, roots) of an ordered batch of writes: paths in the shape paths() returns, roots a list of pairs of ints"""
     idx, ip = RescueTree._indices(indices)
@@ -510,6 +597,13 @@ class RescueTree:
         self._check(self.lib.dst_rtree_paths(self._h, ip, ctypes.c_size_t(idx.size), _ptr(out)))
         v = arr_to_ints(out[:idx.size * n])
         return [[(v[2 * (i * n + k)], v[2 * (i * n + k) + 1]) for k in range(n)] for i in range(idx.size)]
+
+    def multiproof(self, indices, words=False):
+        """the multiproof of the DISTINCT leaves `indices`, any order (dst_rtree_multiproof) -> (leaves, nodes): the leaves in the order of
+        `indices` and the sibling nodes that cannot be recomputed from them, level by level from the leaf level up, ascending within a level
+        -- lists of pairs of ints, or uint64 words [count, 2, 2] and [M, 2, 2] with words=True.  multiproof_root / verify_multiproof check it
+        against a root, multiproof_paths expands it into paths(indices)."""
+        return _tree_multiproof(self, self.lib.dst_rtree_multiproof, indices, words)
 
     def tapes_many(self, indices, what=3):
         """tapes(i, what) for every i of `indices` in one call (dst_rtree_tapes_many): a list of (A, B)"""
@@ -639,6 +733,11 @@ class SparseRescueTree:
 
     def path(self, index):
         return self.paths([index])[0]
+
+    def multiproof(self, indices, words=False):
+        """RescueTree.multiproof with n = depth + 1 for distinct keys, stored or not (dst_stree_multiproof) -> (leaves, nodes); a leaf or a
+        sibling that is not stored is the empty subtree of its level, so absent keys are proven by the same call"""
+        return _tree_multiproof(self, self.lib.dst_stree_multiproof, indices, words)
 
     def tapes_many(self, indices, what=3):
         """RescueTree.tapes_many with n = depth + 1 (dst_stree_tapes_many): a list of (A, B)"""

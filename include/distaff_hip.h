@@ -235,8 +235,47 @@ DST_API int dst_rescue_verify_paths(int device, const uint8_t root[32], const ui
 DST_API int dst_rescue_verify_writes(int device, const uint8_t root_before[32], const uint8_t* paths, uint32_t n, const uint64_t* indices,
                                      const uint8_t* leaves /* count*32 */, const uint8_t* roots /* count*32, or NULL */, size_t count,
                                      int64_t* first_bad, uint32_t* why, uint8_t root_after[32], double* device_ms);
+
+/* ---- compressed batch openings (multiproofs): the paths of many leaves without the nodes they share.  `count` independent paths are
+ * count*n*32 bytes and count*(n-1) digests to check, however much of the tree they share; a multiproof ships every needed node once and its
+ * check computes every shared ancestor once.  It is the node set of the reference's BatchMerkleProof (prove_batch / verify_batch,
+ * src/crypto/merkle.rs:64-263), laid out level by level.  Conventions of dst_rescue_path_roots: n = the nodes of a path, 2 <= n <= 64,
+ * D = n - 1 the depth (log_leaves of a dense tree, depth of a sparse one); node (l, p) is the node of level l at position p < 2^l, level D holds
+ * the leaves, level 0 is the root (heap position 2^l + p of a dense tree's node array).
+ * For a set S of `count` DISTINCT leaf indices below 2^D let K_D = S and K_{l-1} = { p >> 1 : p in K_l }.  The supplied siblings of level l are
+ * the nodes (l, p ^ 1) with p in K_l and p ^ 1 not in K_l.  A multiproof of S is
+ *   leaves: count nodes, leaves[i] = the leaf at indices[i], in the caller's order (any order);
+ *   nodes:  the supplied siblings of level D, then of level D - 1, ... down to level 1, ascending by position within a level.
+ * Their number M = sum over l = 1 .. D of #{ p in K_l : p ^ 1 not in K_l } and their order depend only on S and D, never on the order of
+ * `indices`; checking computes digests = sum over l = 0 .. D - 1 of |K_l| parents.
+ * DST_ERR_ARG: a null pointer with count > 0, n outside 2 .. 64, an index not below 2^(n-1), a repeated index, num_nodes != M, count >= 2^31,
+ * count + M + digests >= 2^32, count = 0 in the three hashing calls (a proof of nothing proves nothing) -- all found on the host before anything
+ * is queued -- and an element of leaves or nodes not below p, found before any result is written (on the host, or by the kernel as in the path
+ * checks).  The tree-less calls report errors by dst_rtree_last_error(NULL); device < 0 runs on the host, one thread, no HIP call. */
+/* M and the digest count of a set, no hashing (host only); count = 0 gives 0 and 0 */
+DST_API int dst_rescue_multiproof_size(uint32_t n, const uint64_t* indices, size_t count, size_t* num_nodes, uint64_t* digests);
+/* the multiproof of `count` distinct leaves of a tree (n = log_leaves + 1): leaves receives count*32 bytes, nodes *num_nodes * 32 <= cap_nodes * 32.
+ * nodes == NULL: size query, only *num_nodes is written.  On a device tree: one upload of positions, one gather launch, one copy back, whatever
+ * count is.  count = 0: DST_OK with 0 nodes.  The tree is never changed. */
+DST_API int dst_rtree_multiproof(const dst_rtree* t, const uint64_t* indices, size_t count, uint8_t* leaves /* count*32 */,
+                                 uint8_t* nodes /* cap_nodes*32, or NULL */, size_t cap_nodes, size_t* num_nodes);
+/* the root a multiproof resolves to; *digests (may be NULL) = how many parents were computed.  device >= 0: one upload (leaves, nodes and the job
+ * lists of every level), at most n - 1 level launches, one synchronisation, one copy back; *device_ms (may be NULL): events around the launches.
+ * Called with OTHER leaves over the same nodes it gives the root after those unordered writes -- the supplied siblings are exactly the nodes
+ * such writes do not change -- which is how a client that holds only a root follows dst_rtree_update / dst_stree_set of stored keys. */
+DST_API int dst_rescue_multiproof_root(int device, uint32_t n, const uint64_t* indices, const uint8_t* leaves /* count*32 */, size_t count,
+                                       const uint8_t* nodes /* num_nodes*32 */, size_t num_nodes, uint8_t root[32], uint64_t* digests, double* device_ms);
+/* *ok = 1 when the multiproof resolves to `root`, else 0: a multiproof that does not is NOT an error, the call returns DST_OK */
+DST_API int dst_rescue_verify_multiproof(int device, const uint8_t root[32], uint32_t n, const uint64_t* indices, const uint8_t* leaves /* count*32 */,
+                                         size_t count, const uint8_t* nodes /* num_nodes*32 */, size_t num_nodes, int* ok, double* device_ms);
+/* the expansion: the `count` full authentication paths in dst_rtree_path's layout, in the order of `indices` -- what dst_rescue_path_tapes and
+ * the path checks take -- and the root they resolve to (to be held against the root the caller trusts).  device >= 0: the level launches of
+ * dst_rescue_multiproof_root, one gather launch, one copy back. */
+DST_API int dst_rescue_multiproof_paths(int device, uint32_t n, const uint64_t* indices, const uint8_t* leaves /* count*32 */, size_t count,
+                                        const uint8_t* nodes /* num_nodes*32 */, size_t num_nodes, uint8_t* paths /* count*n*32 */, uint8_t root[32],
+                                        double* device_ms);
 DST_API void dst_rtree_destroy(dst_rtree* t);
-DST_API const char* dst_rtree_last_error(const dst_rtree* t);     /* t may be NULL: the error of the calling thread's last failed dst_rtree_build / dst_rescue_digest_many / dst_rescue_path_tapes / dst_rescue_path_roots / dst_rescue_verify_* */
+DST_API const char* dst_rtree_last_error(const dst_rtree* t);     /* t may be NULL: the error of the calling thread's last failed dst_rtree_build / dst_rescue_digest_many / dst_rescue_path_tapes / dst_rescue_path_roots / dst_rescue_verify_* / dst_rescue_multiproof_* */
 
 /* ---- sparse Rescue Merkle trees: a set addressed by keys of up to 63 bits (accounts, notes, nullifiers) ------------------------------------
  * A sparse tree of depth D, 1 <= D <= 63, IS the dense tree above over 2^D leaves in which every leaf that was never set holds the tree's empty
@@ -284,6 +323,10 @@ DST_API int dst_stree_root(const dst_stree* t, uint8_t root[32]);
  * not stored is the E_l of its level; a path whose leaf is E_depth proves that the key is empty.  On a device tree: one upload, one launch, one
  * copy back, whatever count is. */
 DST_API int dst_stree_paths(const dst_stree* t, const uint64_t* indices, size_t count, uint8_t* paths /* count*(depth+1)*32 */);
+/* dst_rtree_multiproof with n = depth + 1 for `count` distinct keys below 2^depth, stored or not: an unstored leaf or sibling is the E_l of its
+ * level, as in dst_stree_paths, so absent keys are proven by the same call.  On a device tree: one upload, one lookup launch, one copy back. */
+DST_API int dst_stree_multiproof(const dst_stree* t, const uint64_t* indices, size_t count, uint8_t* leaves /* count*32 */,
+                                 uint8_t* nodes /* cap_nodes*32, or NULL */, size_t cap_nodes, size_t* num_nodes);
 /* dst_rtree_apply on a sparse tree: ordered writes to keys below 2^depth, stored or not, repeats allowed; paths of depth + 1 nodes.  The old leaf
  * of a key that is not stored before operation i is E_depth, a sibling subtree without keys the E_l of its level.  Afterwards the tree is what
  * dst_stree_set makes of the distinct keys with the later value of each (a key written with the empty value stays stored).  On a device tree: depth

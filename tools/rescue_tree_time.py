@@ -10,6 +10,8 @@ device's own modular-multiplication rate sets.
                                                      of 2^20 keys), beside the loop of single-leaf updates and single paths they replace
     python tools/rescue_tree_time.py --verify        checking the witnesses of those ordered writes (dst_rescue_verify_writes, one launch) beside the apply that
                                                      made them, the same check on the host for 256 writes, and dst_rescue_verify_paths of 4 096 paths
+    python tools/rescue_tree_time.py --multiproof    compressed batch openings: bytes, digests and the device time of dst_rescue_multiproof_root beside
+                                                     dst_rescue_verify_paths on the full paths of the same leaves (K = 256, 4 096, 65 536; both trees above)
 One digest is counted as 9 180 field multiplications, the reference's own count per hasher::digest: ten rounds of 6 x 2 for the cubes, 6 x 139
 for x^INV_ALPHA by the addition chain (127 squarings + 12 multiplications) and 2 x 36 for the two MDS products."""
 import argparse
@@ -33,6 +35,7 @@ ap.add_argument("--sparse", action="store_true", help="time dst_stree_set (2^12,
 ap.add_argument("--remove", action="store_true", help="time dst_stree_remove of 1, 256, 65 536 stored keys of the 2^20-key depth-63 tree, each just after a dst_stree_set of the same keys; dst_stree_compact after an apply of 65 536 empties; dst_stree_get of 4 096 keys beside dst_stree_paths")
 ap.add_argument("--sequence", action="store_true", help="time dst_rtree_apply / dst_stree_apply (1, 256, 4 096, 65 536 ordered writes) and, for 256, the loop of update + path calls")
 ap.add_argument("--verify", action="store_true", help="time dst_rescue_verify_writes on the witnesses of dst_rtree_apply / dst_stree_apply (256, 4 096, 65 536 writes), on the host for 256, and dst_rescue_verify_paths of 4 096 paths")
+ap.add_argument("--multiproof", action="store_true", help="time dst_rescue_multiproof_root of 256, 4 096, 65 536 distinct leaves of the dense 2^20 tree and of the depth-63 tree of 2^20 keys beside dst_rescue_verify_paths on the full paths of the same leaves; bytes and digests of both")
 ap.add_argument("sizes", nargs="*", type=int)
 args = ap.parse_args()
 lib = D.lib._open(os.path.abspath(args.lib)) if args.lib else None       # through the binding: one HIP runtime per process
@@ -223,6 +226,81 @@ if args.sparse:
     t0 = time.perf_counter(); w = big.paths_words(idx); s_many = time.perf_counter() - t0
     print("dst_stree_paths of %d indices (half stored, half absent) on the %d-key tree: %.3f ms wall (%d nodes of %d searched levels each)" % (idx.size, big.info()["keys"], s_many * 1e3, DEPTH + 1, DEPTH + 1))
     big.close()
+    sys.exit(0)
+if args.multiproof:
+    import ctypes
+    vp = lambda x: x.ctypes.data_as(ctypes.c_void_p)  # noqa: E731
+    rng = np.random.default_rng(5050)
+
+    def time_multiproofs(name, tree, n, draw, multiproof, open_paths):
+        """per K: the tree's multiproof of K random distinct leaves, its bytes and digests beside those of K full paths, and
+        dst_rescue_multiproof_root's device_ms beside dst_rescue_verify_paths' on the full paths of the same leaves (existing code: the yardstick)"""
+        L = tree.lib
+        root = D.ints_to_arr(tree.root)
+        for count in (256, 4096, 65536):
+            idx = draw(count)
+            m, digests, dms = ctypes.c_size_t(0), ctypes.c_uint64(0), ctypes.c_double(0)
+            assert multiproof(tree._h, vp(idx), ctypes.c_size_t(count), None, None, ctypes.c_size_t(0), ctypes.byref(m)) == 0
+            lv, nodes, got = np.zeros((count, 2, 2), dtype=np.uint64), np.zeros((m.value + 1, 2, 2), dtype=np.uint64), np.zeros((2, 2), dtype=np.uint64)
+            t0 = time.perf_counter()
+            assert multiproof(tree._h, vp(idx), ctypes.c_size_t(count), vp(lv), vp(nodes), ctypes.c_size_t(m.value), ctypes.byref(m)) == 0
+            take_wall = (time.perf_counter() - t0) * 1e3
+            t0 = time.perf_counter()
+            paths = open_paths(idx)
+            paths_wall = (time.perf_counter() - t0) * 1e3
+            first, why = ctypes.c_int64(0), ctypes.c_uint32(0)
+            mp_ms, mp_wall, pv_ms, pv_wall = [], [], [], []
+            for _ in range(1 + args.runs):          # the first is the warm-up: code; the two checks alternate
+                t0 = time.perf_counter()
+                r = L.dst_rescue_multiproof_root(ctypes.c_int(0), ctypes.c_uint32(n), vp(idx), vp(lv), ctypes.c_size_t(count), vp(nodes), ctypes.c_size_t(m.value), vp(got), ctypes.byref(digests), ctypes.byref(dms))
+                mp_wall.append((time.perf_counter() - t0) * 1e3)
+                assert r == 0 and np.array_equal(got, root)
+                mp_ms.append(dms.value)
+                t0 = time.perf_counter()
+                r = L.dst_rescue_verify_paths(ctypes.c_int(0), vp(root), vp(paths), ctypes.c_uint32(n), vp(idx), None, ctypes.c_size_t(count), ctypes.byref(first), ctypes.byref(why), ctypes.byref(dms))
+                pv_wall.append((time.perf_counter() - t0) * 1e3)
+                assert r == 0 and (first.value, why.value) == (-1, 0)
+                pv_ms.append(dms.value)
+            mp_ms, mp_wall, pv_ms, pv_wall = mp_ms[1:], mp_wall[1:], pv_ms[1:], pv_wall[1:]
+            expanded, dms2 = np.zeros((count, n, 2, 2), dtype=np.uint64), ctypes.c_double(0)
+            assert L.dst_rescue_multiproof_paths(ctypes.c_int(0), ctypes.c_uint32(n), vp(idx), vp(lv), ctypes.c_size_t(count), vp(nodes), ctypes.c_size_t(m.value), vp(expanded), vp(got), ctypes.byref(dms2)) == 0
+            assert np.array_equal(expanded, paths)
+            mp_bytes, path_bytes = 32 * (count + m.value), 32 * count * n
+            print("%s, K = %d: multiproof %d bytes (%d leaves + %d nodes) against %d bytes of paths = %.2f x fewer; %d digests against %d = %.2f x fewer; "
+                  "multiproof_root %.3f ms on the device (min of %d after one warm-up; all: %s), %.2f ms wall (min); verify_paths of the same leaves %.3f ms on the device (all: %s), %.2f ms wall (min); "
+                  "multiproof / paths = %.3f on the device, %.3f wall; taking it from the tree %.2f ms wall against %.2f ms for the paths; expansion with the gather %.3f ms on the device"
+                  % (name, count, mp_bytes, count, m.value, path_bytes, path_bytes / mp_bytes, digests.value, count * (n - 1), count * (n - 1) / digests.value,
+                     min(mp_ms), len(mp_ms), " ".join("%.3f" % v for v in mp_ms), min(mp_wall), min(pv_ms), " ".join("%.3f" % v for v in pv_ms), min(pv_wall),
+                     min(mp_ms) / min(pv_ms), min(mp_wall) / min(pv_wall), take_wall, paths_wall, dms2.value))
+
+    log_leaves = 20
+    t = D.RescueTree(leaves(log_leaves), device=0, lib=lib)
+
+    def dense_paths(idx):
+        out = np.zeros((idx.size, log_leaves + 1, 2, 2), dtype=np.uint64)
+        assert t.lib.dst_rtree_paths(t._h, vp(idx), ctypes.c_size_t(idx.size), vp(out)) == 0
+        return out
+
+    time_multiproofs("dense 2^%d leaves" % log_leaves, t, log_leaves + 1, lambda count: np.ascontiguousarray(rng.permutation(1 << log_leaves)[:count].astype(np.uint64)),
+                     t.lib.dst_rtree_multiproof, dense_paths)
+    t.close()
+    DEPTH = 63
+    keys = np.unique(rng.integers(0, 1 << DEPTH, size=(1 << 20) + (1 << 17), dtype=np.uint64))
+    rng.shuffle(keys)
+    keys = keys[:1 << 20]
+    v = rng.integers(0, 1 << 64, size=(keys.size, 2, 2), dtype=np.uint64)
+    v[..., 1] >>= np.uint64(1)
+    s = D.SparseRescueTree(DEPTH, device=0, lib=lib)
+    s.set(keys, v)
+    print("sparse depth %d: %d keys, %d stored nodes" % (DEPTH, s.info()["keys"], s.info()["nodes"]))
+
+    def sparse_draw(count):                         # distinct: half stored keys, half keys that are (almost surely) absent
+        half = keys[rng.permutation(keys.size)[:count // 2]]
+        other = rng.integers(0, 1 << DEPTH, size=count - count // 2 + 8, dtype=np.uint64)
+        return np.ascontiguousarray(rng.permutation(np.unique(np.concatenate([half, other])))[:count])
+
+    time_multiproofs("sparse depth %d, 2^20 keys" % DEPTH, s, DEPTH + 1, sparse_draw, s.lib.dst_stree_multiproof, s.paths_words)
+    s.close()
     sys.exit(0)
 if args.sequence or args.verify:
     import ctypes

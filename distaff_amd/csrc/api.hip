@@ -96,6 +96,7 @@ static int ctx_init(dst_ctx* c) {
     // sharded contexts: the coefficient vectors are all-gathered in rounds of `world` registers (dst_prove_sharded), so the array holds
     // a whole number of rounds
     if ((r = dev_alloc(c, &c->polys, (c->W + c->prm.world - 1) / c->prm.world * c->prm.world * n))) return r;
+    if (c->plan.coeff_tile_major && (r = dev_alloc(c, &c->polys_tm, c->W * n))) return r;      // the coefficients in the extension's tile order (ctx.h)
     if ((r = dev_alloc(c, &c->lde, c->W * Nl))) return r;
     if (c->j0 == 0 && c->Bc > 1 && !c->sw_is("DISTAFF_TRACE_BUFFER", "1")) { c->trace = c->lde; c->trace_stride = Nl; }     // see ctx.h; DISTAFF_TRACE_BUFFER=1: separate buffer + copy (tests)
     else { if ((r = dev_alloc(c, &c->trace, c->W * n))) return r; c->trace_stride = n; }
@@ -253,13 +254,13 @@ int dst_commit_trace(dst_ctx* c, uint8_t trace_root[32]) {
         for (size_t g = 0; g + 1 < c->upload_bounds.size(); g++) {
             const size_t first = c->upload_bounds[g], cnt = c->upload_bounds[g + 1] - first;
             HIP_TRY(c, hipStreamWaitEvent(c->stream, c->upload_done[g], 0));
-            k_intt_columns(c, c->trace + first * c->trace_stride, c->trace_stride, c->polys + first * c->n, cnt);
-            k_lde_columns(c, c->polys + first * c->n, c->lde + first * c->Bc * c->n, cnt);
+            k_intt_columns(c, c->trace + first * c->trace_stride, c->trace_stride, c->polys + first * c->n, cnt, polys_tm_at(c, first));
+            k_lde_columns(c, c->polys + first * c->n, c->lde + first * c->Bc * c->n, cnt, polys_tm_at(c, first));
         }
         c->upload_pending = false;
     } else {
-        k_intt_columns(c, c->trace, c->trace_stride, c->polys, c->W);   // interpolate_fft_twiddles (trace_table.rs:159)
-        k_lde_columns(c, c->polys, c->lde, c->W);                    // eval_fft_twiddles over the LDE domain (trace_table.rs:166)
+        k_intt_columns(c, c->trace, c->trace_stride, c->polys, c->W, c->polys_tm);   // interpolate_fft_twiddles (trace_table.rs:159)
+        k_lde_columns(c, c->polys, c->lde, c->W, c->polys_tm);       // eval_fft_twiddles over the LDE domain (trace_table.rs:166)
     }
     HIP_TRY(c, hipEventRecord(c->ph_ev[5], c->stream));         // end of the extension: the host does not wait here
     k_trace_leaves(c);                                           // trace_table.rs:174-185

@@ -157,7 +157,10 @@ struct NttPlan {
     uint32_t count = 0;                              // 2 or 3
     bool coset_slow = false; uint32_t debug = 0;     // DISTAFF_NTT_ORDER=0, DISTAFF_NTT_DEBUG
     bool tile_major = false;                         // layout of the staging array and the four-step tables (kernels_ntt.hip: ntt_tile_major)
-    NttPass pass[3], first_lde;                      // first_lde: pass[0] as the first pass of an extension (its DIT mode, LDS bytes and instance differ)
+    // the interpolation also leaves the trace coefficients in the first pass's tile order (dst_ctx::polys_tm) and the extension reads them
+    // there: tile-major plans whose first pass has no register pre-stage (n <= 2^20)
+    bool coeff_tile_major = false;
+    NttPass pass[3], first_lde;                     // first_lde: pass[0] as the first pass of an extension (its DIT mode, LDS bytes and instance differ)
     const NttPass& at(uint32_t i, bool lde) const { return (i == 0 && lde) ? first_lde : pass[i]; }
 };
 
@@ -222,6 +225,10 @@ struct dst_ctx {
 
     // data (device)
     fe *trace = nullptr, *polys = nullptr, *lde = nullptr, *tmp = nullptr;
+    // [W][n] or nullptr (NttPlan::coeff_tile_major): the coefficients of `polys` once more, element (m1, m2) of a register (coefficient
+    // m1 * n2 + m2) at ((m2 >> 2) * n1 + m1) * 4 + (m2 & 3) -- a first-pass tile of the extension (four adjacent m2, every m1) is one contiguous
+    // block.  Written by k_intt_columns beside `polys`, read by k_lde_columns alone; everything else reads `polys` in natural order.
+    fe *polys_tm = nullptr;
     size_t tmp_regs = 4;                // tmp (and tmp2) hold tmp_regs x Bc arrays of n elements
     // register r of the trace starts at trace + r * trace_stride.  A context that owns coset 0 of the extension keeps the trace IN the
     // coset-0 slots of `lde` (trace == lde, trace_stride == Bc * n): coset 0 of the extension is the trace itself, nothing is copied
@@ -414,8 +421,14 @@ inline bool fri_tail_starts_at(const dst_ctx* c, int d) {
 // ---- kernel launchers (kernels_*.hip) ------------------------------------------------------------------------------------
 // NTT / LDE
 int k_ntt_init(dst_ctx* c);                                                             // context creation: derives c->plan, builds every table of it, raises the LDS limits
-void k_intt_columns(dst_ctx* c, const fe* src, size_t src_stride, fe* dst, size_t ncols); // size-n inverse NTT of ncols columns src_stride apart -> contiguous columns
-void k_lde_columns(dst_ctx* c, const fe* polys, fe* lde, size_t ncols);                 // n coefficients -> coset-major [Bc][n] per column
+// size-n inverse NTT of ncols columns src_stride apart -> contiguous columns; dst_tm (a view of c->polys_tm at the same registers, or nullptr):
+// the same coefficients once more in the extension's tile order
+void k_intt_columns(dst_ctx* c, const fe* src, size_t src_stride, fe* dst, size_t ncols, fe* dst_tm = nullptr);
+// n coefficients -> coset-major [Bc][n] per column; polys_tm: what k_intt_columns wrote beside THESE columns -- the first pass reads it instead.
+// A caller whose coefficients came another way (all-gathered pieces) hands none and the first pass reads `polys` row-major.
+void k_lde_columns(dst_ctx* c, const fe* polys, fe* lde, size_t ncols, const fe* polys_tm = nullptr);
+// the registers from `first` on of c->polys_tm, or nullptr where the plan keeps no such copy
+static inline fe* polys_tm_at(dst_ctx* c, size_t first) { return c->polys_tm ? c->polys_tm + first * c->n : nullptr; }
 void k_lde_fold8(dst_ctx* c, const fe* poly8n, fe* out);                                // 8n coefficients -> coset-major [Bc][n]
 void k_intt8_cosets(dst_ctx* c, fe* vals /* [8][n] coset-major, in place scratch */, fe* out8n, fe* work);
 void k_coset_to_natural_len(dst_ctx* c, const fe* src, size_t cosets, size_t len, fe* dst);   // [cosets][len] -> natural [len*cosets]

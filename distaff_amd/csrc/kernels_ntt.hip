@@ -54,6 +54,12 @@ struct NttArgs {
     // Every instance whose tiles can be four columns wide reads the flag (uniform): the 1024 x 4 second pass also serves row-major plans
     // (DISTAFF_NTT=lds at 2^21: 2048 x 2 first pass).
     uint32_t tile_major;
+    // The trace coefficients in the same tile-major map (dst_ctx::polys_tm; n1, n2 of the plan: element (m1, m2) = coefficient m1 * n2 + m2).
+    // src_tile_major (first pass of an extension, four-column tiles, no pre-stage): `src` is that array -- a tile is one contiguous block of
+    // 16 * n1 * 4 bytes instead of n1 64-byte segments a row apart, each sharing its 128-byte line with the neighbouring tile.  dst_tm (last pass of
+    // the interpolation, or nullptr): where the pass stores every result once more in that order, beside the natural-order `dst`.
+    uint32_t src_tile_major;
+    fe* dst_tm;
     uint32_t log_n1, log_n2, tile /* log2 of the tile width */, log_N, log_b;
     uint32_t j0;               // global index of the first local coset
     uint32_t has_scale;        // 1: multiply the result by `scale` (1/n of inverse transforms)
@@ -115,15 +121,22 @@ struct OutB {                                          // natural-order store X[
     static constexpr bool active = true;
     fe* __restrict__ dst /* at the tile's first k1 */; uint32_t k_stride, log_n2; bool scale; fe_tw s;
     uint32_t pre_shift, h;                             // register pre-stage: the tile holds the frequencies k2 = (k' << pre_shift) + h
+    // NttArgs::dst_tm (uniform; nullptr in every launch but the interpolation's): the array's start, the tile's first k1 and the plan's log2 n1, log2 n2
+    fe* __restrict__ dst_tm; uint32_t k0, log_rows, log_cols;
     struct Tok {};
     __device__ __forceinline__ Tok pre(uint32_t, uint32_t) const { return Tok{}; }
     __device__ __forceinline__ void put(uint32_t row, uint32_t t, const fe& v, const Tok&) const {
         const uint32_t k2 = ((log_n2 ? (__brev(row) >> (32 - log_n2)) : 0u) << pre_shift) + h;
+        const fe r = scale ? fe_mul_tw(v, s) : v;
 #if NTT_STREAM_B_STORE
-        fe_store_stream(dst + (k2 * k_stride + t), scale ? fe_mul_tw(v, s) : v);
+        fe_store_stream(dst + (k2 * k_stride + t), r);
 #else
-        dst[k2 * k_stride + t] = scale ? fe_mul_tw(v, s) : v;            // uniform base + 32-bit lane offset (at most 2^24 points)
+        dst[k2 * k_stride + t] = r;                                      // uniform base + 32-bit lane offset (at most 2^24 points)
 #endif
+        if (dst_tm != nullptr) {                                         // coefficient m = m1 * n2 + m2 of the natural order, tile-major (NttArgs)
+            const uint32_t m = k0 + t + k2 * k_stride, m2 = m & ((1u << log_cols) - 1u), m1 = m >> log_cols;
+            dst_tm[((((m2 >> 2) << log_rows) + m1) << 2) + (m2 & 3u)] = r;      // read next by every coset of the extension: no streaming hint
+        }
     }
 };
 
@@ -175,6 +188,19 @@ extern "C" __attribute__((visibility("default"))) int dst_lab_stamps(unsigned lo
         for (int k_ = 0; k_ < (nst); k_++) o_[k_] = (st)[k_]; } } while (0)
 #else
 #define NTT_LAB_FLUSH(pass, it, st, nst) ((void)0)
+#endif
+// One-sided lazy butterflies in the coset DIT of a first pass (ntt_lds.h LAZY, fe_addsub_lazy).  The invariant: every sum and difference of a
+// DIT round is u +- v * w, and v * w leaves fe_mul_tw canonical; so u may be ANY 128-bit value, one wrap by 2^128 -> C128 keeps the sum below
+// 2^128, fe_sub is right as it is, and the next round's fe_mul_tw takes what comes.  The lazy values end in the read-out of ntt_pass_a, which
+// multiplies EVERY element by its four-step twiddle (fe_mul / fe_mul_tw: any 128-bit operand) and so stores canonical values; nothing else
+// reads the tile.  The register pre-stage's own fe_add / fe_sub, the pre-scale + DIF mode and every second pass (stores without a
+// multiplication behind it, and both operands of its sums are sums) keep the canonical form.  -DNTT_DIT_LAZY=0: canonical rounds (A/B).
+#ifndef NTT_DIT_LAZY
+#define NTT_DIT_LAZY 1
+#endif
+// -DNTT_COEFF_TILE_MAJOR=0: no copy of the trace coefficients in tile order (NttArgs::src_tile_major), the extension reads `polys` row-major (A/B)
+#ifndef NTT_COEFF_TILE_MAJOR
+#define NTT_COEFF_TILE_MAJOR 1
 #endif
 extern __shared__ __attribute__((aligned(16))) unsigned char ntt_smem[];
 
@@ -235,8 +261,12 @@ __global__ void __launch_bounds__(THREADS, WPE) ntt_pass_a(NttArgs a, const fe* 
     };
 #define NTT_FETCH_A1(e, var) if constexpr ((e) < EPT) { uint32_t idx = lane + (e) * THREADS; idx = idx < count ? idx : 0u; \
         if constexpr (PRE != 0) { const uint32_t row_ = idx >> log_t; const fe x0_ = src[NTT_LAB_SRC(row_, NTT_COL_A(idx), (row_ << a.log_n2) + NTT_COL_A(idx))], x1_ = src[NTT_LAB_SRC(row_ + 512u, NTT_COL_A(idx), ((row_ + n1) << a.log_n2) + NTT_COL_A(idx))]; var = pre_stage_a(x0_, x1_, row_); } \
-        else var = src[NTT_LAB_SRC(idx >> log_t, NTT_COL_A(idx), ((idx >> log_t) << a.log_n2) + NTT_COL_A(idx))]; }
-#define NTT_FETCH_A(tile) { const fe* __restrict__ src = src0 + (tile) * T; NTT_EACH(NTT_FETCH_A1) }
+        else var = src[NTT_LAB_SRC(idx >> log_t, NTT_COL_A(idx), ((idx >> log_t) << src_row_shift) + NTT_COL_A(idx))]; }
+    // tile-major coefficients (NttArgs::src_tile_major): the tile is the block at tile * count and a row is T elements long -- the lane index
+    // with its column rotated; row-major: the tile's first column, rows n2 apart
+#define NTT_FETCH_A(tile) { const fe* __restrict__ src = src0 + (src_tm ? (size_t)(tile) * count : (size_t)(tile) * T); NTT_EACH(NTT_FETCH_A1) }
+    const bool src_tm = (PRE || (LOG_T != 0 && LOG_T != 2)) ? false : a.src_tile_major != 0;
+    const uint32_t src_row_shift = src_tm ? log_t : a.log_n2;
     const tw4_t* __restrict__ tw4 = a.tw4 + (size_t)jl * a.tw4_coset_stride;
     const uint32_t tile0 = group * a.tiles_per_block;
     uint32_t lane = threadIdx.x;
@@ -260,10 +290,10 @@ __global__ void __launch_bounds__(THREADS, WPE) ntt_pass_a(NttArgs a, const fe* 
         NTT_STAMP(st, 12);
         if (PREFETCH && it + 1 < a.tiles_per_block) NTT_FETCH_A(tile + 1)
         if constexpr (LOG_LEN != 0) {
-            if (a.dit) lds_ntt_dit_fixed<THREADS, LOG_LEN, LOG_T>(L, TW, a.dit_last ? a.dit_last + (size_t)((jg << PRE) + hh) * (n1 / 2) : nullptr, NttKeepInLds(), st);
+            if (a.dit) lds_ntt_dit_fixed<THREADS, LOG_LEN, LOG_T, NttKeepInLds, NTT_DIT_LAZY != 0>(L, TW, a.dit_last ? a.dit_last + (size_t)((jg << PRE) + hh) * (n1 / 2) : nullptr, NttKeepInLds(), st);
             else lds_ntt_dif_fixed<THREADS, LOG_LEN, LOG_T>(L, TW, NttKeepInLds(), st);
         } else {
-            if (a.dit) lds_ntt_dit<THREADS>(L, TW, log_n1, log_t, 1u, log_n1 + 1u, a.dit_last ? a.dit_last + (size_t)((jg << PRE) + hh) * (n1 / 2) : nullptr);
+            if (a.dit) lds_ntt_dit<THREADS, NttKeepInLds, NTT_DIT_LAZY != 0>(L, TW, log_n1, log_t, 1u, log_n1 + 1u, a.dit_last ? a.dit_last + (size_t)((jg << PRE) + hh) * (n1 / 2) : nullptr);
             else lds_ntt_dif<THREADS>(L, TW, log_n1, log_t, 1u, log_n1 + 1u);
         }
         // read-out in batches of RB elements per lane: the twiddle loads of a batch are in flight together (the 512-lane instance also
@@ -375,7 +405,8 @@ __global__ void __launch_bounds__(THREADS, WPE) ntt_pass_b(NttArgs a, const fe* 
         __syncthreads();
         NTT_STAMP(st, 12);
         if (PREFETCH && it + 1 < a.tiles_per_block) NTT_FETCH_B(tile0 + it + 1)
-        const OutB out{dst + k1_0, (uint32_t)a.dst_k_stride, log_n2, a.has_scale != 0, a.scale, (uint32_t)PRE, hh};
+        const OutB out{dst + k1_0, (uint32_t)a.dst_k_stride, log_n2, a.has_scale != 0, a.scale, (uint32_t)PRE, hh,
+                       (PRE || a.dst_tm == nullptr) ? nullptr : a.dst_tm + (size_t)col * a.dst_col_stride, k1_0, a.log_n1, a.log_n2};
         const fe_tw* Wuse = TW;
         if constexpr (LOG_LEN != 0) lds_ntt_dif_fixed<THREADS, LOG_LEN, LOG_T, OutB>(L, Wuse, out, st);
         else lds_ntt_dif<THREADS, OutB>(L, Wuse, log_n2, log_t, 1u, log_n2 + 1u, out);
@@ -682,6 +713,9 @@ static NttPlan ntt_plan_derive(uint32_t log_n, const NttSwitches& sw) {
     pl.pass[three ? 2 : 1] = three ? pass(NTT_LAST, pl.log_n3, pl.log_n1, cap, 0, false, false) : pass(NTT_LAST, pl.log_n2 - pre_b, pl.log_n1, cap, pre_b, reg_b, false);
     pl.count = three ? 3 : 2; pl.coset_slow = sw.coset_slow; pl.debug = sw.debug;
     pl.tile_major = ntt_tile_major(pl) && !sw.row_major;
+    // the coefficient copy in tile order: its writer is the interpolation's second pass, its reader the extension's first; neither may have a pre-stage
+    // (a pre-stage first pass reads the rows m and m + len of a column: two blocks, nothing gained -- profiles/ntt_tile_major.md on the same shape of store)
+    pl.coeff_tile_major = NTT_COEFF_TILE_MAJOR && pl.tile_major && !pl.first_lde.pre && !pl.pass[1].pre;
     return pl;
 }
 static int ntt_plan_set(dst_ctx* c) {                 // c->plan from the context's size and switches; every pass must have found its compiled instance
@@ -709,7 +743,9 @@ static void ntt_report_occupancy(const char* name, const NttInstance& I, size_t 
     fprintf(stderr, "[distaff] %s<%d,%d,%d,%d,%d,%d>: %d lanes, %zu B LDS -> %d workgroups per CU (%s)\n", name, I.threads, I.wpe, (int)I.prefetch, I.log_len, I.log_t, I.pre, I.threads, lds, nb, hipGetErrorString(e));
 }
 
-struct NttIo { const fe* src; size_t src_col_stride, src_coset_stride; fe* dst; size_t dst_col_stride, dst_coset_stride; };   // strides in elements
+// strides in elements.  src_tile_major / dst_tm: the coefficient copy in tile order (NttArgs) as the source of an extension's first pass / as the second
+// destination of an interpolation's last pass; the passes in between never see either
+struct NttIo { const fe* src; size_t src_col_stride, src_coset_stride; fe* dst; size_t dst_col_stride, dst_coset_stride; bool src_tile_major = false; fe* dst_tm = nullptr; };
 
 // One pass of a transform over `cosets` x `cols` arrays: the kernel arguments from the pass description, then the launch -- or, with `describe`, a
 // line about the launch instead of it (dst_ntt_describe).  Two-pass plans (n = n1 * n2): the first pass runs the n1-point transforms over the
@@ -722,7 +758,7 @@ static void ntt_run_pass(dst_ctx* c, const NttPass& P, const NttIo& io, size_t c
     const bool first = P.kind == NTT_FIRST, last = P.kind == NTT_LAST;
     const size_t n = c->n, n1 = (size_t)1 << p.log_n1, nrow = (size_t)1 << p.log_n2;
     const char* name = first ? "ntt_pass_a" : last ? "ntt_pass_b" : "ntt_pass_mid";
-    const double bytes = 16.0 * n * cols * ((first && lde) ? 1 + cosets : 2 * cosets);     // an extension reads its coefficients once for all cosets
+    double bytes = 16.0 * n * cols * ((first && lde) ? 1 + cosets : 2 * cosets);           // an extension reads its coefficients once for all cosets
     const uint32_t j0 = lde ? (uint32_t)c->j0 + skip : 0u, has_scale = (last && inverse) ? 1u : 0u;   // 1/n leaves with the last pass
     char line[384];
     if (P.reg) {
@@ -755,6 +791,10 @@ static void ntt_run_pass(dst_ctx* c, const NttPass& P, const NttIo& io, size_t c
     a.stage_tw = P.stage_tw[inverse]; a.tile = P.log_tile; a.pre = P.pre; a.pre_tw = P.pre_tw[inverse];
     a.log_n1 = p.log_n1; a.log_n2 = p.log_n2;
     a.tile_major = p.tile_major ? 1u : 0u;
+    // the plan keeps the copy (ntt_plan_derive: four-column tiles, no pre-stage in either pass concerned), or the caller has none to offer
+    a.src_tile_major = (first && lde && io.src_tile_major && p.coeff_tile_major) ? 1u : 0u;
+    a.dst_tm = (last && inverse && !lde && p.coeff_tile_major) ? io.dst_tm : nullptr;
+    if (a.dst_tm) bytes += 16.0 * n * cols;            // the second store
     size_t units = cosets;             // what the coset dimension of the block index runs over
     uint32_t tiles, batch_log = 0;     // tiles of an array; three-pass last pass: one batch of tile groups per middle frequency
     if (first) {
@@ -809,8 +849,8 @@ static void ntt_transform(dst_ctx* c, const NttIo& io, size_t cosets, size_t col
     fe* const stage[2] = {c->tmp, c->tmp2};
     for (uint32_t i = 0; i < p.count; i++) {
         NttIo s = io;
-        if (i > 0) { s.src = stage[i - 1]; s.src_col_stride = c->n * cosets; s.src_coset_stride = c->n; }
-        if (i + 1 < p.count) { s.dst = stage[i]; s.dst_col_stride = c->n * cosets; s.dst_coset_stride = c->n; }
+        if (i > 0) { s.src = stage[i - 1]; s.src_col_stride = c->n * cosets; s.src_coset_stride = c->n; s.src_tile_major = false; }
+        if (i + 1 < p.count) { s.dst = stage[i]; s.dst_col_stride = c->n * cosets; s.dst_coset_stride = c->n; s.dst_tm = nullptr; }
         ntt_run_pass(c, p.at(i, lde), s, cosets, cols, inverse, lde, skip, describe);
     }
 }
@@ -919,16 +959,16 @@ extern "C" __attribute__((visibility("default"))) int dst_ntt_describe(uint32_t 
 // how many (coset x column) size-n arrays fit in c->tmp
 static size_t tmp_capacity_arrays(const dst_ctx* c) { return c->Bc * c->tmp_regs; }
 
-void k_intt_columns(dst_ctx* c, const fe* src, size_t src_stride, fe* dst, size_t ncols) {
+void k_intt_columns(dst_ctx* c, const fe* src, size_t src_stride, fe* dst, size_t ncols, fe* dst_tm) {
     size_t cap = tmp_capacity_arrays(c);
     for (size_t done = 0; done < ncols;) {
         size_t cols = ncols - done < cap ? ncols - done : cap;
-        ntt_transform(c, {src + done * src_stride, src_stride, 0, dst + done * c->n, c->n, 0}, 1, cols, true, false);
+        ntt_transform(c, {src + done * src_stride, src_stride, 0, dst + done * c->n, c->n, 0, false, dst_tm ? dst_tm + done * c->n : nullptr}, 1, cols, true, false);
         done += cols;
     }
 }
 
-void k_lde_columns(dst_ctx* c, const fe* polys, fe* lde, size_t ncols) {
+void k_lde_columns(dst_ctx* c, const fe* polys, fe* lde, size_t ncols, const fe* polys_tm) {
     // coset 0 of the extension is the trace itself (T(w_n^k) for the interpolant T): when this rank owns it and the polynomials are
     // the interpolated trace, it is copied instead of transformed (1/B of the extension work)
     const bool of_trace = polys >= c->polys && polys < c->polys + c->W * c->n;          // a group of the interpolated trace registers
@@ -942,7 +982,8 @@ void k_lde_columns(dst_ctx* c, const fe* polys, fe* lde, size_t ncols) {
         const size_t cols = ncols - done < bcols ? ncols - done : bcols;
         for (size_t s = skip; s < c->Bc;) {
             const size_t cc = c->Bc - s < bcos ? c->Bc - s : bcos;
-            ntt_transform(c, {polys + done * c->n, c->n, 0, lde + done * c->Bc * c->n + s * c->n, c->Bc * c->n, c->n}, cc, cols, false, true, (uint32_t)s);
+            const bool tm = polys_tm != nullptr && c->plan.coeff_tile_major;
+            ntt_transform(c, {(tm ? polys_tm : polys) + done * c->n, c->n, 0, lde + done * c->Bc * c->n + s * c->n, c->Bc * c->n, c->n, tm}, cc, cols, false, true, (uint32_t)s);
             s += cc;
         }
         done += cols;

@@ -179,7 +179,15 @@ __device__ __forceinline__ void lds_ntt_dif_fixed(fe* L, const fe_tw* W, const O
 // B/2 - 1 (len - 1 entries for the workgroup's coset).  Two stages per LDS round trip, as in lds_ntt_dif.
 // `Wlast` != nullptr: the len/2 twiddles of the LAST stage (half of the coset's table) are not in LDS but read from this global array
 // (contiguous per coset, L2-resident): tile + the other len/2 - 1 pairs then fit the 80 KiB that let two workgroups share a CU.
-template <int THREADS, class Out>
+// LAZY (compile-time switch): every sum / difference of the butterflies is u +- v * w with v * w fresh out of fe_mul_tw, i.e. canonical, so
+// the one-sided lazy form (fe_addsub_lazy, fe.h) keeps every value below 2^128 whatever u is, and the next stage's fe_mul_tw takes any
+// 128-bit operand.  The tile the rounds leave behind is then NOT canonical: LAZY is for callers whose consumer multiplies every element
+// (the first pass's read-out by the four-step twiddle).  Off: the canonical butterflies.
+template <bool LAZY>
+__device__ __forceinline__ void dit_addsub(const fe& u, const fe& r, fe& sum, fe& dif) {
+    if constexpr (LAZY) fe_addsub_lazy(u, r, sum, dif); else fe_addsub(u, r, sum, dif);
+}
+template <int THREADS, class Out, bool LAZY = false>
 __device__ __forceinline__ void lds_dit_round(fe* L, const fe_tw* W, uint32_t log_len, uint32_t log_t, uint32_t s, const fe_tw* __restrict__ Wlast, const Out& out, uint32_t lane) {
     const uint32_t T = 1u << log_t;
     const uint32_t B = 1u << s, half = B >> 1;                     // first stage merges blocks of size B / 2 into B, second B into 2B
@@ -194,14 +202,14 @@ __device__ __forceinline__ void lds_dit_round(fe* L, const fe_tw* W, uint32_t lo
         const fe_tw tb = W[half - 1 + k];
         const fe x0 = *p0, x1 = fe_mul_tw(*p1, tb), x2 = *p2, x3 = fe_mul_tw(*p3, tb);
         fe a0, a1, b2, b3;
-        fe_addsub(x0, x1, a0, a1);
-        fe_addsub(x2, x3, b2, b3);
+        dit_addsub<LAZY>(x0, x1, a0, a1);
+        dit_addsub<LAZY>(x2, x3, b2, b3);
         const bool from_global = Wlast != nullptr && s + 1 == log_len;        // the second stage of this round is the last stage
         const fe_tw t2 = from_global ? Wlast[k] : W[B - 1 + k], t3 = from_global ? Wlast[k + half] : W[B - 1 + k + half];
         const fe a2 = fe_mul_tw(b2, t2), a3 = fe_mul_tw(b3, t3);
         fe y0, y1, y2, y3;
-        fe_addsub(a0, a2, y0, y2);
-        fe_addsub(a1, a3, y1, y3);
+        dit_addsub<LAZY>(a0, a2, y0, y2);
+        dit_addsub<LAZY>(a1, a3, y1, y3);
         if (fin) { out.put(base + k, t, y0, k0); out.put(base + k + B, t, y2, k2); out.put(base + k + half, t, y1, k1); out.put(base + k + B + half, t, y3, k3); }
         else { *p0 = y0; *p2 = y2; *p1 = y1; *p3 = y3; }
     }
@@ -209,7 +217,7 @@ __device__ __forceinline__ void lds_dit_round(fe* L, const fe_tw* W, uint32_t lo
     const bool own_rows = lds_wave_local() && (8u << s) <= ((64u >> log_t) << 2) && s + 3 <= log_len;
     if (!fin) { if (own_rows) lds_wave_sync(); else __syncthreads(); }
 }
-template <int THREADS, class Out>
+template <int THREADS, class Out, bool LAZY = false>
 __device__ __forceinline__ void lds_dit_tail(fe* L, const fe_tw* W, uint32_t log_len, uint32_t log_t, const fe_tw* __restrict__ Wlast, const Out& out, uint32_t lane) {   // last single stage: blocks of len / 2 into len
     const uint32_t T = 1u << log_t;
     const uint32_t half = 1u << (log_len - 1);
@@ -220,22 +228,22 @@ __device__ __forceinline__ void lds_dit_tail(fe* L, const fe_tw* W, uint32_t log
         fe* p0 = L + lds_slot(k, t, log_t); fe* p1 = L + lds_slot(k + half, t, log_t);
         const fe u = *p0, v = fe_mul_tw(*p1, Wlast != nullptr ? Wlast[k] : W[half - 1 + k]);
         fe sum, dif;
-        fe_addsub(u, v, sum, dif);
+        dit_addsub<LAZY>(u, v, sum, dif);
         if (Out::active) { out.put(k, t, sum, k0); out.put(k + half, t, dif, k1); }
         else { *p0 = sum; *p1 = dif; }
     }
     if (!Out::active) __syncthreads();
 }
-template <int THREADS, class Out = NttKeepInLds>
+template <int THREADS, class Out = NttKeepInLds, bool LAZY = false>
 __device__ __forceinline__ void lds_ntt_dit(fe* L, const fe_tw* W, uint32_t log_len, uint32_t log_t, uint32_t s_from, uint32_t s_to, const fe_tw* __restrict__ Wlast = nullptr, const Out& out = Out()) {
     uint32_t s = s_from;                             // stages [s_from, s_to), s_from odd
     const uint32_t lane = lds_opaque_lane();
-    for (; s + 1 <= log_len && s < s_to; s += 2) lds_dit_round<THREADS, Out>(L, W, log_len, log_t, s, Wlast, out, lane);
-    if (s == log_len && s < s_to) lds_dit_tail<THREADS, Out>(L, W, log_len, log_t, Wlast, out, lane);
+    for (; s + 1 <= log_len && s < s_to; s += 2) lds_dit_round<THREADS, Out, LAZY>(L, W, log_len, log_t, s, Wlast, out, lane);
+    if (s == log_len && s < s_to) lds_dit_tail<THREADS, Out, LAZY>(L, W, log_len, log_t, Wlast, out, lane);
 }
-template <int THREADS, int LOG_LEN, int LOG_T, class Out = NttKeepInLds>
+template <int THREADS, int LOG_LEN, int LOG_T, class Out = NttKeepInLds, bool LAZY = false>
 __device__ __forceinline__ void lds_ntt_dit_fixed(fe* L, const fe_tw* W, const fe_tw* __restrict__ Wlast = nullptr, const Out& out = Out(), unsigned long long* stamps = nullptr) {
     const uint32_t lane = lds_opaque_lane();
-    static_for<0, LOG_LEN / 2>([&](auto r_) { constexpr uint32_t s = 1u + 2u * decltype(r_)::value; lds_dit_round<THREADS, Out>(L, W, (uint32_t)LOG_LEN, (uint32_t)LOG_T, s, Wlast, out, lane); (void)stamps; NTT_STAMP(stamps, decltype(r_)::value); });
-    if constexpr (LOG_LEN & 1) lds_dit_tail<THREADS, Out>(L, W, (uint32_t)LOG_LEN, (uint32_t)LOG_T, Wlast, out, lane);
+    static_for<0, LOG_LEN / 2>([&](auto r_) { constexpr uint32_t s = 1u + 2u * decltype(r_)::value; lds_dit_round<THREADS, Out, LAZY>(L, W, (uint32_t)LOG_LEN, (uint32_t)LOG_T, s, Wlast, out, lane); (void)stamps; NTT_STAMP(stamps, decltype(r_)::value); });
+    if constexpr (LOG_LEN & 1) lds_dit_tail<THREADS, Out, LAZY>(L, W, (uint32_t)LOG_LEN, (uint32_t)LOG_T, Wlast, out, lane);
 }

@@ -353,11 +353,15 @@ void* orc_prover_new(const u128* cols, size_t W, size_t n, size_t ctx, size_t lp
 }
 void orc_prover_free(void* hv) { auto h = (ProverHandle*)hv; delete h->p; delete h; }
 
-// step: 1..9 as in prover.rs; `override`/`nover`: caller-supplied challenges for steps 3 (344 draws) and 6 (517 draws incl. z)
-int orc_prover_step(void* hv, int step, const u128* over, size_t nover) {
+// step: 1..9 as in prover.rs; `override`/`nover`: caller-supplied challenges for steps 3 (344 draws) and 6 (517 draws incl. z);
+// `positions`/`npos` (step 8 only, NULL = draw them from the seed): caller-supplied query positions, distinct and below N, which
+// step 9 then opens; seeds and proof-of-work nonce stay as they are.  A non-NULL `positions` with npos == 0 means "no position".
+int orc_prover_step(void* hv, int step, const u128* over, size_t nover, const uint64_t* positions, size_t npos) {
     auto h = (ProverHandle*)hv;
     try {
         vec ov; if (over) ov.assign(over, over + nover);
+        if (positions && step != 8) throw std::runtime_error("query positions can be supplied to step 8 only");
+        std::vector<size_t> pos; if (positions) pos.assign(positions, positions + npos);
         switch (step) {
             case 1: h->p->step1_extend(); break;
             case 2: h->p->step2_trace_tree(); break;
@@ -366,7 +370,7 @@ int orc_prover_step(void* hv, int step, const u128* over, size_t nover) {
             case 5: h->p->step5_constraint_tree(); break;
             case 6: h->p->step6_deep_composition(over ? &ov : nullptr); break;
             case 7: h->p->step7_fri(); break;
-            case 8: h->p->step8_queries(); break;
+            case 8: h->p->step8_queries(positions ? &pos : nullptr); break;
             case 9: h->proof = h->p->step9_build_proof(); h->proof_bytes = serialize_proof(h->proof); h->has_proof = true; break;
             default: return -1;
         }
@@ -482,10 +486,14 @@ long orc_chk_constraints(size_t trace_length, size_t ctx, size_t lp, size_t st, 
 }
 void orc_poly_eval_par(const u128* p, size_t n, const u128* x, u128* out) { *out = chk_poly_eval(p, n, *x); }
 
-int orc_verify(const uint8_t* proof, size_t len, const uint8_t* program_hash, const u128* inputs, size_t nin, const u128* outputs, size_t nout, char* err, size_t errcap) {
+// `positions`/`npos` (NULL = the positions the proof's seed draws): verify the openings at these positions instead; the proof-of-work
+// check and the draw of `num_queries` positions are skipped, every other check of the verifier runs
+int orc_verify(const uint8_t* proof, size_t len, const uint8_t* program_hash, const u128* inputs, size_t nin, const u128* outputs, size_t nout, char* err, size_t errcap,
+               const uint64_t* positions, size_t npos) {
     try {
         StarkProof p = deserialize_proof(proof, len);
-        VerifyResult r = verify(program_hash, vec(inputs, inputs + nin), vec(outputs, outputs + nout), p);
+        std::vector<size_t> pos; if (positions) pos.assign(positions, positions + npos);
+        VerifyResult r = verify(program_hash, vec(inputs, inputs + nin), vec(outputs, outputs + nout), p, positions ? &pos : nullptr);
         if (err && errcap) snprintf(err, errcap, "%s", r.error.c_str());
         return r.ok ? 1 : 0;
     } catch (const std::exception& e) { if (err && errcap) snprintf(err, errcap, "%s", e.what()); return fail(e); }

@@ -299,13 +299,22 @@ struct Prover {
         eval_fft_twiddles(composed_evaluations.data(), N, lde_twiddles, true);
     }
     void step7_fri() { fri = fri_reduce(composed_evaluations, lde_domain); }       // prover.rs:111
-    void step8_queries() {                                         // prover.rs:120-133
+    // `positions_override`: query positions supplied by the caller (distinct, each below N) instead of the draw from the seed; the
+    // seeds and the proof-of-work nonce are computed as always, so step 9 opens the same commitments at other places
+    void step8_queries(const std::vector<size_t>* positions_override = nullptr) {   // prover.rs:120-133
         std::vector<uint8_t> roots;
         for (auto& t : fri.trees) roots.insert(roots.end(), t.root().begin(), t.root().end());
         query_seed0 = hash_bytes(roots.data(), roots.size());
         auto pw = find_pow_nonce(query_seed0, options);
         query_seed1 = pw.first; pow_nonce = pw.second;
-        positions = compute_query_positions(query_seed1, N, options);
+        if (positions_override) {
+            std::set<size_t> seen;
+            for (size_t p : *positions_override) {
+                if (p >= N) throw std::runtime_error("query position is outside the evaluation domain");
+                if (!seen.insert(p).second) throw std::runtime_error("query positions repeat");
+            }
+            positions = *positions_override;
+        } else positions = compute_query_positions(query_seed1, N, options);
     }
     StarkProof step9_build_proof() {                               // prover.rs:143-165
         StarkProof p;

@@ -449,6 +449,14 @@ GET = {"polys": 0, "registers": 1, "trace_leaves": 2, "trace_nodes": 3, "constra
        "roots": 26, "fri_roots": 27}
 
 
+def _positions(positions):
+    """caller-supplied query positions -> (uint64 array or None, count); an empty list still has an address (NULL means "draw them")"""
+    if positions is None:
+        return None, 0
+    pos = np.asarray(list(positions), dtype=np.uint64).reshape(-1)
+    return np.concatenate([pos, np.zeros(1, dtype=np.uint64)]), pos.size
+
+
 class Prover:
     """Step-wise CPU prover keeping every intermediate (oracle/prover.hpp)."""
 
@@ -476,12 +484,15 @@ class Prover:
         if getattr(self, "_h", None):
             lib().orc_prover_free(ctypes.c_void_p(self._h)); self._h = None
 
-    def step(self, k, override=None):
-        if override is not None:
-            ov = _c(override)
-            r = lib().orc_prover_step(ctypes.c_void_p(self._h), k, _p(ov), ctypes.c_size_t(ov.shape[0]))
-        else:
-            r = lib().orc_prover_step(ctypes.c_void_p(self._h), k, None, ctypes.c_size_t(0))
+    def step(self, k, override=None, positions=None):
+        """Run prover step ``k`` (1..9).  ``override``: caller-supplied challenges for steps 3 and 6.  ``positions`` (step 8 only):
+        a list of distinct query positions below N that replaces the draw from the seed -- seeds and proof-of-work nonce are computed
+        as always, and ``step(9)`` then builds the proof at exactly these positions, in this order.  An empty list means no position;
+        ``None`` draws them as the prover does."""
+        ov = _c(override) if override is not None else None
+        pos, count = _positions(positions)
+        r = lib().orc_prover_step(ctypes.c_void_p(self._h), k, _p(ov) if ov is not None else None, ctypes.c_size_t(ov.shape[0] if ov is not None else 0),
+                                  _p(pos) if pos is not None else None, ctypes.c_size_t(count))
         if r != 0:
             raise RuntimeError(last_error())
 
@@ -515,13 +526,19 @@ class Prover:
         return [int(x) for x in np.frombuffer(self.get_bytes(what), dtype=np.uint64)]
 
 
-def verify(proof_bytes, program_hash, inputs, outputs):
-    """Returns (ok, error_string) -- error strings are the reference's (verifier.rs)."""
+def verify(proof_bytes, program_hash, inputs, outputs, positions=None):
+    """Returns (ok, error_string) -- error strings are the reference's (verifier.rs).
+
+    ``positions``: verify the openings at these positions of the LDE domain instead of the ones the proof's seed draws (for proofs built
+    with ``Prover.step(8, positions=...)``).  Both Merkle batch proofs, the constraints at z, the DEEP composition and the FRI layers with
+    the remainder are checked as always; the proof-of-work check and the draw of ``num_queries`` positions are skipped."""
     i = to_arr(list(inputs)) if len(inputs) else np.zeros((0, 2), dtype=np.uint64)
     o = to_arr(list(outputs)) if len(outputs) else np.zeros((0, 2), dtype=np.uint64)
     err = ctypes.create_string_buffer(512)
+    pos, count = _positions(positions)
     r = lib().orc_verify(bytes(proof_bytes), ctypes.c_size_t(len(proof_bytes)), bytes(program_hash), _p(i), ctypes.c_size_t(len(inputs)),
-                         _p(o), ctypes.c_size_t(len(outputs)), err, ctypes.c_size_t(512))
+                         _p(o), ctypes.c_size_t(len(outputs)), err, ctypes.c_size_t(512),
+                         _p(pos) if pos is not None else None, ctypes.c_size_t(count))
     return r == 1, err.value.decode()
 
 

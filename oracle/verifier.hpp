@@ -30,7 +30,8 @@ static inline VerifyResult fri_verify_remainder(const vec& remainder, size_t max
 
 static inline VerifyResult fri_verify(const FriProof& proof, const vec& evaluations_in, const std::vector<size_t>& positions_in,
                                       size_t max_degree, const ProofOptions& options) {                                       // fri/verifier.rs:11
-    size_t domain_size = ((size_t)1 << proof.layers[0].depth) * 4;
+    // a domain of at most 256 points is its own remainder: the proof then has no layer to take the size from
+    size_t domain_size = proof.layers.empty() ? proof.rem_values.size() : ((size_t)1 << proof.layers[0].depth) * 4;
     u128 domain_root = get_root_of_unity(domain_size);
     u128 quartic_roots[4] = {1, exp(domain_root, (u128)(domain_size / 4)), exp(domain_root, (u128)(domain_size / 2)), exp(domain_root, (u128)(domain_size * 3 / 4))};
     size_t max_degree_plus_1 = max_degree + 1;
@@ -69,7 +70,11 @@ static inline VerifyResult fri_verify(const FriProof& proof, const vec& evaluati
     return fri_verify_remainder(proof.rem_values, max_degree_plus_1, domain_root, options.extension_factor);
 }
 
-static inline VerifyResult verify(const uint8_t program_hash[32], const vec& inputs, const vec& outputs, const StarkProof& proof) {   // verifier.rs:11
+// `positions_override`: verify the openings at these positions of the LDE domain instead of the ones the proof's seed draws.  Every
+// other check runs as always (both Merkle batch proofs, the constraints at z, the DEEP composition, the FRI layers and remainder); the
+// proof-of-work check and the draw of `num_queries` positions are skipped, since the positions no longer come from the seed.
+static inline VerifyResult verify(const uint8_t program_hash[32], const vec& inputs, const vec& outputs, const StarkProof& proof,
+                                  const std::vector<size_t>* positions_override = nullptr) {                                          // verifier.rs:11
     const ProofOptions& options = proof.options;
     // 1 -- proof of work and query positions
     std::vector<uint8_t> fri_roots;
@@ -77,8 +82,8 @@ static inline VerifyResult verify(const uint8_t program_hash[32], const vec& inp
     fri_roots.insert(fri_roots.end(), proof.degree_proof.rem_root.begin(), proof.degree_proof.rem_root.end());
     hash32 seed = hash_bytes(fri_roots.data(), fri_roots.size());
     hash32 seed1 = pow_hash(seed, proof.pow_nonce);                 // proof_of_work.rs:34
-    if (!pow_check(seed1, options.grinding_factor)) return {false, "seed proof-of-work verification failed"};
-    std::vector<size_t> t_positions = compute_query_positions(seed1, proof.domain_size(), options);
+    if (!positions_override && !pow_check(seed1, options.grinding_factor)) return {false, "seed proof-of-work verification failed"};
+    std::vector<size_t> t_positions = positions_override ? *positions_override : compute_query_positions(seed1, proof.domain_size(), options);
     std::vector<size_t> c_positions = map_trace_to_constraint_positions(t_positions);
     // 2 -- minimum operation count
     if (proof.op_count < MIN_TRACE_LENGTH) return {false, "Verification of minimum operation count failed"};

@@ -523,3 +523,9 @@ int k_rescue_path_roots(hipStream_t stream, const fe* paths, uint32_t n, const u
 // multiproofs (host/multiproof_plan.h): one level of `count` jobs over the pool, pool[out] = digest(pool[left], pool[right]) with the three pool
 // indices of job j at jobs[3 j ..) (device); *bad = 1 for an element >= p in a pool node below `inputs` (the leaves and the supplied nodes)
 int k_rescue_multiproof_level(hipStream_t stream, fe* pool, const uint32_t* jobs, size_t count, uint32_t inputs, uint32_t* bad);
+// audits: ONE launch over every parent of every level; *first_bad (device, set to all ones by the caller) receives by atomicMin the first parent
+// that is not the digest of its children -- dense: its heap position in [1, leaves); sparse: (level << 32) | index within the level, for the
+// `count` >= 1 parents at the flat positions first + [0, count) = every level above the leaf level; levels / empties as k_rescue_stree_open
+int k_rescue_tree_audit(hipStream_t stream, const fe* nodes, size_t leaves, unsigned long long* first_bad);
+int k_rescue_stree_audit(hipStream_t stream, const fe* nodes, const uint64_t* pref, const uint64_t* levels, const fe* empties, uint32_t depth, size_t first, size_t count,
+                         unsigned long long* first_bad);

@@ -6,6 +6,7 @@
 #include "../ctx.h"
 #include "../host_rescue.h"
 #include "tree_sequence.h"
+#include "tree_blob.h"
 
 struct dst_rtree {
     int device = -1;                      // < 0: the nodes live in `host`
@@ -404,4 +405,85 @@ int dst_rtree_apply(dst_rtree* t, const uint64_t* indices, const uint8_t* leaves
         if (r != DST_OK) { t->broken = true; t->err += "; the sequence did not complete, the tree is unusable"; }
         return r;
     } catch (const std::bad_alloc&) { return rt_fail(t, DST_ERR_HIP, "out of host memory"); }      // thrown before anything was queued
+}
+
+// ---- save, load, audit (tree_blob.h has the saved form and the parser of untrusted bytes) ------------------------------------------------------
+// the saved tree: the header and the nodes of heap positions 1 and up, as dst_rtree_read_nodes returns them
+int dst_rtree_save(const dst_rtree* t, uint8_t* out, size_t cap, size_t* len) {
+    if (int r = rt_enter(t)) return r;
+    if (!len) return rt_fail(t, DST_ERR_ARG, "null pointer");
+    const uint64_t nodes = ((uint64_t)2 << t->log_leaves) - 1;
+    *len = (size_t)tblob_dense_bytes(t->log_leaves);
+    if (!out) return DST_OK;                                                                // size query
+    if (cap < *len) return rt_fail(t, DST_ERR_ARG, "the buffer is smaller than the saved tree");
+    tblob_put_header(out, TBLOB_DENSE, t->log_leaves, nullptr, (uint64_t)1 << t->log_leaves, nodes);
+    return dst_rtree_read_nodes(t, 1, nodes, out + TBLOB_HEADER);
+}
+// the first parent in [1, leaves) that is not the digest of its children: *key = its heap position, all ones when there is none
+static int rtree_audit_run(const dst_rtree* t, uint64_t* key, double* ms) {
+    const size_t n = (size_t)1 << t->log_leaves;
+    *key = ~(uint64_t)0; *ms = 0;
+    if (t->device < 0) {
+        const size_t chunk = 1024;                                                          // ascending positions: the first chunk with a bad parent ends the walk
+        std::vector<u128> d(2 * std::min(chunk, n));
+        for (size_t p = 1; p < n; p += chunk) {
+            const size_t m = std::min(chunk, n - p);
+            rescue_digest_many_host(t->host.data() + 4 * p, m, d.data());                   // the children of p are the nodes 2p, 2p + 1: four elements at 4p
+            for (size_t i = 0; i < m; i++) if (memcmp(&d[2 * i], &t->host[2 * (p + i)], 32) != 0) { *key = p + i; return DST_OK; }
+        }
+        return DST_OK;
+    }
+    if (int r = rtree_stage(t, 8)) return r;
+    unsigned long long* d_key = reinterpret_cast<unsigned long long*>(t->stage);
+    RT_HIP(t->err, hipMemsetAsync(d_key, 0xFF, 8, t->stream));
+    RT_HIP(t->err, hipEventRecord(t->ev[0], t->stream));
+    if (k_rescue_tree_audit(t->stream, t->dev, n, d_key)) return rt_fail(t, DST_ERR_HIP, "rescue_tree_audit_kernel: launch failed");
+    RT_HIP(t->err, hipEventRecord(t->ev[1], t->stream));
+    RT_HIP(t->err, hipMemcpyAsync(key, d_key, 8, hipMemcpyDeviceToHost, t->stream));
+    RT_HIP(t->err, hipStreamSynchronize(t->stream));
+    return rtree_elapsed(t, ms);
+}
+// the tree is only read: an error here leaves it usable
+int dst_rtree_audit(const dst_rtree* t, int64_t* first_bad, double* device_ms) {
+    if (int r = rt_enter(t)) return r;
+    if (!first_bad) return rt_fail(t, DST_ERR_ARG, "null pointer");
+    uint64_t key = 0;
+    double ms = 0;
+    try {
+        if (int r = rtree_audit_run(t, &key, &ms)) return r;
+    } catch (const std::bad_alloc&) { return rt_fail(t, DST_ERR_HIP, "out of host memory"); }
+    *first_bad = key == ~(uint64_t)0 ? -1 : (int64_t)key;
+    if (device_ms) *device_ms = ms;
+    return DST_OK;
+}
+// a tree from its saved form: nothing is hashed -- one allocation, one upload -- unless the caller asks for the audit
+int dst_rtree_load(int device, const uint8_t* blob, size_t len, uint32_t audit, dst_rtree** out) {
+    if (out) *out = nullptr;
+    if (!blob || !out) { g_rtree_error = "null pointer"; return DST_ERR_ARG; }
+    tblob_view v;
+    if (const char* why = tblob_parse(blob, len, TBLOB_DENSE, v)) { g_rtree_error = why; return DST_ERR_ARG; }
+    std::unique_ptr<dst_rtree> t(new (std::nothrow) dst_rtree);
+    if (!t) { g_rtree_error = "out of host memory"; return DST_ERR_HIP; }
+    t->device = device < 0 ? -1 : device; t->log_leaves = v.depth;
+    const size_t n = (size_t)1 << v.depth;
+    auto upload = [&]() -> int {
+        if (int r = rtree_stage(t.get(), 0)) return r;
+        RT_HIP(t->err, hipMalloc((void**)&t->dev, 64 * n));
+        RT_HIP(t->err, hipMemsetAsync(t->dev, 0, 32, t->stream));                           // nodes[0] is not part of the tree
+        RT_HIP(t->err, hipMemcpyAsync(t->dev + 2, v.values, 32 * (2 * n - 1), hipMemcpyHostToDevice, t->stream));
+        RT_HIP(t->err, hipStreamSynchronize(t->stream));
+        return DST_OK;
+    };
+    try {
+        if (device >= 0) { if (int r = upload()) { g_rtree_error = t->err; return r; } }
+        else { t->host.assign(4 * n, 0); memcpy(t->host.data() + 2, v.values, 32 * (2 * n - 1)); }
+        if (audit) {
+            uint64_t key = 0;
+            double ms = 0;
+            if (int r = rtree_audit_run(t.get(), &key, &ms)) { g_rtree_error = t->err; return r; }
+            if (key != ~(uint64_t)0) { g_rtree_error = "audit: node " + std::to_string(key) + " is not the digest of its children"; return DST_ERR_ARG; }
+        }
+    } catch (const std::bad_alloc&) { g_rtree_error = "out of host memory"; return DST_ERR_HIP; }
+    *out = t.release();
+    return DST_OK;
 }

@@ -366,3 +366,135 @@ int dst_stree_apply(dst_stree* t, const uint64_t* indices, const uint8_t* leaves
         return DST_OK;
     } catch (const std::bad_alloc&) { return st_fail(t, DST_ERR_HIP, "out of host memory"); }
 }
+
+// ---- save, load, audit (tree_blob.h) --------------------------------------------------------------------------------------------------------------
+// the saved tree: the header, the level lengths, the prefixes and the nodes, all in the order of the flat positions (the leaf level first): copies
+int dst_stree_save(const dst_stree* t, uint8_t* out, size_t cap, size_t* len) {
+    if (int r = st_enter(t)) return r;
+    if (!len) return st_fail(t, DST_ERR_ARG, "null pointer");
+    const size_t total = t->shape.total(), D = t->depth;
+    *len = (size_t)tblob_sparse_bytes(t->depth, total);
+    if (!out) return DST_OK;                                                                // size query
+    if (cap < *len) return st_fail(t, DST_ERR_ARG, "the buffer is smaller than the saved tree");
+    tblob_put_header(out, TBLOB_SPARSE, t->depth, reinterpret_cast<const uint8_t*>(t->empties + 2 * D), t->shape.cnt[D], total);
+    uint8_t* at = out + TBLOB_HEADER;
+    for (size_t k = 0; k <= D; k++, at += 8) tblob_put_u64(at, t->shape.cnt[D - k]);
+    for (size_t j = 0; j < total; j++, at += 8) tblob_put_u64(at, t->shape.pref[j]);
+    if (total == 0) return DST_OK;
+    if (t->device < 0) { memcpy(at, t->host.data(), 32 * total); return DST_OK; }
+    RT_HIP(t->err, hipSetDevice(t->device));
+    RT_HIP(t->err, hipMemcpy(at, t->dev_nodes(), 32 * total, hipMemcpyDeviceToHost));
+    return DST_OK;
+}
+// the first stored parent, from the root down and by prefix within a level, that is not the digest of its children (a child that is not stored is
+// the E_l of its level): *key = (level << 32) | index within the level, all ones when there is none
+static int stree_audit_run(const dst_stree* t, uint64_t* key, double* ms) {
+    const stree_shape& sh = t->shape;
+    const size_t D = t->depth, first = sh.cnt[D], count = sh.total() - first;
+    *key = ~(uint64_t)0; *ms = 0;
+    if (count == 0) return DST_OK;                                                          // no keys, no parents
+    if (t->device < 0) {
+        const size_t chunk = 1024;
+        std::vector<u128> in(4 * chunk), d(2 * chunk);
+        for (size_t l = 0; l < D; l++) {
+            const size_t cstart = sh.start[l + 1];
+            const u128* e = t->empties + 2 * (l + 1);
+            for (size_t i = 0; i < sh.cnt[l]; i += chunk) {
+                const size_t m = std::min(chunk, sh.cnt[l] - i);
+                for (size_t g = 0; g < m; g++) {
+                    size_t left, right;
+                    stree_children(sh.pref.data() + cstart, sh.cnt[l + 1], sh.pref[sh.start[l] + i + g], left, right);
+                    memcpy(&in[4 * g], left != STREE_ABSENT ? &t->host[2 * (cstart + left)] : e, 32);
+                    memcpy(&in[4 * g + 2], right != STREE_ABSENT ? &t->host[2 * (cstart + right)] : e, 32);
+                }
+                rescue_digest_many_host(in.data(), m, d.data());
+                for (size_t g = 0; g < m; g++)
+                    if (memcmp(&d[2 * g], &t->host[2 * (sh.start[l] + i + g)], 32) != 0) { *key = ((uint64_t)l << 32) | (uint64_t)(i + g); return DST_OK; }
+            }
+        }
+        return DST_OK;
+    }
+    if (int r = rtree_stage(t, 8)) return r;
+    unsigned long long* d_key = reinterpret_cast<unsigned long long*>(t->stage);
+    RT_HIP(t->err, hipMemsetAsync(d_key, 0xFF, 8, t->stream));
+    RT_HIP(t->err, hipEventRecord(t->ev[0], t->stream));
+    if (k_rescue_stree_audit(t->stream, t->dev_nodes(), t->dev_pref(), t->dev_levels(), t->dev_empties(), t->depth, first, count, d_key))
+        return st_fail(t, DST_ERR_HIP, "rescue_stree_audit_kernel: launch failed");
+    RT_HIP(t->err, hipEventRecord(t->ev[1], t->stream));
+    RT_HIP(t->err, hipMemcpyAsync(key, d_key, 8, hipMemcpyDeviceToHost, t->stream));
+    RT_HIP(t->err, hipStreamSynchronize(t->stream));
+    return rtree_elapsed(t, ms);
+}
+// the tree is only read: an error here leaves it usable
+int dst_stree_audit(const dst_stree* t, int32_t* bad_level, uint64_t* bad_prefix, double* device_ms) {
+    if (int r = st_enter(t)) return r;
+    if (!bad_level || !bad_prefix) return st_fail(t, DST_ERR_ARG, "null pointer");
+    uint64_t key = 0;
+    double ms = 0;
+    try {
+        if (int r = stree_audit_run(t, &key, &ms)) return r;
+    } catch (const std::bad_alloc&) { return st_fail(t, DST_ERR_HIP, "out of host memory"); }
+    const bool bad = key != ~(uint64_t)0;
+    *bad_level = bad ? (int32_t)(key >> 32) : -1;
+    *bad_prefix = bad ? t->shape.pref[t->shape.start[key >> 32] + (size_t)(key & 0xFFFFFFFFu)] : 0;
+    if (device_ms) *device_ms = ms;
+    return DST_OK;
+}
+// a tree from its saved form: the E_l come from the empty leaf as in dst_stree_create, nothing else is hashed -- a device tree is one allocation
+// and four copies into it, the nodes straight from the blob -- unless the caller asks for the audit
+int dst_stree_load(int device, const uint8_t* blob, size_t len, uint32_t audit, dst_stree** out) {
+    if (out) *out = nullptr;
+    if (!blob || !out) { g_stree_error = "null pointer"; return DST_ERR_ARG; }
+    tblob_view v;
+    if (const char* why = tblob_parse(blob, len, TBLOB_SPARSE, v)) { g_stree_error = why; return DST_ERR_ARG; }
+    std::unique_ptr<dst_stree> t(new (std::nothrow) dst_stree);
+    if (!t) { g_stree_error = "out of host memory"; return DST_ERR_HIP; }
+    const size_t D = v.depth, total = (size_t)v.nodes;
+    t->device = device < 0 ? -1 : device; t->depth = v.depth;
+    memcpy(t->empties + 2 * D, v.empty, 32);
+    for (size_t l = D; l-- > 0;) {                                                          // E_l = digest(E_{l+1}, E_{l+1})
+        const u128 in[4] = {t->empties[2 * l + 2], t->empties[2 * l + 3], t->empties[2 * l + 2], t->empties[2 * l + 3]};
+        rescue_digest_many_host(in, 1, t->empties + 2 * l);
+    }
+    uint64_t lv[128] = {0};
+    auto copies = [&]() -> int {                                                            // [nodes][empties][levels][prefixes], as stree_apply_device lays it out:
+        uint8_t* d = t->dev;                                                                // the nodes go up straight from the caller's blob, no second host image
+        if (total) RT_HIP(t->err, hipMemcpyAsync(d, v.values, 32 * total, hipMemcpyHostToDevice, t->stream));
+        RT_HIP(t->err, hipMemcpyAsync(d + 32 * total, t->empties, 2048, hipMemcpyHostToDevice, t->stream));
+        RT_HIP(t->err, hipMemcpyAsync(d + 32 * total + 2048, lv, 1024, hipMemcpyHostToDevice, t->stream));
+        if (total) RT_HIP(t->err, hipMemcpyAsync(d + 32 * total + 3072, t->shape.pref.data(), 8 * total, hipMemcpyHostToDevice, t->stream));
+        return DST_OK;
+    };
+    auto upload = [&]() -> int {
+        for (size_t l = 0; l <= D; l++) { lv[2 * l] = t->shape.start[l]; lv[2 * l + 1] = t->shape.cnt[l]; }
+        if (int r = rtree_stage(t.get(), 0)) return r;
+        RT_HIP(t->err, hipMalloc((void**)&t->dev, 40 * total + 3072));
+        const int r = copies();
+        const hipError_t e = hipStreamSynchronize(t->stream);                               // also after a failed copy: the sources are the caller's and this frame's
+        if (r != DST_OK) return r;
+        RT_HIP(t->err, e);
+        return DST_OK;
+    };
+    try {
+        stree_shape& sh = t->shape;
+        sh.depth = v.depth;
+        sh.pref.resize(total);
+        for (size_t j = 0; j < total; j++) sh.pref[j] = tblob_u64(v.prefixes + 8 * j);
+        size_t at = 0;
+        for (size_t k = 0; k <= D; k++) { sh.start[D - k] = at; sh.cnt[D - k] = (size_t)tblob_u64(v.counts + 8 * k); at += sh.cnt[D - k]; }
+        if (device >= 0) { if (int r = upload()) { g_stree_error = t->err; return r; } }
+        else { t->host.assign(2 * total, 0); if (total) memcpy(t->host.data(), v.values, 32 * total); }
+        if (audit) {
+            uint64_t key = 0;
+            double ms = 0;
+            if (int r = stree_audit_run(t.get(), &key, &ms)) { g_stree_error = t->err; return r; }
+            if (key != ~(uint64_t)0) {
+                g_stree_error = "audit: the node of level " + std::to_string(key >> 32) + " with prefix " + std::to_string(sh.pref[sh.start[key >> 32] + (size_t)(key & 0xFFFFFFFFu)]) +
+                                " is not the digest of its children";
+                return DST_ERR_ARG;
+            }
+        }
+    } catch (const std::bad_alloc&) { g_stree_error = "out of host memory"; return DST_ERR_HIP; }
+    *out = t.release();
+    return DST_OK;
+}

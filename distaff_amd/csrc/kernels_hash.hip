@@ -734,3 +734,96 @@ int k_rescue_multiproof_level(hipStream_t stream, fe* pool, const uint32_t* jobs
     else hipLaunchKernelGGL(rescue_multiproof_level_kernel, grid, block, 0, stream, pool, jobs, count, inputs, bad);
     return hipGetLastError() == hipSuccess ? 0 : -1;
 }
+
+// ---- audits (dst_rtree_audit, dst_stree_audit): is every stored parent still the digest of its two children?  The work of a build without its
+//      shape: all parents are there, no level waits for the one below, so ONE launch checks every parent of every level.  A lane hashes the
+//      children as the level kernels do, compares the digest with the stored node, which it reads after the digest, and a parent that differs
+//      goes into *first_bad by atomicMin -- the only word these kernels write; the host sets it to all ones.  The key orders the parents from
+//      the root down: a dense tree's heap position; a sparse tree's level in the high 32 bits and the index within the level's list below. ------
+__global__ void __launch_bounds__(RESCUE_THREADS) rescue_tree_audit_kernel(const fe* __restrict__ nodes, size_t leaves, unsigned long long* __restrict__ first_bad) {
+    const size_t p = (size_t)blockIdx.x * RESCUE_THREADS + threadIdx.x + 1;
+    if (p >= leaves) return;
+    fe d0, d1;
+    rescue_digest4(nodes[4 * p], nodes[4 * p + 1], nodes[4 * p + 2], nodes[4 * p + 3], d0, d1);
+    if (!(fe_eq(d0, nodes[2 * p]) && fe_eq(d1, nodes[2 * p + 1]))) atomicMin(first_bad, (unsigned long long)p);
+}
+// the six-lanes-of-eight form (rescue_parent_spread): the digest ends in lanes 5, 4, which compare an element each.  A group past the end is
+// given the root, keeps the barriers and reports nothing.
+__global__ void __launch_bounds__(RESCUE_THREADS) rescue_tree_audit_spread_kernel(const fe* __restrict__ nodes, size_t leaves, unsigned long long* __restrict__ first_bad) {
+    __shared__ fe xch[RESCUE_THREADS];
+    const size_t i = (size_t)blockIdx.x * (RESCUE_THREADS / 8u) + (threadIdx.x >> 3) + 1;
+    const bool live = i < leaves;
+    const size_t p = live ? i : 1;
+    const uint32_t e = threadIdx.x & 7u;
+    fe v = fe_zero();                                                  // state after hasher.rs:18: (0, 0, r1, r0, l1, l0)
+    if (e >= 2u && e < 6u) v = nodes[4 * p + (5u - e)];
+    rescue_permute_lane(v, e, xch + (threadIdx.x & ~7u));
+    if (live && (e == 5u || e == 4u) && !fe_eq(v, nodes[2 * p + (5u - e)])) atomicMin(first_bad, (unsigned long long)p);
+}
+// sparse: the parents are the flat positions [first, first + count) -- every level above the leaf level, which the layout puts first.  levels[2 l],
+// levels[2 l + 1] = start and length of level l and the starts fall as l grows, so the level of p is the number of levels l < depth that start
+// past p; empties[2 l ..) = the value of an empty subtree of level l.  The searches come first, as in rescue_stree_level_kernel.
+__device__ __forceinline__ uint32_t rescue_stree_level_of(const uint64_t* __restrict__ levels, uint32_t depth, size_t p) {
+    uint32_t l = 0;
+    for (uint32_t k = 0; k < depth; k++) l += p < levels[2 * k] ? 1u : 0u;
+    return l;
+}
+__global__ void __launch_bounds__(RESCUE_THREADS) rescue_stree_audit_kernel(const fe* __restrict__ nodes, const uint64_t* __restrict__ pref, const uint64_t* __restrict__ levels,
+                                                                           const fe* __restrict__ empties, uint32_t depth, size_t first, size_t count,
+                                                                           unsigned long long* __restrict__ first_bad) {
+    const size_t g = (size_t)blockIdx.x * RESCUE_THREADS + threadIdx.x;
+    if (g >= count) return;
+    const size_t p = first + g;
+    const uint32_t l = rescue_stree_level_of(levels, depth, p);
+    const size_t cstart = levels[2 * l + 2];
+    size_t left, right;
+    stree_children(pref + cstart, levels[2 * l + 3], pref[p], left, right);
+    fe v0 = empties[2 * l + 2], v1 = empties[2 * l + 3], v2 = v0, v3 = v1;
+    if (left != STREE_ABSENT) { v0 = nodes[2 * (cstart + left)]; v1 = nodes[2 * (cstart + left) + 1]; }
+    if (right != STREE_ABSENT) { v2 = nodes[2 * (cstart + right)]; v3 = nodes[2 * (cstart + right) + 1]; }
+    fe d0, d1;
+    rescue_digest4(v0, v1, v2, v3, d0, d1);
+    if (!(fe_eq(d0, nodes[2 * p]) && fe_eq(d1, nodes[2 * p + 1]))) atomicMin(first_bad, ((unsigned long long)l << 32) | (unsigned long long)(p - levels[2 * l]));
+}
+// the six-lanes-of-eight form (rescue_stree_level_spread_kernel): lanes 5, 4 hold l0, l1 and lanes 3, 2 hold r0, r1; a group past the end is
+// given the first parent, keeps the barriers and reports nothing
+__global__ void __launch_bounds__(RESCUE_THREADS) rescue_stree_audit_spread_kernel(const fe* __restrict__ nodes, const uint64_t* __restrict__ pref, const uint64_t* __restrict__ levels,
+                                                                                  const fe* __restrict__ empties, uint32_t depth, size_t first, size_t count,
+                                                                                  unsigned long long* __restrict__ first_bad) {
+    __shared__ fe xch[RESCUE_THREADS];
+    const size_t i = (size_t)blockIdx.x * (RESCUE_THREADS / 8u) + (threadIdx.x >> 3);
+    const bool live = i < count;
+    const size_t p = first + (live ? i : 0);
+    const uint32_t e = threadIdx.x & 7u;
+    const uint32_t l = rescue_stree_level_of(levels, depth, p);
+    fe v = fe_zero();                                                  // state after hasher.rs:18: (0, 0, r1, r0, l1, l0)
+    if (e >= 2u && e < 6u) {
+        const size_t cstart = levels[2 * l + 2];
+        size_t left, right;
+        stree_children(pref + cstart, levels[2 * l + 3], pref[p], left, right);
+        const size_t child = e >= 4u ? left : right;
+        v = empties[2 * l + 2 + (1u - (e & 1u))];
+        if (child != STREE_ABSENT) v = nodes[2 * (cstart + child) + (1u - (e & 1u))];
+    }
+    rescue_permute_lane(v, e, xch + (threadIdx.x & ~7u));
+    if (live && (e == 5u || e == 4u) && !fe_eq(v, nodes[2 * p + (5u - e)])) atomicMin(first_bad, ((unsigned long long)l << 32) | (unsigned long long)(p - levels[2 * l]));
+}
+
+int k_rescue_tree_audit(hipStream_t stream, const fe* nodes, size_t leaves, unsigned long long* first_bad) {
+    const size_t count = leaves - 1;
+    const bool spread = count <= RESCUE_SPREAD_MAX;
+    const size_t per_block = spread ? RESCUE_THREADS / 8 : RESCUE_THREADS;
+    const dim3 grid((unsigned)((count + per_block - 1) / per_block)), block(RESCUE_THREADS);
+    if (spread) hipLaunchKernelGGL(rescue_tree_audit_spread_kernel, grid, block, 0, stream, nodes, leaves, first_bad);
+    else hipLaunchKernelGGL(rescue_tree_audit_kernel, grid, block, 0, stream, nodes, leaves, first_bad);
+    return hipGetLastError() == hipSuccess ? 0 : -1;
+}
+int k_rescue_stree_audit(hipStream_t stream, const fe* nodes, const uint64_t* pref, const uint64_t* levels, const fe* empties, uint32_t depth, size_t first, size_t count,
+                         unsigned long long* first_bad) {
+    const bool spread = count <= RESCUE_SPREAD_MAX;
+    const size_t per_block = spread ? RESCUE_THREADS / 8 : RESCUE_THREADS;
+    const dim3 grid((unsigned)((count + per_block - 1) / per_block)), block(RESCUE_THREADS);
+    if (spread) hipLaunchKernelGGL(rescue_stree_audit_spread_kernel, grid, block, 0, stream, nodes, pref, levels, empties, depth, first, count, first_bad);
+    else hipLaunchKernelGGL(rescue_stree_audit_kernel, grid, block, 0, stream, nodes, pref, levels, empties, depth, first, count, first_bad);
+    return hipGetLastError() == hipSuccess ? 0 : -1;
+}

@@ -63,7 +63,8 @@ EXPORTS = ["dst_ctx_create", "dst_ctx_destroy", "dst_last_error", "dst_phase_ms"
            "dst_rescue_path_roots", "dst_rescue_verify_paths", "dst_rescue_verify_writes",
            "dst_stree_remove", "dst_stree_compact", "dst_stree_get",
            "dst_rescue_multiproof_size", "dst_rtree_multiproof", "dst_stree_multiproof", "dst_rescue_multiproof_root", "dst_rescue_verify_multiproof",
-           "dst_rescue_multiproof_paths"]
+           "dst_rescue_multiproof_paths",
+           "dst_rtree_save", "dst_rtree_load", "dst_rtree_audit", "dst_stree_save", "dst_stree_load", "dst_stree_audit"]
 
 
 class DistaffError(RuntimeError):
@@ -485,6 +486,25 @@ def multiproof_paths(n, indices, leaves, nodes, device=0, lib=None, stats=None, 
     return [[(v[2 * (i * n + k)], v[2 * (i * n + k) + 1]) for k in range(n)] for i in range(idx.size)], tuple(arr_to_ints(root))
 
 
+def _tree_save(tree, call):
+    """save() of either tree: the size query, then the bytes"""
+    n = ctypes.c_size_t(0)
+    tree._check(call(tree._h, None, ctypes.c_size_t(0), ctypes.byref(n)))
+    out = np.zeros(n.value, dtype=np.uint8)
+    tree._check(call(tree._h, _ptr(out), ctypes.c_size_t(n.value), ctypes.byref(n)))
+    return out.tobytes()
+
+
+def _tree_load(lib, call, error, blob, device, audit):
+    """load() of either tree -> the handle; `error(lib)` = the text of the calling thread's last failed call without a tree"""
+    a = np.frombuffer(blob, dtype=np.uint8)
+    h = ctypes.c_void_p()
+    r = call(ctypes.c_int(device), _ptr(a) if a.size else None, ctypes.c_size_t(a.size), ctypes.c_uint32(1 if audit else 0), ctypes.byref(h))
+    if r != DST_OK:
+        raise DistaffError(r, error(lib))
+    return h
+
+
 def _apply(tree, call, n, indices, leaves):
     """(paths, roots) of an ordered batch of writes: paths in the shape paths() returns, roots a list of pairs of ints"""
     idx, ip = RescueTree._indices(indices)
@@ -622,6 +642,30 @@ class RescueTree:
         out = np.zeros((count, 2, 2), dtype=np.uint64)
         self._check(self.lib.dst_rtree_read_nodes(self._h, ctypes.c_uint64(first), ctypes.c_uint64(count), _ptr(out)))
         return out
+
+    def save(self):
+        """the tree as bytes (dst_rtree_save): a 64-byte header and the nodes of heap positions 1 and up; include/distaff_hip.h has the layout.
+        The same bytes whether the tree lives on the host or on a device."""
+        return _tree_save(self, self.lib.dst_rtree_save)
+
+    @classmethod
+    def load(cls, blob, device=0, audit=False, lib=None):
+        """the tree save() wrote, on `device` (dst_rtree_load), without hashing it again: build_ms is 0.  Malformed bytes raise
+        DistaffError(DST_ERR_ARG).  Without `audit` the node values are believed -- the tree is only as good as its blob; with it, audit() runs
+        first and a bad node raises DistaffError(DST_ERR_ARG) whose text names it."""
+        t = cls.__new__(cls)
+        t.lib = lib or load()
+        t._h = _tree_load(t.lib, t.lib.dst_rtree_load, _rtree_error, blob, device, audit)
+        t.log_leaves = int.from_bytes(bytes(blob[12:16]), "little")
+        return t
+
+    def audit(self):
+        """None when every parent is the digest of its two children, else the lowest heap position in [1, 2^log_leaves) whose node is not
+        (dst_rtree_audit).  One launch on a device tree; audit_ms then holds its device milliseconds.  The tree is unchanged."""
+        bad, ms = ctypes.c_int64(0), ctypes.c_double(0)
+        self._check(self.lib.dst_rtree_audit(self._h, ctypes.byref(bad), ctypes.byref(ms)))
+        self.audit_ms = ms.value
+        return None if bad.value < 0 else bad.value
 
 class StreeInfo(ctypes.Structure):
     _fields_ = [("depth", ctypes.c_uint32), ("device", ctypes.c_int32), ("keys", ctypes.c_uint64), ("nodes", ctypes.c_uint64),
@@ -769,6 +813,31 @@ class SparseRescueTree:
         i = StreeInfo()
         self._check(self.lib.dst_stree_info(self._h, ctypes.byref(i)))
         return {f: getattr(i, f) for f, _ in StreeInfo._fields_}
+
+    def save(self):
+        """the tree as bytes (dst_stree_save): a 64-byte header, the level lengths, every level's prefixes, every level's nodes, the leaf level
+        first; include/distaff_hip.h has the layout.  The same bytes whether the tree lives on the host or on a device."""
+        return _tree_save(self, self.lib.dst_stree_save)
+
+    @classmethod
+    def load(cls, blob, device=0, audit=False, lib=None):
+        """the tree save() wrote, on `device` (dst_stree_load), without hashing it again: last_digests is 0.  Bytes that are malformed, or
+        whose levels create + set could not have made, raise DistaffError(DST_ERR_ARG).  Without `audit` the node values are believed -- the
+        tree is only as good as its blob; with it, audit() runs first and a bad node raises DistaffError(DST_ERR_ARG) whose text names it."""
+        t = cls.__new__(cls)
+        t.lib = lib or load()
+        t._h = _tree_load(t.lib, t.lib.dst_stree_load, lambda l: t._error(None), blob, device, audit)
+        t.depth = t.info()["depth"]
+        return t
+
+    def audit(self):
+        """None when every stored parent is the digest of its two children (one that is not stored counts as the empty subtree of its
+        level), else (level, prefix) of the bad parent nearest the root, the lowest prefix within its level (dst_stree_audit).  One launch on a
+        device tree; audit_ms then holds its device milliseconds.  The tree is unchanged."""
+        level, prefix, ms = ctypes.c_int32(0), ctypes.c_uint64(0), ctypes.c_double(0)
+        self._check(self.lib.dst_stree_audit(self._h, ctypes.byref(level), ctypes.byref(prefix), ctypes.byref(ms)))
+        self.audit_ms = ms.value
+        return None if level.value < 0 else (level.value, prefix.value)
 
 
 class Comm:

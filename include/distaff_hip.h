@@ -275,7 +275,7 @@ DST_API int dst_rescue_multiproof_paths(int device, uint32_t n, const uint64_t* 
                                         const uint8_t* nodes /* num_nodes*32 */, size_t num_nodes, uint8_t* paths /* count*n*32 */, uint8_t root[32],
                                         double* device_ms);
 DST_API void dst_rtree_destroy(dst_rtree* t);
-DST_API const char* dst_rtree_last_error(const dst_rtree* t);     /* t may be NULL: the error of the calling thread's last failed dst_rtree_build / dst_rescue_digest_many / dst_rescue_path_tapes / dst_rescue_path_roots / dst_rescue_verify_* / dst_rescue_multiproof_* */
+DST_API const char* dst_rtree_last_error(const dst_rtree* t);     /* t may be NULL: the error of the calling thread's last failed dst_rtree_build / dst_rtree_load / dst_rescue_digest_many / dst_rescue_path_tapes / dst_rescue_path_roots / dst_rescue_verify_* / dst_rescue_multiproof_* */
 
 /* ---- sparse Rescue Merkle trees: a set addressed by keys of up to 63 bits (accounts, notes, nullifiers) ------------------------------------
  * A sparse tree of depth D, 1 <= D <= 63, IS the dense tree above over 2^D leaves in which every leaf that was never set holds the tree's empty
@@ -349,8 +349,46 @@ typedef struct dst_stree_info_t {
     double last_device_ms;              /* events around that call's level launches, as dst_rtree_update_ms; 0 on a host tree */
 } dst_stree_info_t;
 DST_API int dst_stree_info(const dst_stree* t, dst_stree_info_t* out);
+
+/* ---- save, restore and audit: a tree survives a restart without being hashed again ------------------------------------------------------------
+ * THE BLOB is little-endian and self-describing, and byte-identical whether a host tree or a device tree wrote it:
+ *   header, 64 bytes:  8 bytes of magic "DSTTREE1" (the last byte is the version digit) | u32 kind: 1 = dense, 2 = sparse | u32 depth: log_leaves
+ *                      of a dense tree, the depth of a sparse one | 32 bytes of empty leaf, all zero in a dense blob | u64 number of keys (2^log_leaves
+ *                      in a dense blob) | u64 number of stored nodes;
+ *   dense body:        the 2^(log_leaves+1) - 1 nodes of heap positions 1 and up, 32 bytes each: the bytes of dst_rtree_read_nodes(t, 1, ...);
+ *   sparse body:       depth + 1 level lengths as u64, then every level's sorted prefixes as u64, then every level's nodes, 32 bytes each.  All
+ *                      three run in the order the tree keeps its levels -- the leaf level (depth) first, the root level (0) last -- so saving
+ *                      is a copy.  A key stored with the empty value stays stored.  The E_l are not in the blob: load derives them from the empty
+ *                      leaf as dst_stree_create does.
+ * The length must be exactly what the header implies: 64 + 32 * nodes (dense), 64 + 8 * (depth + 1) + 40 * nodes (sparse).
+ * SAVE: out == NULL is the size query; *len always receives the length; DST_ERR_ARG when cap is smaller.  The tree is unchanged.
+ * LOAD takes untrusted bytes and refuses with DST_ERR_ARG, before anything is allocated: a short blob or trailing bytes, a wrong magic, version
+ * or kind, a depth outside 1..26 (dense) / 1..63 (sparse), counts that disagree with the depth or with each other, an element -- the empty leaf
+ * included -- that is not below p, and any sparse shape that create + set could not have made: prefixes of a level not strictly ascending or not
+ * below 2^level, level l not exactly the distinct prefix >> 1 of level l + 1, more than one root, a leaf level whose length is not the key count,
+ * 2^32 - 1 stored nodes or more.  *out is NULL after any refusal and nothing stays allocated; the reason is dst_rtree_last_error(NULL) /
+ * dst_stree_last_error(NULL).  A sparse blob without keys is valid: the tree with root E_0.
+ * With audit == 0 load hashes NOTHING (a sparse load computes the depth digests E_l on the host, as create does): one allocation, the upload
+ * of the nodes straight from the caller's blob (a sparse tree's two small tables and its prefixes beside them), no digest launch, no second copy
+ * of the blob in host memory; dst_rtree_build_ms and last_digests then read 0.  A TREE LOADED WITHOUT AUDIT IS ONLY AS GOOD AS ITS BLOB: the shape is
+ * checked, the node values are believed.  With audit != 0 the audit below runs before the tree is handed out; a bad node is DST_ERR_ARG, *out is
+ * NULL and the error text names the node ("audit: node 5 ...", "audit: the node of level 3 with prefix 5 ...").  A caller that wants the
+ * location in numbers loads without audit and calls the audit itself.  A loaded tree is a full tree: update, apply, set, remove, compact,
+ * paths, tapes and multiproofs work on it as on a built one.
+ * AUDIT checks that every stored parent is the digest of its two children, on built and on loaded trees, and leaves the tree unchanged.  The
+ * work of a build, but no level waits for the one below: on a device tree it is ONE launch over all parents of all levels, whatever the depth.
+ * Dense: *first_bad = the lowest heap position p in [1, 2^log_leaves) whose node differs from digest(node[2p], node[2p+1]), -1 when there is
+ * none.  Sparse: every stored node of a level l < depth must equal the digest of its children at level l + 1, a child that is not stored being
+ * E_{l+1}; the bad parent nearest the root is reported, within its level the one of the lowest prefix; *bad_level = -1 (and *bad_prefix = 0)
+ * when there is none.  A bad node is NOT an error: the call returns DST_OK.  *device_ms (may be NULL): events around the launch, 0 on the host. */
+DST_API int dst_rtree_save(const dst_rtree* t, uint8_t* out /* cap bytes, or NULL */, size_t cap, size_t* len);
+DST_API int dst_rtree_load(int device, const uint8_t* blob, size_t len, uint32_t audit, dst_rtree** out);
+DST_API int dst_rtree_audit(const dst_rtree* t, int64_t* first_bad, double* device_ms /* may be NULL */);
+DST_API int dst_stree_save(const dst_stree* t, uint8_t* out /* cap bytes, or NULL */, size_t cap, size_t* len);
+DST_API int dst_stree_load(int device, const uint8_t* blob, size_t len, uint32_t audit, dst_stree** out);
+DST_API int dst_stree_audit(const dst_stree* t, int32_t* bad_level, uint64_t* bad_prefix, double* device_ms /* may be NULL */);
 DST_API void dst_stree_destroy(dst_stree* t);
-DST_API const char* dst_stree_last_error(const dst_stree* t);     /* t may be NULL: the error of the calling thread's last failed dst_stree_create */
+DST_API const char* dst_stree_last_error(const dst_stree* t);     /* t may be NULL: the error of the calling thread's last failed dst_stree_create / dst_stree_load */
 
 /* ---- host-side helpers that the Rust host would otherwise take from `rand` (they run on the CPU) -------------------- */
 DST_API void dst_prng_vector(const uint8_t seed[32], uint32_t count, uint8_t* out /* count*16 */);          /* field.rs:271 */

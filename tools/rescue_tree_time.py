@@ -12,6 +12,8 @@ device's own modular-multiplication rate sets.
                                                      made them, the same check on the host for 256 writes, and dst_rescue_verify_paths of 4 096 paths
     python tools/rescue_tree_time.py --multiproof    compressed batch openings: bytes, digests and the device time of dst_rescue_multiproof_root beside
                                                      dst_rescue_verify_paths on the full paths of the same leaves (K = 256, 4 096, 65 536; both trees above)
+    python tools/rescue_tree_time.py --restore       save, restore, audit: dst_rtree_audit beside dst_rtree_build_ms of the dense 2^20 tree, dst_stree_audit beside the
+                                                     one dst_stree_set that builds the depth-63 tree of 2^20 keys, the wall time of a load beside that of the rebuild
 One digest is counted as 9 180 field multiplications, the reference's own count per hasher::digest: ten rounds of 6 x 2 for the cubes, 6 x 139
 for x^INV_ALPHA by the addition chain (127 squarings + 12 multiplications) and 2 x 36 for the two MDS products."""
 import argparse
@@ -36,6 +38,7 @@ ap.add_argument("--remove", action="store_true", help="time dst_stree_remove of 
 ap.add_argument("--sequence", action="store_true", help="time dst_rtree_apply / dst_stree_apply (1, 256, 4 096, 65 536 ordered writes) and, for 256, the loop of update + path calls")
 ap.add_argument("--verify", action="store_true", help="time dst_rescue_verify_writes on the witnesses of dst_rtree_apply / dst_stree_apply (256, 4 096, 65 536 writes), on the host for 256, and dst_rescue_verify_paths of 4 096 paths")
 ap.add_argument("--multiproof", action="store_true", help="time dst_rescue_multiproof_root of 256, 4 096, 65 536 distinct leaves of the dense 2^20 tree and of the depth-63 tree of 2^20 keys beside dst_rescue_verify_paths on the full paths of the same leaves; bytes and digests of both")
+ap.add_argument("--restore", action="store_true", help="time dst_rtree_audit / dst_stree_audit (one launch each) beside the builds of the same trees (dense 2^20; depth 63 with 2^20 keys), and dst_rtree_load / dst_stree_load of their saved forms beside the wall time of the rebuild")
 ap.add_argument("sizes", nargs="*", type=int)
 args = ap.parse_args()
 lib = D.lib._open(os.path.abspath(args.lib)) if args.lib else None       # through the binding: one HIP runtime per process
@@ -105,7 +108,7 @@ if args.update:
     print("dst_rtree_paths of %d indices: %.3f ms wall; %d calls of dst_rtree_path: %.2f ms wall (ctypes, no conversion): %.0f x" % (count, c_many * 1e3, count, c_single * 1e3, c_single / c_many))
     t.close()
     sys.exit(0)
-if args.sparse or args.remove:
+if args.sparse or args.remove or args.restore:
     DEPTH = 63
 
     def keys_and_leaves(count, seed):
@@ -116,6 +119,86 @@ if args.sparse or args.remove:
         v[..., 1] >>= np.uint64(1)
         return k[:count], v
 
+if args.restore:
+    import ctypes
+    L = lib or D.load()
+    vp = lambda x: x.ctypes.data_as(ctypes.c_void_p)  # noqa: E731
+
+    def saved(tree, save):
+        """the blob in a numpy array, through the C call alone, and the wall milliseconds of the call that wrote it"""
+        n = ctypes.c_size_t(0)
+        assert save(tree._h, None, ctypes.c_size_t(0), ctypes.byref(n)) == 0
+        out = np.zeros(n.value, dtype=np.uint8)
+        t0 = time.perf_counter()
+        assert save(tree._h, vp(out), ctypes.c_size_t(n.value), ctypes.byref(n)) == 0
+        return out, (time.perf_counter() - t0) * 1e3
+
+    def loaded(load, destroy, blob, audit, runs):
+        """wall milliseconds of `runs` loads of the blob (each tree destroyed outside the timed part) and the last handle"""
+        ms, h = [], None
+        for _ in range(runs):
+            if h is not None:
+                destroy(h)
+            h = ctypes.c_void_p()
+            t0 = time.perf_counter()
+            r = load(ctypes.c_int(0), vp(blob), ctypes.c_size_t(blob.size), ctypes.c_uint32(audit), ctypes.byref(h))
+            ms.append((time.perf_counter() - t0) * 1e3)
+            assert r == 0, r
+        return ms, h
+
+    L.dst_rtree_destroy.restype = L.dst_stree_destroy.restype = None
+    log_leaves = 20
+    a = leaves(log_leaves)
+    D.RescueTree(a, device=0, lib=lib).close()      # warm-up
+    t0 = time.perf_counter(); t = D.RescueTree(a, device=0, lib=lib); build_wall = (time.perf_counter() - t0) * 1e3
+    build_ms = t.build_ms
+    audits = []
+    for _ in range(1 + args.runs):                  # the first is the warm-up: the staging word, code
+        assert t.audit() is None
+        audits.append(t.audit_ms)
+    audits = audits[1:]
+    blob, save_ms = saved(t, L.dst_rtree_save)
+    print("dense 2^%d leaves: build %.3f ms on the device (dst_rtree_build_ms, %d level launches), %.1f ms wall with the upload; audit %.3f ms on the device, ONE launch over %d parents "
+          "(min of %d after one warm-up; all: %s): audit / build = %.3f" % (log_leaves, build_ms, log_leaves, build_wall, min(audits), (1 << log_leaves) - 1, args.runs,
+                                                                          " ".join("%.3f" % v for v in audits), min(audits) / build_ms))
+    ms, h = loaded(L.dst_rtree_load, L.dst_rtree_destroy, blob, 0, 1 + args.runs)
+    ms_a, h_a = loaded(L.dst_rtree_load, L.dst_rtree_destroy, blob, 1, args.runs)
+    L.dst_rtree_destroy(h_a)
+    back = D.RescueTree.__new__(D.RescueTree)
+    back.lib, back._h, back.log_leaves = L, h, log_leaves
+    assert back.root == t.root and back.build_ms == 0 and back.audit() is None
+    print("   saved in %.1f ms wall, %d bytes; dst_rtree_load without audit: %.1f ms wall (min of %d after one warm-up; all: %s), with audit: %.1f ms wall (all: %s); rebuild / load = %.2f, "
+          "rebuild / load with audit = %.2f; root %032x %032x" % (save_ms, blob.size, min(ms[1:]), args.runs, " ".join("%.1f" % v for v in ms[1:]), min(ms_a), " ".join("%.1f" % v for v in ms_a),
+                                                                   build_wall / min(ms[1:]), build_wall / min(ms_a), back.root[0], back.root[1]))
+    back.close(); t.close()
+    del blob, a
+    k, v = keys_and_leaves(1 << 20, 20)
+    s = D.SparseRescueTree(DEPTH, device=0, lib=lib)
+    t0 = time.perf_counter(); s.set(k, v); set_wall = (time.perf_counter() - t0) * 1e3
+    info = s.info()
+    audits = []
+    for _ in range(1 + min(args.runs, 3)):
+        assert s.audit() is None
+        audits.append(s.audit_ms)
+    audits = audits[1:]
+    blob, save_ms = saved(s, L.dst_stree_save)
+    print("sparse depth %d, %d keys, %d stored nodes: the one set that builds it %.3f ms on the device (last_device_ms, one launch per level), %d digests, %.1f ms wall with the plan and the "
+          "uploads; audit %.3f ms on the device, ONE launch over %d parents (min of %d after one warm-up; all: %s): audit / set = %.3f"
+          % (DEPTH, info["keys"], info["nodes"], info["last_device_ms"], info["last_digests"], set_wall, min(audits), info["nodes"] - info["keys"], len(audits),
+             " ".join("%.3f" % x for x in audits), min(audits) / info["last_device_ms"]))
+    root = s.root
+    s.close()
+    ms, h = loaded(L.dst_stree_load, L.dst_stree_destroy, blob, 0, 3)
+    ms_a, h_a = loaded(L.dst_stree_load, L.dst_stree_destroy, blob, 1, 2)
+    L.dst_stree_destroy(h_a)
+    back = D.SparseRescueTree.__new__(D.SparseRescueTree)
+    back.lib, back._h, back.depth = L, h, DEPTH
+    assert back.root == root and back.info()["last_digests"] == 0 and back.info()["nodes"] == info["nodes"]
+    print("   saved in %.1f ms wall, %d bytes; dst_stree_load without audit: %.1f ms wall (min of 2 after one warm-up; all: %s), with audit: %.1f ms wall (all: %s); rebuild / load = %.2f, "
+          "rebuild / load with audit = %.2f; root %032x %032x" % (save_ms, blob.size, min(ms[1:]), " ".join("%.1f" % x for x in ms[1:]), min(ms_a), " ".join("%.1f" % x for x in ms_a),
+                                                                   set_wall / min(ms[1:]), set_wall / min(ms_a), root[0], root[1]))
+    back.close()
+    sys.exit(0)
 if args.remove:
     import ctypes
     vp = lambda x: x.ctypes.data_as(ctypes.c_void_p)  # noqa: E731

@@ -624,9 +624,9 @@ int dst_proof_info(const uint8_t* proof, size_t len, dst_proof_info_t* info) {
 
 // ---- Rescue digests and Rescue Merkle trees (dst_rescue_digest_many, dst_rtree_*): no context, compiled with this unit ---------------------
 #include "host/rtree_impl.h"
-// ---- sparse Rescue Merkle trees (dst_stree_*): the same, over keys of up to 63 bits ----------------------------------------------------------
+// ---- sparse Rescue Merkle trees: the same, over keys of up to 63 bits (dst_stree_*) and of up to 127 bits (dst_wtree_*) --------------------------
 #include "host/stree_impl.h"
-// ---- checking paths and the witnesses of ordered writes (dst_rescue_path_roots, dst_rescue_verify_*): no tree, no context -------------------
+// ---- checking paths and the witnesses of ordered writes (dst_rescue_path_roots, dst_rescue_verify_*, their _w forms): no tree, no context -----
 #include "host/path_verify_impl.h"
 // ---- compressed batch openings (dst_rescue_multiproof_*, dst_rtree_multiproof, dst_stree_multiproof): every shared ancestor once ------------
 #include "host/multiproof_impl.h"

@@ -499,6 +499,13 @@ int k_rescue_tree_scatter(hipStream_t stream, fe* nodes, const uint32_t* pos /* 
 int k_rescue_tree_gather(hipStream_t stream, const fe* nodes, const uint32_t* pos /* device */, fe* out /* 2 per node */, size_t count);       // out[i] = nodes[pos[i]]
 // sparse trees (host/stree_levels.h): all levels in one node array and one prefix array (device), indexed by flat positions.  One level: the `count`
 // parents at list[..] (device; nullptr: pstart + [0, count)) from the child level [cstart, cstart + ccnt); empty = the value of an empty child (host)
+// Every launcher that reads prefixes or indices has a second form over stree_wide, the 16-byte keys of the wide trees (dst_wtree_*, dst_rescue_*_w):
+// the same kernel body instantiated over the key type
+struct stree_wide;
+int k_rescue_stree_level(hipStream_t stream, fe* nodes, const stree_wide* pref, const uint32_t* list, size_t count, size_t pstart, size_t cstart, size_t ccnt, const fe* empty);
+int k_rescue_stree_open(hipStream_t stream, const fe* nodes, const stree_wide* pref, const uint64_t* levels, const fe* empties, const stree_wide* indices, fe* out, size_t count, uint32_t depth);
+int k_rescue_stree_lookup(hipStream_t stream, const fe* nodes, const stree_wide* pref, const uint64_t* levels, const fe* empties, const stree_wide* prefix, const uint32_t* level, fe* out, size_t count);
+int k_rescue_stree_get(hipStream_t stream, const fe* nodes, const stree_wide* pref, size_t lstart, size_t lcnt, const fe* empty, const stree_wide* indices, fe* out, uint8_t* stored, size_t count);
 int k_rescue_stree_level(hipStream_t stream, fe* nodes, const uint64_t* pref, const uint32_t* list, size_t count, size_t pstart, size_t cstart, size_t ccnt, const fe* empty);
 int k_rescue_stree_carry(hipStream_t stream, fe* dst, const fe* src, const uint32_t* from /* device */, size_t count);     // dst[j] = src[from[j]] unless from[j] == STREE_NEW
 // out[(i * (depth + 1) + k) ..] = node k of the path of indices[i], stored or empty; levels = (start, length) per level, empties = 2 elements per level (device)
@@ -528,4 +535,7 @@ int k_rescue_multiproof_level(hipStream_t stream, fe* pool, const uint32_t* jobs
 // `count` >= 1 parents at the flat positions first + [0, count) = every level above the leaf level; levels / empties as k_rescue_stree_open
 int k_rescue_tree_audit(hipStream_t stream, const fe* nodes, size_t leaves, unsigned long long* first_bad);
 int k_rescue_stree_audit(hipStream_t stream, const fe* nodes, const uint64_t* pref, const uint64_t* levels, const fe* empties, uint32_t depth, size_t first, size_t count,
+                         unsigned long long* first_bad);
+int k_rescue_path_roots(hipStream_t stream, const fe* paths, uint32_t n, const stree_wide* indices, size_t count, const fe* alt_leaves, uint32_t mode, fe* out /* 2 per chain */, uint32_t* bad);
+int k_rescue_stree_audit(hipStream_t stream, const fe* nodes, const stree_wide* pref, const uint64_t* levels, const fe* empties, uint32_t depth, size_t first, size_t count,
                          unsigned long long* first_bad);

@@ -9,17 +9,20 @@
 
 #define PV_MIN_NODES 2u
 #define PV_MAX_NODES 64u
+#define PV_WIDE_MAX_NODES 128u                       // the calls with 16-byte indices (dst_rescue_*_w)
 // the values of `why` (include/distaff_hip.h: DST_PATH_*)
 enum { PV_OK = 0, PV_BAD_LEAF = 1, PV_BAD_ROOT = 2, PV_BAD_NEXT_ROOT = 3 };
 
-// nullptr when `count` paths of n nodes with these indices can be hashed, else what is wrong: 2 <= n <= 64, count < 2^31, indices[i] < 2^(n-1)
-inline const char* pv_check_shape(uint32_t n, const uint64_t* indices, size_t count) {
-    if (n < PV_MIN_NODES || n > PV_MAX_NODES) return "a path has 2 .. 64 nodes";
+// nullptr when `count` paths of n nodes with these indices can be hashed, else what is wrong: 2 <= n <= 64 (128 for the 16-byte indices K of
+// the wide calls), count < 2^31, indices[i] < 2^(n-1)
+template <class K> inline const char* pv_check_shape_of(uint32_t n, const K* indices, size_t count) {
+    if (n < PV_MIN_NODES || n > 8 * sizeof(K)) return sizeof(K) == 8 ? "a path has 2 .. 64 nodes" : "a path has 2 .. 128 nodes";
     if ((uint64_t)count >= ((uint64_t)1 << 31)) return "2^31 paths or more";
     for (size_t i = 0; i < count; i++)
-        if (indices[i] >> (n - 1)) return "leaf index past the end";       // n - 1 <= 63: the shift is defined
+        if (indices[i] >> (n - 1)) return "leaf index past the end";       // n - 1 is below the width of K: the shift is defined
     return nullptr;
 }
+inline const char* pv_check_shape(uint32_t n, const uint64_t* indices, size_t count) { return pv_check_shape_of<uint64_t>(n, indices, count); }
 
 struct pv_verdict {
     int64_t first_bad = -1;

@@ -281,8 +281,9 @@ int dst_rtree_path(const dst_rtree* t, uint64_t index, uint8_t* path) {
     if (!path) return rt_fail(t, DST_ERR_ARG, "null pointer");
     return rtree_paths(t, &index, 1, path);
 }
-// the tapes of `count` paths of n nodes each, `each` elements per tape and path (dense and sparse trees)
-static void tapes_from_paths(const u128* paths, size_t n, const uint64_t* indices, size_t count, uint32_t what, size_t each, uint8_t* tape_a, uint8_t* tape_b) {
+// the tapes of `count` paths of n nodes each, `each` elements per tape and path (dense and sparse trees; K: uint64_t, or u128 for the wide ones)
+template <class K>
+static void tapes_from_paths(const u128* paths, size_t n, const K* indices, size_t count, uint32_t what, size_t each, uint8_t* tape_a, uint8_t* tape_b) {
     std::vector<u128> a, b;
     for (size_t i = 0; i < count; i++) {
         rescue_tapes(paths + 2 * n * i, n, indices[i], what, a, b);
@@ -308,10 +309,12 @@ static int rtree_tapes(const dst_rtree* t, const uint64_t* indices, size_t count
     } catch (const std::bad_alloc&) { return rt_fail(t, DST_ERR_HIP, "out of host memory"); }
     return DST_OK;
 }
-// generate_program_inputs over paths the caller holds (the witnesses of dst_rtree_apply / dst_stree_apply, or anyone's): no tree, no device
-int dst_rescue_path_tapes(const uint8_t* paths, uint32_t n, const uint64_t* indices, size_t count, uint32_t what, uint8_t* tape_a, uint8_t* tape_b, size_t cap_elems_each, size_t* elems_each) {
+// generate_program_inputs over paths the caller holds (the witnesses of dst_rtree_apply / dst_stree_apply / dst_wtree_apply, or anyone's): no tree,
+// no device.  K: uint64_t (n <= 64) or u128 (dst_rescue_path_tapes_w, n <= 128)
+template <class K>
+static int path_tapes(const uint8_t* paths, uint32_t n, const K* indices, size_t count, uint32_t what, uint8_t* tape_a, uint8_t* tape_b, size_t cap_elems_each, size_t* elems_each) {
     if (!elems_each || what < 1 || what > 3) { g_rtree_error = "elems_each missing, or what outside 1..3"; return DST_ERR_ARG; }
-    if (n < 2 || n > TSEQ_MAX_DEPTH + 1) { g_rtree_error = "a path has 2 .. 64 nodes"; return DST_ERR_ARG; }
+    if (n < 2 || n > 8 * sizeof(K)) { g_rtree_error = sizeof(K) == 8 ? "a path has 2 .. 64 nodes" : "a path has 2 .. 128 nodes"; return DST_ERR_ARG; }
     if (!indices && count) { g_rtree_error = "null pointer"; return DST_ERR_ARG; }
     if (count > ((size_t)1 << 40)) { g_rtree_error = "too many indices"; return DST_ERR_ARG; }
     const size_t each = ((what & 1u) ? 2 * (size_t)n - 1 : 0) + ((what & 2u) ? (size_t)n - 1 : 0);
@@ -329,6 +332,9 @@ int dst_rescue_path_tapes(const uint8_t* paths, uint32_t n, const uint64_t* indi
     } catch (const std::bad_alloc&) { g_rtree_error = "out of host memory"; return DST_ERR_HIP; }
     return DST_OK;
 }
+int dst_rescue_path_tapes(const uint8_t* paths, uint32_t n, const uint64_t* indices, size_t count, uint32_t what, uint8_t* tape_a, uint8_t* tape_b, size_t cap_elems_each, size_t* elems_each) {
+    return path_tapes(paths, n, indices, count, what, tape_a, tape_b, cap_elems_each, elems_each);
+}
 int dst_rtree_tapes(const dst_rtree* t, uint64_t index, uint32_t what, uint8_t* tape_a, uint8_t* tape_b, size_t cap_elems, size_t* elems) {
     return rtree_tapes(t, &index, 1, what, tape_a, tape_b, cap_elems, elems, "elems");
 }
@@ -342,15 +348,19 @@ int dst_rtree_tapes_many(const dst_rtree* t, const uint64_t* indices, size_t cou
 // otherwise.  Staging: [the leaves = the versions of level D][indices][source words][spos][the touched nodes' last operations] -- one upload --
 // [the versions of level D - 1]: the levels take the two version areas by turns; then [paths].  The last versions of level l + 1 go into the node
 // array behind the launch of level l, which reads that level's nodes as they were.  One synchronisation; ms: events around the launches.
-template <class T>
-static int tseq_run_device(const T* t, fe* nodes, const u128* empties, const tseq_plan& p, const std::vector<uint32_t>& spos, const uint64_t* indices, const uint8_t* leaves,
+// The level kernel reads bit k - 1 of a 64-bit index word.  16-byte indices (Key = u128, the wide sparse trees) are staged as two arrays, all
+// low halves and then all high halves; the launches of path nodes k > 64 get the high halves, k - 64, and the paths moved up by 64 nodes, which
+// is the same bit, the same sibling and the same slot of the path.
+template <class T, class Key>
+static int tseq_run_device(const T* t, fe* nodes, const u128* empties, const tseq_plan_t<Key>& p, const std::vector<uint32_t>& spos, const Key* indices, const uint8_t* leaves,
                            uint8_t* paths, uint8_t* roots, double* ms) {
-    const size_t K = p.count, D = p.depth, n = D + 1, S = spos.size();
-    const size_t o_idx = 32 * K, o_src = o_idx + 8 * K, o_pos = o_src + 4 * K * n, o_from = o_pos + 4 * S, up_bytes = o_from + 4 * S;
+    const size_t K = p.count, D = p.depth, n = D + 1, S = spos.size(), W = sizeof(Key) / 8;
+    const size_t o_idx = 32 * K, o_src = o_idx + 8 * W * K, o_pos = o_src + 4 * K * n, o_from = o_pos + 4 * S, up_bytes = o_from + 4 * S;
     const size_t o_other = (up_bytes + 15) & ~(size_t)15, o_paths = o_other + 32 * K, total = o_paths + (paths ? 32 * K * n : 0);
     std::vector<uint8_t> up(up_bytes);                                // the last host allocation: nothing is queued yet
     memcpy(up.data(), leaves, 32 * K);
-    memcpy(up.data() + o_idx, indices, 8 * K);
+    for (size_t w = 0; w < W; w++)
+        for (size_t i = 0; i < K; i++) { const uint64_t half = (uint64_t)(indices[i] >> (32 * w) >> (32 * w)); memcpy(up.data() + o_idx + 8 * (w * K + i), &half, 8); }
     memcpy(up.data() + o_src, p.src.data(), 4 * K * n);
     if (S) { memcpy(up.data() + o_pos, spos.data(), 4 * S); memcpy(up.data() + o_from, p.tlast.data(), 4 * S); }
     if (int r = rtree_stage(t, total)) return r;
@@ -366,8 +376,9 @@ static int tseq_run_device(const T* t, fe* nodes, const u128* empties, const tse
     RT_HIP(t->err, hipMemcpyAsync(st, up.data(), up_bytes, hipMemcpyHostToDevice, t->stream));
     RT_HIP(t->err, hipEventRecord(t->ev[0], t->stream));
     for (size_t l = D; l-- > 0;) {
-        const uint32_t k = (uint32_t)(D - l);
-        if (k_rescue_seq_level(t->stream, nodes, ver[(k - 1) & 1], ver[k & 1], d_src + k * K, k == 1 ? d_src : nullptr, d_idx, d_paths, K, k, (uint32_t)n,
+        const uint32_t k = (uint32_t)(D - l), high = k > 64 ? 64u : 0u;
+        if (k_rescue_seq_level(t->stream, nodes, ver[(k - 1) & 1], ver[k & 1], d_src + k * K, k == 1 ? d_src : nullptr, d_idx + (high ? K : 0), d_paths ? d_paths + 2 * high : nullptr, K, k - high,
+                               (uint32_t)n,
                                reinterpret_cast<const fe*>(empties ? empties + 2 * (l + 1) : none))) { t->err = "rescue_seq_level_kernel: launch failed"; return DST_ERR_HIP; }
         if (scatter(l + 1)) { t->err = "rescue_tree_scatter_from_kernel: launch failed"; return DST_ERR_HIP; }
     }

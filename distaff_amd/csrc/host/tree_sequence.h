@@ -15,7 +15,8 @@
 #define TSEQ_EMPTY 0x7FFFFFFFu
 #define TSEQ_MAX_DEPTH 63u
 
-struct tseq_plan {
+// K: the type of an index -- uint64_t (depth <= 63) or, for the wide sparse trees, unsigned __int128 (depth <= 127): one bit more than the depth
+template <class K> struct tseq_plan_t {
     uint32_t depth = 0;
     size_t count = 0;
     // row 0: where the old value of operation i's own leaf is read; row k (1 .. depth): where node k of its authentication path is, the sibling
@@ -23,19 +24,20 @@ struct tseq_plan {
     std::vector<uint32_t> src;
     // the nodes the sequence writes and the last operation through each: level l's, sorted by prefix = index >> (depth - l), at
     // [toff[l], toff[l] + tcnt[l]).  Level depth: the distinct indices with the operation whose value stays.
-    std::vector<uint64_t> tpref;
+    std::vector<K> tpref;
     std::vector<uint32_t> tlast;
-    size_t toff[TSEQ_MAX_DEPTH + 1] = {0}, tcnt[TSEQ_MAX_DEPTH + 1] = {0};
+    size_t toff[8 * sizeof(K)] = {0}, tcnt[8 * sizeof(K)] = {0};
     size_t touched() const { return tpref.size(); }
 };
+typedef tseq_plan_t<uint64_t> tseq_plan;
 
 // original(level, prefix) -> the source word of that node before the call (a position or TSEQ_EMPTY).  count < 2^31, indices below 2^depth.
 // One sort by (index, i); then, per level going up, one pass over the operations, held as groups of equal prefix, each in the order of i:
 // two sibling groups are merged by i, which says for every operation the last earlier one on the other side, and the merged group is the
 // parent's.  O(count * depth) after the sort, besides the calls of `original` (at most two per group and level).
-template <class Original>
-inline tseq_plan tseq_plan_make(uint32_t depth, const uint64_t* indices, size_t count, Original original) {
-    tseq_plan p;
+template <class K, class Original>
+inline tseq_plan_t<K> tseq_plan_make(uint32_t depth, const K* indices, size_t count, Original original) {
+    tseq_plan_t<K> p;
     p.depth = depth; p.count = count;
     p.src.assign((size_t)(depth + 1) * count, TSEQ_EMPTY);
     p.tpref.reserve(count * 2); p.tlast.reserve(count * 2);
@@ -46,15 +48,15 @@ inline tseq_plan tseq_plan_make(uint32_t depth, const uint64_t* indices, size_t 
         const uint32_t shift = depth - l;
         uint32_t* row = p.src.data() + (size_t)(depth - l + 1) * count;
         p.toff[l] = p.tpref.size();
-        auto group_end = [&](size_t a, uint64_t q) { while (a < count && (indices[ord[a]] >> shift) == q) a++; return a; };
-        auto touch = [&](size_t a, size_t b, uint64_t q) {             // the group [a, b) of prefix q
+        auto group_end = [&](size_t a, K q) { while (a < count && (indices[ord[a]] >> shift) == q) a++; return a; };
+        auto touch = [&](size_t a, size_t b, K q) {             // the group [a, b) of prefix q
             p.tpref.push_back(q); p.tlast.push_back(ord[b - 1]);
             if (l != depth) return;
             for (size_t t = a; t < b; t++) p.src[ord[t]] = t == a ? original(depth, q) : TSEQ_VERSION | ord[t - 1];
         };
         size_t w = 0;
         for (size_t a = 0; a < count;) {
-            const uint64_t q = indices[ord[a]] >> shift;
+            const K q = indices[ord[a]] >> shift;
             const size_t b = group_end(a, q);
             touch(a, b, q);
             const size_t c = (q & 1) == 0 ? group_end(b, q | 1) : b;

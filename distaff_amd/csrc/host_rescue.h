@@ -70,10 +70,10 @@ inline void rescue_path_positions(uint32_t log_leaves, uint64_t index, uint64_t*
 
 // the secret tapes of generate_program_inputs (merkle.rs:63-94) from a path of n nodes: what & 1 the leaf and the smpath inputs (2n - 1
 // elements per tape), what & 2 the pmpath inputs (n - 1)
-inline void rescue_tapes(const u128* path /* 2 per node */, size_t n, uint64_t index, uint32_t what, std::vector<u128>& a, std::vector<u128>& b) {
+inline void rescue_tapes(const u128* path /* 2 per node */, size_t n, u128 index /* below 2^(n-1), n <= 128 */, uint32_t what, std::vector<u128>& a, std::vector<u128>& b) {
     a.clear(); b.clear();
     if (what & 1u) {
-        uint64_t idx = index + ((uint64_t)1 << (n - 1));
+        u128 idx = index + ((u128)1 << (n - 1));
         a.push_back(path[0]); b.push_back(path[1]);
         for (size_t i = 1; i < n; i++) {
             a.push_back(0); b.push_back(idx & 1); idx >>= 1;

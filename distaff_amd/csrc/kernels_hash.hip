@@ -423,8 +423,11 @@ int k_rescue_tree_gather(hipStream_t stream, const fe* nodes, const uint32_t* po
 //      for 2q among the child level's prefixes [cstart, cstart + ccnt) and takes a side that is not stored from (e0, e1), the value of an empty
 //      subtree of the child level.  The search comes first: only the flat positions found live across the digest.  The parents of a launch are
 //      the flat positions list[0 .. count) (a dirty list) or pstart + [0 .. count) (the whole level, list == nullptr).  The host has validated the
-//      leaves, every inner node is a digest: nothing is checked here. ----------------------------------------------------------------------------
-__global__ void __launch_bounds__(RESCUE_THREADS) rescue_stree_level_kernel(fe* nodes, const uint64_t* __restrict__ pref, const uint32_t* __restrict__ list, size_t count,
+//      leaves, every inner node is a digest: nothing is checked here.  The kernels that read prefixes or indices are stated once over the key
+//      type K: uint64_t (dst_stree_*) and stree_wide, 16 bytes (dst_wtree_*, depth <= 127).  The wider search state -- two prefixes of two words
+//      each and the search bounds -- is dead before the digest starts, as the narrow search's is. ----------------------------------------------
+template <class K>
+__global__ void __launch_bounds__(RESCUE_THREADS) rescue_stree_level_kernel(fe* nodes, const K* __restrict__ pref, const uint32_t* __restrict__ list, size_t count,
                                                                            size_t pstart, size_t cstart, size_t ccnt, fe e0, fe e1) {
     const size_t g = (size_t)blockIdx.x * RESCUE_THREADS + threadIdx.x;
     if (g >= count) return;
@@ -440,7 +443,8 @@ __global__ void __launch_bounds__(RESCUE_THREADS) rescue_stree_level_kernel(fe* 
 }
 // the six-lanes-of-eight form (rescue_parent_spread): lanes 5, 4 hold l0, l1 and lanes 3, 2 hold r0, r1; a group past the end is given the first
 // parent, keeps the barriers and stores nothing
-__global__ void __launch_bounds__(RESCUE_THREADS) rescue_stree_level_spread_kernel(fe* nodes, const uint64_t* __restrict__ pref, const uint32_t* __restrict__ list, size_t count,
+template <class K>
+__global__ void __launch_bounds__(RESCUE_THREADS) rescue_stree_level_spread_kernel(fe* nodes, const K* __restrict__ pref, const uint32_t* __restrict__ list, size_t count,
                                                                                   size_t pstart, size_t cstart, size_t ccnt, fe e0, fe e1) {
     __shared__ fe xch[RESCUE_THREADS];
     const size_t i = (size_t)blockIdx.x * (RESCUE_THREADS / 8u) + (threadIdx.x >> 3);
@@ -468,22 +472,24 @@ __global__ void rescue_stree_carry_kernel(fe* __restrict__ dst, const fe* __rest
 }
 // openings: one lane per (index, path node, element).  levels[2 l], levels[2 l + 1] = start and length of level l; empties[2 l ..) = the value of
 // an empty subtree of level l.  A node that is not stored, the leaf included, is that value.
-__global__ void rescue_stree_open_kernel(const fe* __restrict__ nodes, const uint64_t* __restrict__ pref, const uint64_t* __restrict__ levels, const fe* __restrict__ empties,
-                                         const uint64_t* __restrict__ indices, fe* __restrict__ out, size_t count, uint32_t depth) {
+template <class K>
+__global__ void rescue_stree_open_kernel(const fe* __restrict__ nodes, const K* __restrict__ pref, const uint64_t* __restrict__ levels, const fe* __restrict__ empties,
+                                         const K* __restrict__ indices, fe* __restrict__ out, size_t count, uint32_t depth) {
     const size_t t = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
     const size_t n = depth + 1;
     if (t >= 2 * count * n) return;
     const size_t s = t >> 1;
     uint32_t level;
-    uint64_t prefix;
+    K prefix;
     stree_path_slot(depth, indices[s / n], (uint32_t)(s % n), level, prefix);
     const size_t start = levels[2 * level], pos = stree_find(pref + start, levels[2 * level + 1], prefix);
     out[t] = pos != STREE_ABSENT ? nodes[2 * (start + pos) + (t & 1)] : empties[2 * level + (t & 1)];
 }
 // the nodes of a multiproof (dst_stree_multiproof): one lane per (node, element); node s is (level[s], prefix[s]), found in its level's list like a
 // path node above, its level's empty subtree when it is not stored
-__global__ void rescue_stree_lookup_kernel(const fe* __restrict__ nodes, const uint64_t* __restrict__ pref, const uint64_t* __restrict__ levels, const fe* __restrict__ empties,
-                                           const uint64_t* __restrict__ prefix, const uint32_t* __restrict__ level, fe* __restrict__ out, size_t count) {
+template <class K>
+__global__ void rescue_stree_lookup_kernel(const fe* __restrict__ nodes, const K* __restrict__ pref, const uint64_t* __restrict__ levels, const fe* __restrict__ empties,
+                                           const K* __restrict__ prefix, const uint32_t* __restrict__ level, fe* __restrict__ out, size_t count) {
     const size_t t = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (t >= 2 * count) return;
     const size_t s = t >> 1;
@@ -493,8 +499,9 @@ __global__ void rescue_stree_lookup_kernel(const fe* __restrict__ nodes, const u
 }
 // the leaves alone (dst_stree_get): one lane per index, one search of the leaf level [lstart, lstart + lcnt); a key that is not stored gives the
 // empty leaf (e0, e1) and stored[i] = 0
-__global__ void rescue_stree_get_kernel(const fe* __restrict__ nodes, const uint64_t* __restrict__ pref, size_t lstart, size_t lcnt, fe e0, fe e1,
-                                        const uint64_t* __restrict__ indices, fe* __restrict__ out, uint8_t* __restrict__ stored, size_t count) {
+template <class K>
+__global__ void rescue_stree_get_kernel(const fe* __restrict__ nodes, const K* __restrict__ pref, size_t lstart, size_t lcnt, fe e0, fe e1,
+                                        const K* __restrict__ indices, fe* __restrict__ out, uint8_t* __restrict__ stored, size_t count) {
     const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= count) return;
     const size_t pos = stree_find(pref + lstart, lcnt, indices[i]);
@@ -510,30 +517,58 @@ __global__ void rescue_stree_empty_leaves_kernel(const fe* __restrict__ leaves, 
     flags[i] = fe_eq(leaves[2 * i], e0) && fe_eq(leaves[2 * i + 1], e1) ? 1 : 0;
 }
 
-int k_rescue_stree_level(hipStream_t stream, fe* nodes, const uint64_t* pref, const uint32_t* list, size_t count, size_t pstart, size_t cstart, size_t ccnt, const fe* empty) {
+template <class K>
+static int rescue_stree_level(hipStream_t stream, fe* nodes, const K* pref, const uint32_t* list, size_t count, size_t pstart, size_t cstart, size_t ccnt, const fe* empty) {
     const bool spread = count <= RESCUE_SPREAD_MAX;
     const size_t per_block = spread ? RESCUE_THREADS / 8 : RESCUE_THREADS;
     const dim3 grid((unsigned)((count + per_block - 1) / per_block)), block(RESCUE_THREADS);
-    if (spread) hipLaunchKernelGGL(rescue_stree_level_spread_kernel, grid, block, 0, stream, nodes, pref, list, count, pstart, cstart, ccnt, empty[0], empty[1]);
-    else hipLaunchKernelGGL(rescue_stree_level_kernel, grid, block, 0, stream, nodes, pref, list, count, pstart, cstart, ccnt, empty[0], empty[1]);
+    if (spread) hipLaunchKernelGGL(rescue_stree_level_spread_kernel<K>, grid, block, 0, stream, nodes, pref, list, count, pstart, cstart, ccnt, empty[0], empty[1]);
+    else hipLaunchKernelGGL(rescue_stree_level_kernel<K>, grid, block, 0, stream, nodes, pref, list, count, pstart, cstart, ccnt, empty[0], empty[1]);
     return hipGetLastError() == hipSuccess ? 0 : -1;
+}
+int k_rescue_stree_level(hipStream_t stream, fe* nodes, const uint64_t* pref, const uint32_t* list, size_t count, size_t pstart, size_t cstart, size_t ccnt, const fe* empty) {
+    return rescue_stree_level(stream, nodes, pref, list, count, pstart, cstart, ccnt, empty);
+}
+int k_rescue_stree_level(hipStream_t stream, fe* nodes, const stree_wide* pref, const uint32_t* list, size_t count, size_t pstart, size_t cstart, size_t ccnt, const fe* empty) {
+    return rescue_stree_level(stream, nodes, pref, list, count, pstart, cstart, ccnt, empty);
 }
 int k_rescue_stree_carry(hipStream_t stream, fe* dst, const fe* src, const uint32_t* from, size_t count) {
     hipLaunchKernelGGL(rescue_stree_carry_kernel, dim3((unsigned)((2 * count + HASH_THREADS - 1) / HASH_THREADS)), dim3(HASH_THREADS), 0, stream, dst, src, from, count);
     return hipGetLastError() == hipSuccess ? 0 : -1;
 }
-int k_rescue_stree_open(hipStream_t stream, const fe* nodes, const uint64_t* pref, const uint64_t* levels, const fe* empties, const uint64_t* indices, fe* out, size_t count, uint32_t depth) {
+template <class K>
+static int rescue_stree_open(hipStream_t stream, const fe* nodes, const K* pref, const uint64_t* levels, const fe* empties, const K* indices, fe* out, size_t count, uint32_t depth) {
     const size_t lanes = 2 * count * (depth + 1);
-    hipLaunchKernelGGL(rescue_stree_open_kernel, dim3((unsigned)((lanes + HASH_THREADS - 1) / HASH_THREADS)), dim3(HASH_THREADS), 0, stream, nodes, pref, levels, empties, indices, out, count, depth);
+    hipLaunchKernelGGL(rescue_stree_open_kernel<K>, dim3((unsigned)((lanes + HASH_THREADS - 1) / HASH_THREADS)), dim3(HASH_THREADS), 0, stream, nodes, pref, levels, empties, indices, out, count, depth);
+    return hipGetLastError() == hipSuccess ? 0 : -1;
+}
+int k_rescue_stree_open(hipStream_t stream, const fe* nodes, const uint64_t* pref, const uint64_t* levels, const fe* empties, const uint64_t* indices, fe* out, size_t count, uint32_t depth) {
+    return rescue_stree_open(stream, nodes, pref, levels, empties, indices, out, count, depth);
+}
+int k_rescue_stree_open(hipStream_t stream, const fe* nodes, const stree_wide* pref, const uint64_t* levels, const fe* empties, const stree_wide* indices, fe* out, size_t count, uint32_t depth) {
+    return rescue_stree_open(stream, nodes, pref, levels, empties, indices, out, count, depth);
+}
+template <class K>
+static int rescue_stree_lookup(hipStream_t stream, const fe* nodes, const K* pref, const uint64_t* levels, const fe* empties, const K* prefix, const uint32_t* level, fe* out, size_t count) {
+    hipLaunchKernelGGL(rescue_stree_lookup_kernel<K>, dim3((unsigned)((2 * count + HASH_THREADS - 1) / HASH_THREADS)), dim3(HASH_THREADS), 0, stream, nodes, pref, levels, empties, prefix, level, out, count);
     return hipGetLastError() == hipSuccess ? 0 : -1;
 }
 int k_rescue_stree_lookup(hipStream_t stream, const fe* nodes, const uint64_t* pref, const uint64_t* levels, const fe* empties, const uint64_t* prefix, const uint32_t* level, fe* out, size_t count) {
-    hipLaunchKernelGGL(rescue_stree_lookup_kernel, dim3((unsigned)((2 * count + HASH_THREADS - 1) / HASH_THREADS)), dim3(HASH_THREADS), 0, stream, nodes, pref, levels, empties, prefix, level, out, count);
+    return rescue_stree_lookup(stream, nodes, pref, levels, empties, prefix, level, out, count);
+}
+int k_rescue_stree_lookup(hipStream_t stream, const fe* nodes, const stree_wide* pref, const uint64_t* levels, const fe* empties, const stree_wide* prefix, const uint32_t* level, fe* out, size_t count) {
+    return rescue_stree_lookup(stream, nodes, pref, levels, empties, prefix, level, out, count);
+}
+template <class K>
+static int rescue_stree_get(hipStream_t stream, const fe* nodes, const K* pref, size_t lstart, size_t lcnt, const fe* empty, const K* indices, fe* out, uint8_t* stored, size_t count) {
+    hipLaunchKernelGGL(rescue_stree_get_kernel<K>, dim3((unsigned)((count + HASH_THREADS - 1) / HASH_THREADS)), dim3(HASH_THREADS), 0, stream, nodes, pref, lstart, lcnt, empty[0], empty[1], indices, out, stored, count);
     return hipGetLastError() == hipSuccess ? 0 : -1;
 }
 int k_rescue_stree_get(hipStream_t stream, const fe* nodes, const uint64_t* pref, size_t lstart, size_t lcnt, const fe* empty, const uint64_t* indices, fe* out, uint8_t* stored, size_t count) {
-    hipLaunchKernelGGL(rescue_stree_get_kernel, dim3((unsigned)((count + HASH_THREADS - 1) / HASH_THREADS)), dim3(HASH_THREADS), 0, stream, nodes, pref, lstart, lcnt, empty[0], empty[1], indices, out, stored, count);
-    return hipGetLastError() == hipSuccess ? 0 : -1;
+    return rescue_stree_get(stream, nodes, pref, lstart, lcnt, empty, indices, out, stored, count);
+}
+int k_rescue_stree_get(hipStream_t stream, const fe* nodes, const stree_wide* pref, size_t lstart, size_t lcnt, const fe* empty, const stree_wide* indices, fe* out, uint8_t* stored, size_t count) {
+    return rescue_stree_get(stream, nodes, pref, lstart, lcnt, empty, indices, out, stored, count);
 }
 int k_rescue_stree_empty_leaves(hipStream_t stream, const fe* leaves, const fe* empty, uint8_t* flags, size_t count) {
     hipLaunchKernelGGL(rescue_stree_empty_leaves_kernel, dim3((unsigned)((count + HASH_THREADS - 1) / HASH_THREADS)), dim3(HASH_THREADS), 0, stream, leaves, empty[0], empty[1], flags, count);
@@ -625,7 +660,8 @@ int k_rescue_tree_scatter_from(hipStream_t stream, fe* nodes, const uint32_t* po
 // the six-lanes-of-eight form (rescue_parent_spread): lanes 5, 4 hold l0, l1 and lanes 3, 2 hold r0, r1.  After the permutation the digest sits in
 // lanes 5, 4; it reaches the side bit k - 1 of the index names through the group's LDS slots 5, 4, and the other side loads path[k].  A group past
 // the end is given chain 0, keeps the barriers and stores nothing.
-__global__ void __launch_bounds__(RESCUE_THREADS) rescue_path_root_spread_kernel(const fe* __restrict__ paths, uint32_t n, const uint64_t* __restrict__ indices, size_t count,
+template <class K>
+__global__ void __launch_bounds__(RESCUE_THREADS) rescue_path_root_spread_kernel(const fe* __restrict__ paths, uint32_t n, const K* __restrict__ indices, size_t count,
                                                                                 const fe* __restrict__ alt, uint32_t mode, size_t chains, fe* __restrict__ out, uint32_t* __restrict__ bad) {
     __shared__ fe xch[RESCUE_THREADS];
     const size_t g = (size_t)blockIdx.x * (RESCUE_THREADS / 8u) + (threadIdx.x >> 3);
@@ -636,10 +672,10 @@ __global__ void __launch_bounds__(RESCUE_THREADS) rescue_path_root_spread_kernel
     const bool works = e >= 2u && e < 6u;
     fe* const xs = xch + (threadIdx.x & ~7u);
     const fe* const path = paths + 2 * i * n;
-    const uint64_t idx = indices[i];
+    const K idx = indices[i];
     fe v = fe_zero();                                                  // state after hasher.rs:18: (0, 0, r1, r0, l1, l0)
     if (works) {
-        const bool right = idx & 1u;                                   // the leaf is the right child: the sibling goes first
+        const bool right = stree_bit(idx, 0u);                         // the leaf is the right child: the sibling goes first
         v = (e >= 4u) == right ? path[2 + elem] : sub ? alt[2 * i + elem] : path[elem];
         if (live && !rescue_canonical(v)) *bad = 1u;
     }
@@ -650,7 +686,7 @@ __global__ void __launch_bounds__(RESCUE_THREADS) rescue_path_root_spread_kernel
         __syncthreads();
         v = fe_zero();
         if (works) {
-            const bool right = (idx >> (k - 1u)) & 1u;
+            const bool right = stree_bit(idx, k - 1u);
             if ((e >= 4u) == right) {
                 v = path[2 * k + elem];
                 if (live && !rescue_canonical(v)) *bad = 1u;
@@ -663,34 +699,42 @@ __global__ void __launch_bounds__(RESCUE_THREADS) rescue_path_root_spread_kernel
 }
 // one chain per lane, for more chains than RESCUE_SPREAD_MAX: the digest is stated once, in a loop over the levels; only the running digest, the
 // index and the chain's base address live across it.  Lanes read their paths n * 32 bytes apart: a level is milliseconds of arithmetic.
-__global__ void __launch_bounds__(RESCUE_THREADS) rescue_path_root_kernel(const fe* __restrict__ paths, uint32_t n, const uint64_t* __restrict__ indices, size_t count,
+template <class K>
+__global__ void __launch_bounds__(RESCUE_THREADS) rescue_path_root_kernel(const fe* __restrict__ paths, uint32_t n, const K* __restrict__ indices, size_t count,
                                                                          const fe* __restrict__ alt, uint32_t mode, size_t chains, fe* __restrict__ out, uint32_t* __restrict__ bad) {
     const size_t c = (size_t)blockIdx.x * RESCUE_THREADS + threadIdx.x;
     if (c >= chains) return;
     const size_t i = c < count ? c : c - count;
     const fe* const path = paths + 2 * i * n;
     const fe* const leaf = (mode == RESCUE_PATH_ALT || c >= count) ? alt + 2 * i : path;
-    const uint64_t idx = indices[i];
+    const K idx = indices[i];
     fe d0 = leaf[0], d1 = leaf[1];
     if (!(rescue_canonical(d0) && rescue_canonical(d1))) *bad = 1u;
 #pragma unroll 1
     for (uint32_t k = 1; k < n; k++) {
         const fe s0 = path[2 * k], s1 = path[2 * k + 1];
         if (!(rescue_canonical(s0) && rescue_canonical(s1))) *bad = 1u;
-        const bool right = (idx >> (k - 1u)) & 1u;                     // the running node is the right child: the sibling goes first
+        const bool right = stree_bit(idx, k - 1u);                     // the running node is the right child: the sibling goes first
         const fe c0 = d0, c1 = d1;
         rescue_digest4(rescue_pick(right, s0, c0), rescue_pick(right, s1, c1), rescue_pick(right, c0, s0), rescue_pick(right, c1, s1), d0, d1);
     }
     out[2 * c] = d0; out[2 * c + 1] = d1;
 }
-int k_rescue_path_roots(hipStream_t stream, const fe* paths, uint32_t n, const uint64_t* indices, size_t count, const fe* alt_leaves, uint32_t mode, fe* out, uint32_t* bad) {
+template <class K>
+static int rescue_path_roots(hipStream_t stream, const fe* paths, uint32_t n, const K* indices, size_t count, const fe* alt_leaves, uint32_t mode, fe* out, uint32_t* bad) {
     const size_t chains = mode == RESCUE_PATH_BOTH ? 2 * count : count;
     const bool spread = chains <= RESCUE_SPREAD_MAX;
     const size_t per_block = spread ? RESCUE_THREADS / 8 : RESCUE_THREADS;
     const dim3 grid((unsigned)((chains + per_block - 1) / per_block)), block(RESCUE_THREADS);
-    if (spread) hipLaunchKernelGGL(rescue_path_root_spread_kernel, grid, block, 0, stream, paths, n, indices, count, alt_leaves, mode, chains, out, bad);
-    else hipLaunchKernelGGL(rescue_path_root_kernel, grid, block, 0, stream, paths, n, indices, count, alt_leaves, mode, chains, out, bad);
+    if (spread) hipLaunchKernelGGL(rescue_path_root_spread_kernel<K>, grid, block, 0, stream, paths, n, indices, count, alt_leaves, mode, chains, out, bad);
+    else hipLaunchKernelGGL(rescue_path_root_kernel<K>, grid, block, 0, stream, paths, n, indices, count, alt_leaves, mode, chains, out, bad);
     return hipGetLastError() == hipSuccess ? 0 : -1;
+}
+int k_rescue_path_roots(hipStream_t stream, const fe* paths, uint32_t n, const uint64_t* indices, size_t count, const fe* alt_leaves, uint32_t mode, fe* out, uint32_t* bad) {
+    return rescue_path_roots(stream, paths, n, indices, count, alt_leaves, mode, out, bad);
+}
+int k_rescue_path_roots(hipStream_t stream, const fe* paths, uint32_t n, const stree_wide* indices, size_t count, const fe* alt_leaves, uint32_t mode, fe* out, uint32_t* bad) {
+    return rescue_path_roots(stream, paths, n, indices, count, alt_leaves, mode, out, bad);
 }
 
 // ---- multiproofs (dst_rescue_multiproof_root, dst_rescue_verify_multiproof, dst_rescue_multiproof_paths; host/multiproof_plan.h): the leaves of a
@@ -768,7 +812,8 @@ __device__ __forceinline__ uint32_t rescue_stree_level_of(const uint64_t* __rest
     for (uint32_t k = 0; k < depth; k++) l += p < levels[2 * k] ? 1u : 0u;
     return l;
 }
-__global__ void __launch_bounds__(RESCUE_THREADS) rescue_stree_audit_kernel(const fe* __restrict__ nodes, const uint64_t* __restrict__ pref, const uint64_t* __restrict__ levels,
+template <class K>
+__global__ void __launch_bounds__(RESCUE_THREADS) rescue_stree_audit_kernel(const fe* __restrict__ nodes, const K* __restrict__ pref, const uint64_t* __restrict__ levels,
                                                                            const fe* __restrict__ empties, uint32_t depth, size_t first, size_t count,
                                                                            unsigned long long* __restrict__ first_bad) {
     const size_t g = (size_t)blockIdx.x * RESCUE_THREADS + threadIdx.x;
@@ -787,7 +832,8 @@ __global__ void __launch_bounds__(RESCUE_THREADS) rescue_stree_audit_kernel(cons
 }
 // the six-lanes-of-eight form (rescue_stree_level_spread_kernel): lanes 5, 4 hold l0, l1 and lanes 3, 2 hold r0, r1; a group past the end is
 // given the first parent, keeps the barriers and reports nothing
-__global__ void __launch_bounds__(RESCUE_THREADS) rescue_stree_audit_spread_kernel(const fe* __restrict__ nodes, const uint64_t* __restrict__ pref, const uint64_t* __restrict__ levels,
+template <class K>
+__global__ void __launch_bounds__(RESCUE_THREADS) rescue_stree_audit_spread_kernel(const fe* __restrict__ nodes, const K* __restrict__ pref, const uint64_t* __restrict__ levels,
                                                                                   const fe* __restrict__ empties, uint32_t depth, size_t first, size_t count,
                                                                                   unsigned long long* __restrict__ first_bad) {
     __shared__ fe xch[RESCUE_THREADS];
@@ -818,12 +864,21 @@ int k_rescue_tree_audit(hipStream_t stream, const fe* nodes, size_t leaves, unsi
     else hipLaunchKernelGGL(rescue_tree_audit_kernel, grid, block, 0, stream, nodes, leaves, first_bad);
     return hipGetLastError() == hipSuccess ? 0 : -1;
 }
-int k_rescue_stree_audit(hipStream_t stream, const fe* nodes, const uint64_t* pref, const uint64_t* levels, const fe* empties, uint32_t depth, size_t first, size_t count,
-                         unsigned long long* first_bad) {
+template <class K>
+static int rescue_stree_audit(hipStream_t stream, const fe* nodes, const K* pref, const uint64_t* levels, const fe* empties, uint32_t depth, size_t first, size_t count,
+                              unsigned long long* first_bad) {
     const bool spread = count <= RESCUE_SPREAD_MAX;
     const size_t per_block = spread ? RESCUE_THREADS / 8 : RESCUE_THREADS;
     const dim3 grid((unsigned)((count + per_block - 1) / per_block)), block(RESCUE_THREADS);
-    if (spread) hipLaunchKernelGGL(rescue_stree_audit_spread_kernel, grid, block, 0, stream, nodes, pref, levels, empties, depth, first, count, first_bad);
-    else hipLaunchKernelGGL(rescue_stree_audit_kernel, grid, block, 0, stream, nodes, pref, levels, empties, depth, first, count, first_bad);
+    if (spread) hipLaunchKernelGGL(rescue_stree_audit_spread_kernel<K>, grid, block, 0, stream, nodes, pref, levels, empties, depth, first, count, first_bad);
+    else hipLaunchKernelGGL(rescue_stree_audit_kernel<K>, grid, block, 0, stream, nodes, pref, levels, empties, depth, first, count, first_bad);
     return hipGetLastError() == hipSuccess ? 0 : -1;
+}
+int k_rescue_stree_audit(hipStream_t stream, const fe* nodes, const uint64_t* pref, const uint64_t* levels, const fe* empties, uint32_t depth, size_t first, size_t count,
+                         unsigned long long* first_bad) {
+    return rescue_stree_audit(stream, nodes, pref, levels, empties, depth, first, count, first_bad);
+}
+int k_rescue_stree_audit(hipStream_t stream, const fe* nodes, const stree_wide* pref, const uint64_t* levels, const fe* empties, uint32_t depth, size_t first, size_t count,
+                         unsigned long long* first_bad) {
+    return rescue_stree_audit(stream, nodes, pref, levels, empties, depth, first, count, first_bad);
 }

@@ -64,7 +64,10 @@ EXPORTS = ["dst_ctx_create", "dst_ctx_destroy", "dst_last_error", "dst_phase_ms"
            "dst_stree_remove", "dst_stree_compact", "dst_stree_get",
            "dst_rescue_multiproof_size", "dst_rtree_multiproof", "dst_stree_multiproof", "dst_rescue_multiproof_root", "dst_rescue_verify_multiproof",
            "dst_rescue_multiproof_paths",
-           "dst_rtree_save", "dst_rtree_load", "dst_rtree_audit", "dst_stree_save", "dst_stree_load", "dst_stree_audit"]
+           "dst_rtree_save", "dst_rtree_load", "dst_rtree_audit", "dst_stree_save", "dst_stree_load", "dst_stree_audit",
+           "dst_wtree_create", "dst_wtree_set", "dst_wtree_remove", "dst_wtree_compact", "dst_wtree_get", "dst_wtree_root", "dst_wtree_paths", "dst_wtree_apply",
+           "dst_wtree_tapes_many", "dst_wtree_read_level", "dst_wtree_info", "dst_wtree_audit", "dst_wtree_destroy", "dst_wtree_last_error", "dst_wtree_test_set_node",
+           "dst_rescue_path_roots_w", "dst_rescue_verify_paths_w", "dst_rescue_verify_writes_w", "dst_rescue_path_tapes_w"]
 
 
 class DistaffError(RuntimeError):
@@ -290,20 +293,42 @@ def rescue_digest(values, device=0, lib=None):
     return out
 
 
-def path_tapes(paths, indices, what=3, lib=None):
+def _wide_keys(indices):
+    """16-byte little-endian keys from Python ints, or uint64 words [count, 2] (low half first) as they are -> (uint64 words [count, 2], pointer
+    or None); an int outside 0 .. 2^128 - 1 cannot be a key"""
+    if isinstance(indices, np.ndarray) and indices.dtype == np.uint64 and indices.ndim == 2 and indices.shape[1] == 2:
+        idx = np.ascontiguousarray(indices)
+        return idx, (_ptr(idx) if idx.shape[0] else None)
+    vals = [int(i) for i in indices]
+    if any(v < 0 or v >> 128 for v in vals):
+        raise DistaffError(DST_ERR_ARG, "a key is an integer in 0 .. 2^128 - 1")
+    idx = ints_to_arr(vals)
+    return idx, (_ptr(idx) if len(vals) else None)
+
+
+class _Keys:
+    """the indices of a call without a tree: 8-byte words for the dst_rescue_* calls, 16-byte words for their _w forms (suffix)"""
+    def __init__(self, indices, wide):
+        self.arr, self.ptr = _wide_keys(indices) if wide else RescueTree._indices(indices)
+        self.size = self.arr.shape[0]
+        self.suffix = "_w" if wide else ""
+
+
+def path_tapes(paths, indices, what=3, lib=None, _wide=False):
     """RescueTree.tapes_many over paths the caller holds (dst_rescue_path_tapes; host only, no tree): `paths` as paths() or apply() return them
     -- a list with one list of n pairs of ints per index -- or uint64 words [count, n, 2, 2] -> a list of (A, B)"""
     lib = lib or load()
-    idx, ip = RescueTree._indices(indices)
+    idx = _Keys(indices, _wide)
+    ip, call = idx.ptr, getattr(lib, "dst_rescue_path_tapes" + idx.suffix)
     w, n_nodes = _path_words(paths, idx.size)
     nodes = ctypes.c_uint32(n_nodes)
     n = ctypes.c_size_t(0)
-    r = lib.dst_rescue_path_tapes(_ptr(w) if idx.size else None, nodes, ip, ctypes.c_size_t(idx.size), ctypes.c_uint32(what), None, None, ctypes.c_size_t(0), ctypes.byref(n))
+    r = call(_ptr(w) if idx.size else None, nodes, ip, ctypes.c_size_t(idx.size), ctypes.c_uint32(what), None, None, ctypes.c_size_t(0), ctypes.byref(n))
     if r == DST_OK:
         each = n.value
         a = np.zeros((max(idx.size * each, 1), 2), dtype=np.uint64)
         b = np.zeros((max(idx.size * each, 1), 2), dtype=np.uint64)
-        r = lib.dst_rescue_path_tapes(_ptr(w) if idx.size else None, nodes, ip, ctypes.c_size_t(idx.size), ctypes.c_uint32(what), _ptr(a), _ptr(b), ctypes.c_size_t(each), ctypes.byref(n))
+        r = call(_ptr(w) if idx.size else None, nodes, ip, ctypes.c_size_t(idx.size), ctypes.c_uint32(what), _ptr(a), _ptr(b), ctypes.c_size_t(each), ctypes.byref(n))
     if r != DST_OK:
         raise DistaffError(r, _rtree_error(lib) or "dst_rescue_path_tapes failed")
     va, vb = arr_to_ints(a[:idx.size * each]), arr_to_ints(b[:idx.size * each])
@@ -340,17 +365,18 @@ def _pairs(words):
     return [(v[2 * i], v[2 * i + 1]) for i in range(len(v) // 2)]
 
 
-def path_roots(paths, indices, leaves=None, device=0, lib=None, stats=None):
+def path_roots(paths, indices, leaves=None, device=0, lib=None, stats=None, _wide=False):
     """compute_merkle_root (src/examples/merkle.rs:112-145) of every path with its index (dst_rescue_path_roots) -> a list of pairs of ints: what
     path i resolves to, or with `leaves` what it resolves to with leaves[i] as its first node.  `paths` as path_tapes takes them, what paths()
     and apply() return included.  device >= 0: one launch on that GPU for all paths; device < 0: on the host.  stats (a dict) receives device_ms."""
     lib = lib or load()
-    idx, ip = RescueTree._indices(indices)
+    idx = _Keys(indices, _wide)
+    ip = idx.ptr
     w, n = _path_words(paths, idx.size)
     alt = _nodes_for(leaves, idx.size, "leaves") if leaves is not None else None
     out = np.zeros((max(idx.size, 1), 2, 2), dtype=np.uint64)
     ms = ctypes.c_double(0)
-    r = lib.dst_rescue_path_roots(ctypes.c_int(device), _ptr(w) if idx.size else None, ctypes.c_uint32(n), ip, ctypes.c_size_t(idx.size),
+    r = getattr(lib, "dst_rescue_path_roots" + idx.suffix)(ctypes.c_int(device), _ptr(w) if idx.size else None, ctypes.c_uint32(n), ip, ctypes.c_size_t(idx.size),
                                   _ptr(alt) if alt is not None and idx.size else None, _ptr(out), ctypes.byref(ms))
     if r != DST_OK:
         raise DistaffError(r, _rtree_error(lib) or "dst_rescue_path_roots failed")
@@ -359,17 +385,18 @@ def path_roots(paths, indices, leaves=None, device=0, lib=None, stats=None):
     return _pairs(out[:idx.size])
 
 
-def verify_paths(root, paths, indices, leaves=None, device=0, lib=None, stats=None):
+def verify_paths(root, paths, indices, leaves=None, device=0, lib=None, stats=None, _wide=False):
     """membership / absence (dst_rescue_verify_paths) -> (first_bad, why): (-1, DST_PATH_OK) when every path resolves to `root` and, with
     `leaves`, has leaves[i] as its first node (the empty leaf of a sparse tree: the key is absent); else the lowest failing i and DST_PATH_BAD_LEAF
     or DST_PATH_BAD_ROOT.  A path that does not verify is a result, not an exception."""
     lib = lib or load()
-    idx, ip = RescueTree._indices(indices)
+    idx = _Keys(indices, _wide)
+    ip = idx.ptr
     w, n = _path_words(paths, idx.size)
     want = _nodes_for(leaves, idx.size, "leaves") if leaves is not None else None
     r0 = _nodes_for([tuple(root)], 1, "roots")
     first, why, ms = ctypes.c_int64(-1), ctypes.c_uint32(0), ctypes.c_double(0)
-    r = lib.dst_rescue_verify_paths(ctypes.c_int(device), _ptr(r0), _ptr(w) if idx.size else None, ctypes.c_uint32(n), ip,
+    r = getattr(lib, "dst_rescue_verify_paths" + idx.suffix)(ctypes.c_int(device), _ptr(r0), _ptr(w) if idx.size else None, ctypes.c_uint32(n), ip,
                                     _ptr(want) if want is not None and idx.size else None, ctypes.c_size_t(idx.size), ctypes.byref(first), ctypes.byref(why), ctypes.byref(ms))
     if r != DST_OK:
         raise DistaffError(r, _rtree_error(lib) or "dst_rescue_verify_paths failed")
@@ -378,20 +405,21 @@ def verify_paths(root, paths, indices, leaves=None, device=0, lib=None, stats=No
     return first.value, why.value
 
 
-def verify_writes(root_before, indices, paths, leaves, roots=None, device=0, lib=None, stats=None):
+def verify_writes(root_before, indices, paths, leaves, roots=None, device=0, lib=None, stats=None, _wide=False):
     """the checker of RescueTree.apply / SparseRescueTree.apply (dst_rescue_verify_writes) -> (first_bad, why, root_after): write i holds when
     paths[i] resolves to the root before it (root_before, then the root after write i - 1 as computed here) and, with `roots`, resolves to roots[i]
     with leaves[i] as its first node.  (-1, DST_PATH_OK, the root after the last write) when all hold.  Without `roots` a wrong new leaf shows one
     write later (DST_PATH_BAD_ROOT), in the last write only in root_after.  On a device all 2 * count chains run in one launch."""
     lib = lib or load()
-    idx, ip = RescueTree._indices(indices)
+    idx = _Keys(indices, _wide)
+    ip = idx.ptr
     w, n = _path_words(paths, idx.size)
     new = _nodes_for(leaves, idx.size, "leaves")
     claimed = _nodes_for(roots, idx.size, "roots") if roots is not None else None
     r0 = _nodes_for([tuple(root_before)], 1, "roots")
     after = np.zeros((2, 2), dtype=np.uint64)
     first, why, ms = ctypes.c_int64(-1), ctypes.c_uint32(0), ctypes.c_double(0)
-    r = lib.dst_rescue_verify_writes(ctypes.c_int(device), _ptr(r0), _ptr(w) if idx.size else None, ctypes.c_uint32(n), ip, _ptr(new) if idx.size else None,
+    r = getattr(lib, "dst_rescue_verify_writes" + idx.suffix)(ctypes.c_int(device), _ptr(r0), _ptr(w) if idx.size else None, ctypes.c_uint32(n), ip, _ptr(new) if idx.size else None,
                                      _ptr(claimed) if claimed is not None and idx.size else None, ctypes.c_size_t(idx.size), ctypes.byref(first), ctypes.byref(why), _ptr(after),
                                      ctypes.byref(ms))
     if r != DST_OK:
@@ -399,6 +427,26 @@ def verify_writes(root_before, indices, paths, leaves, roots=None, device=0, lib
     if stats is not None:
         stats["device_ms"] = ms.value
     return first.value, why.value, tuple(arr_to_ints(after))
+
+
+def path_tapes_wide(paths, indices, what=3, lib=None):
+    """path_tapes for paths of up to 128 nodes and indices of up to 127 bits, Python ints (dst_rescue_path_tapes_w)"""
+    return path_tapes(paths, indices, what, lib, _wide=True)
+
+
+def path_roots_wide(paths, indices, leaves=None, device=0, lib=None, stats=None):
+    """path_roots for paths of up to 128 nodes and indices of up to 127 bits, Python ints (dst_rescue_path_roots_w)"""
+    return path_roots(paths, indices, leaves, device, lib, stats, _wide=True)
+
+
+def verify_paths_wide(root, paths, indices, leaves=None, device=0, lib=None, stats=None):
+    """verify_paths for paths of up to 128 nodes and indices of up to 127 bits, Python ints (dst_rescue_verify_paths_w)"""
+    return verify_paths(root, paths, indices, leaves, device, lib, stats, _wide=True)
+
+
+def verify_writes_wide(root_before, indices, paths, leaves, roots=None, device=0, lib=None, stats=None):
+    """verify_writes for WideSparseRescueTree.apply: paths of up to 128 nodes, indices of up to 127 bits (dst_rescue_verify_writes_w)"""
+    return verify_writes(root_before, indices, paths, leaves, roots, device, lib, stats, _wide=True)
 
 
 def multiproof_size(n, indices, lib=None):
@@ -507,15 +555,16 @@ def _tree_load(lib, call, error, blob, device, audit):
 
 def _apply(tree, call, n, indices, leaves):
     """(paths, roots) of an ordered batch of writes: paths in the shape paths() returns, roots a list of pairs of ints"""
-    idx, ip = RescueTree._indices(indices)
+    idx, ip = getattr(tree, "_keys", RescueTree._indices)(indices)
     a = _elements(leaves, 2)
-    if a.shape[0] != idx.size:
+    count = idx.shape[0]
+    if a.shape[0] != count:
         raise DistaffError(DST_ERR_ARG, "as many leaves as indices")
-    paths = np.zeros((max(idx.size, 1) * n, 2, 2), dtype=np.uint64)
-    roots = np.zeros((max(idx.size, 1), 2, 2), dtype=np.uint64)
-    tree._check(call(tree._h, ip, _ptr(a) if idx.size else None, ctypes.c_size_t(idx.size), _ptr(paths), _ptr(roots)))
-    v, r = arr_to_ints(paths[:idx.size * n]), arr_to_ints(roots[:idx.size])
-    return ([[(v[2 * (i * n + k)], v[2 * (i * n + k) + 1]) for k in range(n)] for i in range(idx.size)], [(r[2 * i], r[2 * i + 1]) for i in range(idx.size)])
+    paths = np.zeros((max(count, 1) * n, 2, 2), dtype=np.uint64)
+    roots = np.zeros((max(count, 1), 2, 2), dtype=np.uint64)
+    tree._check(call(tree._h, ip, _ptr(a) if count else None, ctypes.c_size_t(count), _ptr(paths), _ptr(roots)))
+    v, r = arr_to_ints(paths[:count * n]), arr_to_ints(roots[:count])
+    return ([[(v[2 * (i * n + k)], v[2 * (i * n + k) + 1]) for k in range(n)] for i in range(count)], [(r[2 * i], r[2 * i + 1]) for i in range(count)])
 
 
 class RescueTree:
@@ -672,25 +721,36 @@ class StreeInfo(ctypes.Structure):
                 ("last_digests", ctypes.c_uint64), ("last_device_ms", ctypes.c_double)]
 
 
-class SparseRescueTree:
-    """A sparse Rescue Merkle tree (``dst_stree``): the dense RescueTree over 2^depth leaves, 1 <= depth <= 63, in which every leaf that was
-    never set holds `empty_leaf`; only the nodes above set leaves are stored.  Same roots, same paths (depth + 1 nodes), same tapes.
-    device >= 0 keeps it on that GPU; device < 0 on the host."""
+class _SparseTree:
+    """What SparseRescueTree (dst_stree_*, 8-byte keys) and WideSparseRescueTree (dst_wtree_*, 16-byte keys) share: every call the two handles
+    have in common, stated once.  _PREFIX names the entry points, _keys packs the keys of a call, _prefixes / _as_key read keys back."""
+    _PREFIX = None
+
+    def _fn(self, name):
+        return getattr(self.lib, self._PREFIX + name)
+
+    @staticmethod
+    def _keys(indices):
+        return RescueTree._indices(indices)
+
+    @staticmethod
+    def _prefixes(m):
+        return np.zeros(m, dtype=np.uint64)
 
     def __init__(self, depth, empty_leaf=(0, 0), device=0, lib=None):
         self.lib = lib or load()
         self.depth = int(depth)
         e = _elements([tuple(empty_leaf)], 2)
         h = ctypes.c_void_p()
-        r = self.lib.dst_stree_create(ctypes.c_int(device), ctypes.c_uint32(self.depth), _ptr(e), ctypes.byref(h))
+        r = self._fn("create")(ctypes.c_int(device), ctypes.c_uint32(self.depth), _ptr(e), ctypes.byref(h))
         if r != DST_OK:
             raise DistaffError(r, self._error(None))
         self._h = h
 
     def _error(self, handle):
-        self.lib.dst_stree_last_error.restype = ctypes.c_char_p
-        self.lib.dst_stree_last_error.argtypes = [ctypes.c_void_p]
-        return (self.lib.dst_stree_last_error(handle) or b"").decode()
+        self._fn("last_error").restype = ctypes.c_char_p
+        self._fn("last_error").argtypes = [ctypes.c_void_p]
+        return (self._fn("last_error")(handle) or b"").decode()
 
     def _check(self, r):
         if r != DST_OK:
@@ -698,8 +758,8 @@ class SparseRescueTree:
 
     def close(self):
         if getattr(self, "_h", None):
-            self.lib.dst_stree_destroy.restype = None
-            self.lib.dst_stree_destroy(self._h)
+            self._fn("destroy").restype = None
+            self._fn("destroy")(self._h)
             self._h = None
 
     def __del__(self):
@@ -709,24 +769,24 @@ class SparseRescueTree:
         """inserts or replaces the leaves at the distinct keys `indices` (any order; `leaves`: as many pairs of ints, or uint64 words
         [count, 2, 2]) and hashes exactly their ancestors (dst_stree_set).  A repeated key, a key past 2^depth or an element not below p
         raises DistaffError(DST_ERR_ARG) and leaves the tree as it was."""
-        idx, ip = RescueTree._indices(indices)
+        idx, ip = self._keys(indices)
         a = _elements(leaves, 2)
-        if a.shape[0] != idx.size:
+        if a.shape[0] != idx.shape[0]:
             raise DistaffError(DST_ERR_ARG, "as many leaves as indices")
-        self._check(self.lib.dst_stree_set(self._h, ip, _ptr(a) if idx.size else None, ctypes.c_size_t(idx.size)))
+        self._check(self._fn("set")(self._h, ip, _ptr(a) if idx.shape[0] else None, ctypes.c_size_t(idx.shape[0])))
 
     def apply(self, indices, leaves):
         """RescueTree.apply on keys below 2^depth, stored or not (dst_stree_apply) -> (paths, roots); the old leaf of a key that is not stored is
         the empty leaf.  Afterwards the tree is set()'s of the distinct keys with the later value of each."""
-        return _apply(self, self.lib.dst_stree_apply, self.depth + 1, indices, leaves)
+        return _apply(self, self._fn("apply"), self.depth + 1, indices, leaves)
 
     def remove(self, indices):
         """deletes the stored keys among the distinct keys `indices` (any order) and every node left without a key below it
         (dst_stree_remove) -> how many were stored.  The tree then equals a fresh one set with the remaining keys; only the surviving
         ancestors of the removed keys are hashed.  A repeated key or a key past 2^depth raises DistaffError(DST_ERR_ARG)."""
-        idx, ip = RescueTree._indices(indices)
+        idx, ip = self._keys(indices)
         n = ctypes.c_uint64(0)
-        self._check(self.lib.dst_stree_remove(self._h, ip, ctypes.c_size_t(idx.size), ctypes.byref(n)))
+        self._check(self._fn("remove")(self._h, ip, ctypes.c_size_t(idx.shape[0]), ctypes.byref(n)))
         return n.value
 
     def compact(self):
@@ -734,15 +794,15 @@ class SparseRescueTree:
         keys.  The root and the remaining nodes do not change and nothing is hashed.  apply(keys, empty leaves) + compact() is a removal
         with a witness per key."""
         n = ctypes.c_uint64(0)
-        self._check(self.lib.dst_stree_compact(self._h, ctypes.byref(n)))
+        self._check(self._fn("compact")(self._h, ctypes.byref(n)))
         return n.value
 
     def get_words(self, indices):
         """get() as (leaves: uint64 words [count, 2, 2], stored: uint8 [count])"""
-        idx, ip = RescueTree._indices(indices)
-        out = np.zeros((idx.size, 2, 2), dtype=np.uint64)
-        stored = np.zeros(idx.size, dtype=np.uint8)
-        self._check(self.lib.dst_stree_get(self._h, ip, ctypes.c_size_t(idx.size), _ptr(out) if idx.size else None, _ptr(stored) if idx.size else None))
+        idx, ip = self._keys(indices)
+        out = np.zeros((idx.shape[0], 2, 2), dtype=np.uint64)
+        stored = np.zeros(idx.shape[0], dtype=np.uint8)
+        self._check(self._fn("get")(self._h, ip, ctypes.c_size_t(idx.shape[0]), _ptr(out) if idx.shape[0] else None, _ptr(stored) if idx.shape[0] else None))
         return out, stored
 
     def get(self, indices):
@@ -756,15 +816,15 @@ class SparseRescueTree:
     def root(self):
         """(r0, r1)"""
         out = np.zeros((2, 2), dtype=np.uint64)
-        self._check(self.lib.dst_stree_root(self._h, _ptr(out)))
+        self._check(self._fn("root")(self._h, _ptr(out)))
         return tuple(arr_to_ints(out))
 
     def paths_words(self, indices):
         """paths() as uint64 words [count, depth + 1, 2, 2]"""
-        idx, ip = RescueTree._indices(indices)
+        idx, ip = self._keys(indices)
         n = self.depth + 1
-        out = np.zeros((idx.size, n, 2, 2), dtype=np.uint64)
-        self._check(self.lib.dst_stree_paths(self._h, ip, ctypes.c_size_t(idx.size), _ptr(out) if idx.size else None))
+        out = np.zeros((idx.shape[0], n, 2, 2), dtype=np.uint64)
+        self._check(self._fn("paths")(self._h, ip, ctypes.c_size_t(idx.shape[0]), _ptr(out) if idx.shape[0] else None))
         return out
 
     def paths(self, indices):
@@ -778,22 +838,17 @@ class SparseRescueTree:
     def path(self, index):
         return self.paths([index])[0]
 
-    def multiproof(self, indices, words=False):
-        """RescueTree.multiproof with n = depth + 1 for distinct keys, stored or not (dst_stree_multiproof) -> (leaves, nodes); a leaf or a
-        sibling that is not stored is the empty subtree of its level, so absent keys are proven by the same call"""
-        return _tree_multiproof(self, self.lib.dst_stree_multiproof, indices, words)
-
     def tapes_many(self, indices, what=3):
         """RescueTree.tapes_many with n = depth + 1 (dst_stree_tapes_many): a list of (A, B)"""
-        idx, ip = RescueTree._indices(indices)
+        idx, ip = self._keys(indices)
         n = ctypes.c_size_t(0)
-        self._check(self.lib.dst_stree_tapes_many(self._h, ip, ctypes.c_size_t(idx.size), ctypes.c_uint32(what), None, None, ctypes.c_size_t(0), ctypes.byref(n)))
+        self._check(self._fn("tapes_many")(self._h, ip, ctypes.c_size_t(idx.shape[0]), ctypes.c_uint32(what), None, None, ctypes.c_size_t(0), ctypes.byref(n)))
         each = n.value
-        a = np.zeros((max(idx.size * each, 1), 2), dtype=np.uint64)
-        b = np.zeros((max(idx.size * each, 1), 2), dtype=np.uint64)
-        self._check(self.lib.dst_stree_tapes_many(self._h, ip, ctypes.c_size_t(idx.size), ctypes.c_uint32(what), _ptr(a), _ptr(b), ctypes.c_size_t(each), ctypes.byref(n)))
-        va, vb = arr_to_ints(a[:idx.size * each]), arr_to_ints(b[:idx.size * each])
-        return [(va[i * each:(i + 1) * each], vb[i * each:(i + 1) * each]) for i in range(idx.size)]
+        a = np.zeros((max(idx.shape[0] * each, 1), 2), dtype=np.uint64)
+        b = np.zeros((max(idx.shape[0] * each, 1), 2), dtype=np.uint64)
+        self._check(self._fn("tapes_many")(self._h, ip, ctypes.c_size_t(idx.shape[0]), ctypes.c_uint32(what), _ptr(a), _ptr(b), ctypes.c_size_t(each), ctypes.byref(n)))
+        va, vb = arr_to_ints(a[:idx.shape[0] * each]), arr_to_ints(b[:idx.shape[0] * each])
+        return [(va[i * each:(i + 1) * each], vb[i * each:(i + 1) * each]) for i in range(idx.shape[0])]
 
     def tapes(self, index, what=3):
         return self.tapes_many([index], what)[0]
@@ -801,18 +856,43 @@ class SparseRescueTree:
     def level(self, l):
         """level l's sorted list (dst_stree_read_level): (prefixes uint64 [m], nodes uint64 words [m, 2, 2]); level depth = the leaves, 0 = the root"""
         m = ctypes.c_uint64(0)
-        self._check(self.lib.dst_stree_read_level(self._h, ctypes.c_uint32(l), ctypes.c_uint64(0), ctypes.c_uint64(0), None, None, ctypes.byref(m)))
-        prefixes = np.zeros(m.value, dtype=np.uint64)
+        self._check(self._fn("read_level")(self._h, ctypes.c_uint32(l), ctypes.c_uint64(0), ctypes.c_uint64(0), None, None, ctypes.byref(m)))
+        prefixes = self._prefixes(m.value)
         nodes = np.zeros((m.value, 2, 2), dtype=np.uint64)
         if m.value:
-            self._check(self.lib.dst_stree_read_level(self._h, ctypes.c_uint32(l), ctypes.c_uint64(0), ctypes.c_uint64(m.value), _ptr(prefixes), _ptr(nodes), ctypes.byref(m)))
+            self._check(self._fn("read_level")(self._h, ctypes.c_uint32(l), ctypes.c_uint64(0), ctypes.c_uint64(m.value), _ptr(prefixes), _ptr(nodes), ctypes.byref(m)))
         return prefixes, nodes
 
     def info(self):
         """dst_stree_info: depth, device, keys, nodes, last_digests, last_device_ms"""
         i = StreeInfo()
-        self._check(self.lib.dst_stree_info(self._h, ctypes.byref(i)))
+        self._check(self._fn("info")(self._h, ctypes.byref(i)))
         return {f: getattr(i, f) for f, _ in StreeInfo._fields_}
+
+    def audit(self):
+        """None when every stored parent is the digest of its two children (one that is not stored counts as the empty subtree of its
+        level), else (level, prefix) of the bad parent nearest the root, the lowest prefix within its level (dst_stree_audit).  One launch on a
+        device tree; audit_ms then holds its device milliseconds.  The tree is unchanged."""
+        level, prefix, ms = ctypes.c_int32(0), self._prefixes(1), ctypes.c_double(0)
+        self._check(self._fn("audit")(self._h, ctypes.byref(level), _ptr(prefix), ctypes.byref(ms)))
+        self.audit_ms = ms.value
+        return None if level.value < 0 else (level.value, self._as_key(prefix[0]))
+
+    @staticmethod
+    def _as_key(word):
+        return int(word)
+
+
+class SparseRescueTree(_SparseTree):
+    """A sparse Rescue Merkle tree (``dst_stree``): the dense RescueTree over 2^depth leaves, 1 <= depth <= 63, in which every leaf that was
+    never set holds `empty_leaf`; only the nodes above set leaves are stored.  Same roots, same paths (depth + 1 nodes), same tapes.
+    device >= 0 keeps it on that GPU; device < 0 on the host."""
+    _PREFIX = "dst_stree_"
+
+    def multiproof(self, indices, words=False):
+        """RescueTree.multiproof with n = depth + 1 for distinct keys, stored or not (dst_stree_multiproof) -> (leaves, nodes); a leaf or a
+        sibling that is not stored is the empty subtree of its level, so absent keys are proven by the same call"""
+        return _tree_multiproof(self, self.lib.dst_stree_multiproof, indices, words)
 
     def save(self):
         """the tree as bytes (dst_stree_save): a 64-byte header, the level lengths, every level's prefixes, every level's nodes, the leaf level
@@ -830,14 +910,30 @@ class SparseRescueTree:
         t.depth = t.info()["depth"]
         return t
 
-    def audit(self):
-        """None when every stored parent is the digest of its two children (one that is not stored counts as the empty subtree of its
-        level), else (level, prefix) of the bad parent nearest the root, the lowest prefix within its level (dst_stree_audit).  One launch on a
-        device tree; audit_ms then holds its device milliseconds.  The tree is unchanged."""
-        level, prefix, ms = ctypes.c_int32(0), ctypes.c_uint64(0), ctypes.c_double(0)
-        self._check(self.lib.dst_stree_audit(self._h, ctypes.byref(level), ctypes.byref(prefix), ctypes.byref(ms)))
-        self.audit_ms = ms.value
-        return None if level.value < 0 else (level.value, prefix.value)
+
+class WideSparseRescueTree(_SparseTree):
+    """A sparse Rescue Merkle tree over keys of up to 127 bits (``dst_wtree``), 1 <= depth <= 127: the tree SparseRescueTree is, for keys that
+    are hashes.  Keys are Python ints; level() returns its prefixes as uint64 words [m, 2] (low half first; arr_to_ints turns them into
+    ints) and audit() names a prefix as an int.  Multiproofs and save / load are not available for wide trees yet."""
+    _PREFIX = "dst_wtree_"
+
+    @staticmethod
+    def _keys(indices):
+        return _wide_keys(indices)
+
+    @staticmethod
+    def _prefixes(m):
+        return np.zeros((m, 2), dtype=np.uint64)
+
+    @staticmethod
+    def _as_key(word):
+        return arr_to_ints(word)[0]
+
+    def test_set_node(self, level, index, node):
+        """overwrites entry `index` of level `level`'s node list with the pair `node`, hashing nothing (dst_wtree_test_set_node; the test build
+        of the library only): what an audit is then to find"""
+        w = _elements([tuple(node)], 2)
+        self._check(self.lib.dst_wtree_test_set_node(self._h, ctypes.c_uint32(level), ctypes.c_uint64(index), _ptr(w)))
 
 
 class Comm:

@@ -390,6 +390,61 @@ DST_API int dst_stree_audit(const dst_stree* t, int32_t* bad_level, uint64_t* ba
 DST_API void dst_stree_destroy(dst_stree* t);
 DST_API const char* dst_stree_last_error(const dst_stree* t);     /* t may be NULL: the error of the calling thread's last failed dst_stree_create / dst_stree_load */
 
+/* ---- wide-key sparse Rescue Merkle trees: keys of up to 127 bits, depth up to 127 --------------------------------------------------------------
+ * The keys of accounts, notes and nullifiers are hashes.  Cut down to the 63 bits of a dst_stree key, two of them collide after about 2^31.5
+ * insertions; at 127 bits the birthday bound is 2^63.  A dst_wtree is the sparse tree above with 16-byte keys and 1 <= depth <= 127: the same
+ * definition (the dense tree over 2^depth leaves with the empty leaf wherever nothing was set), the same parents, the same E_l, the same path
+ * layout [leaf, sibling, uncle, ...], the same tapes, so smpath.n / pmpath.n with n = depth + 1 <= 128 authenticate it.
+ * WHY 127 AND NOT 255: pmpath rebuilds the index with binacc into ONE field element, so every index must stay below p, and 2^127 < p =
+ * 2^128 - 45 * 2^40 + 1 holds where 2^128 does not; up to depth 127 both smpath and pmpath authenticate the tree, and index + 2^(n-1), the tape
+ * rule (merkle.rs:68), still fits in 128 bits.
+ * A KEY, an index or a prefix is 16 bytes, a little-endian integer: the memory image of a u128 and the layout of a field element, at any
+ * alignment.  A key must be below 2^depth as a whole -- one that violates this only in its high 8 bytes is refused -- and "repeated" compares
+ * all 128 bits: two keys with equal low halves and different high halves are two keys.
+ * THE LIMIT ON STORED NODES stays 2^32 - 2 (2^31 - 2 for dst_wtree_apply on a device tree), because flat positions are 32 bits; a random
+ * 127-bit key stores about 110 nodes of its own, so a tree holds some 3.9e7 such keys.
+ * Each call has the semantics, the argument checks (DST_ERR_ARG, found on the host before anything is queued, the tree unchanged), the host
+ * path for device < 0, the launch count per call, the last_digests and last_device_ms, and the rule that a HIP error inside a call that changes
+ * the tree leaves it unusable, of the dst_stree_* call of the same name; dst_wtree_info fills a dst_stree_info_t.  Beyond those, DST_ERR_ARG:
+ * more than 2^40 keys in one call.
+ * NOT YET AVAILABLE for wide trees: multiproofs (dst_stree_multiproof, dst_rescue_multiproof_*) and save / load (dst_stree_save,
+ * dst_stree_load); a host persists a wide tree through dst_wtree_read_level and rebuilds it with one dst_wtree_set. */
+typedef struct dst_wtree dst_wtree;
+DST_API int dst_wtree_create(int device, uint32_t depth /* 1 .. 127 */, const uint8_t empty_leaf[32] /* NULL: (0, 0) */, dst_wtree** out);   /* dst_stree_create */
+DST_API int dst_wtree_set(dst_wtree* t, const uint8_t* keys /* count*16 */, const uint8_t* leaves /* count*32 */, size_t count);              /* dst_stree_set */
+DST_API int dst_wtree_remove(dst_wtree* t, const uint8_t* keys /* count*16 */, size_t count, uint64_t* removed /* may be NULL */);            /* dst_stree_remove */
+DST_API int dst_wtree_compact(dst_wtree* t, uint64_t* removed /* may be NULL */);                                                            /* dst_stree_compact */
+DST_API int dst_wtree_get(const dst_wtree* t, const uint8_t* keys /* count*16 */, size_t count,
+                          uint8_t* leaves /* count*32 */, uint8_t* stored /* count bytes of 0 / 1, may be NULL */);                           /* dst_stree_get */
+DST_API int dst_wtree_root(const dst_wtree* t, uint8_t root[32]);                                                                            /* dst_stree_root */
+DST_API int dst_wtree_paths(const dst_wtree* t, const uint8_t* keys /* count*16 */, size_t count, uint8_t* paths /* count*(depth+1)*32 */);   /* dst_stree_paths */
+DST_API int dst_wtree_apply(dst_wtree* t, const uint8_t* keys /* count*16 */, const uint8_t* leaves /* count*32 */, size_t count,
+                            uint8_t* paths /* count*(depth+1)*32, or NULL */, uint8_t* roots /* count*32, or NULL */);                        /* dst_stree_apply */
+DST_API int dst_wtree_tapes_many(const dst_wtree* t, const uint8_t* keys /* count*16 */, size_t count, uint32_t what,
+                                 uint8_t* tape_a, uint8_t* tape_b, size_t cap_elems_each, size_t* elems_each);                               /* dst_stree_tapes_many */
+DST_API int dst_wtree_read_level(const dst_wtree* t, uint32_t level, uint64_t first, uint64_t count,
+                                 uint8_t* prefixes /* count*16 */, uint8_t* nodes /* count*32 */, uint64_t* level_count);                    /* dst_stree_read_level */
+DST_API int dst_wtree_info(const dst_wtree* t, dst_stree_info_t* out);                                                                       /* dst_stree_info */
+/* dst_stree_audit; bad_prefix receives 16 bytes, all zero when no parent is bad */
+DST_API int dst_wtree_audit(const dst_wtree* t, int32_t* bad_level, uint8_t bad_prefix[16], double* device_ms /* may be NULL */);
+/* test build only (the product library answers DST_ERR_STATE): overwrites entry `index` of level `level`'s node list and hashes nothing, so that an
+ * audit has something to find */
+DST_API int dst_wtree_test_set_node(dst_wtree* t, uint32_t level, uint64_t index, const uint8_t node[32]);
+DST_API void dst_wtree_destroy(dst_wtree* t);
+DST_API const char* dst_wtree_last_error(const dst_wtree* t);     /* t may be NULL: the error of the calling thread's last failed dst_wtree_create */
+/* the path tools without a tree over 16-byte indices: 2 <= n <= 128, indices[i] below 2^(n-1) as a whole; everything else -- arguments, verdicts,
+ * `why`, first_bad, the one launch of a device >= 0 call, device_ms, errors filed with dst_rtree_last_error(NULL) -- as dst_rescue_path_roots,
+ * dst_rescue_verify_paths, dst_rescue_verify_writes and dst_rescue_path_tapes.  The direction bit of level k is bit k of the whole index. */
+DST_API int dst_rescue_path_roots_w(int device, const uint8_t* paths /* count*n*32 */, uint32_t n, const uint8_t* indices /* count*16 */, size_t count,
+                                    const uint8_t* leaves /* count*32, or NULL */, uint8_t* roots /* count*32 */, double* device_ms);
+DST_API int dst_rescue_verify_paths_w(int device, const uint8_t root[32], const uint8_t* paths /* count*n*32 */, uint32_t n, const uint8_t* indices /* count*16 */,
+                                      const uint8_t* leaves /* count*32, or NULL */, size_t count, int64_t* first_bad, uint32_t* why, double* device_ms);
+DST_API int dst_rescue_verify_writes_w(int device, const uint8_t root_before[32], const uint8_t* paths /* count*n*32 */, uint32_t n, const uint8_t* indices /* count*16 */,
+                                       const uint8_t* leaves /* count*32 */, const uint8_t* roots /* count*32, or NULL */, size_t count, int64_t* first_bad,
+                                       uint32_t* why, uint8_t root_after[32] /* may be NULL */, double* device_ms);
+DST_API int dst_rescue_path_tapes_w(const uint8_t* paths /* count*n*32 */, uint32_t n, const uint8_t* indices /* count*16 */, size_t count, uint32_t what,
+                                    uint8_t* tape_a, uint8_t* tape_b, size_t cap_elems_each, size_t* elems_each);
+
 /* ---- host-side helpers that the Rust host would otherwise take from `rand` (they run on the CPU) -------------------- */
 DST_API void dst_prng_vector(const uint8_t seed[32], uint32_t count, uint8_t* out /* count*16 */);          /* field.rs:271 */
 DST_API int dst_query_positions(const uint8_t seed[32], uint64_t domain_size, uint32_t blowup, uint32_t num_queries, uint64_t* out); /* utils/mod.rs:25 */

@@ -4,6 +4,8 @@ device's own modular-multiplication rate sets.
     python tools/rescue_tree_time.py [--host-log 12] [--lib path/to/another/build.so] [log_leaves ...]        (default 12 16 20)
     python tools/rescue_tree_time.py --update        updates in place and batched openings on the 2^20 tree instead (dst_rtree_update_ms)
     python tools/rescue_tree_time.py --sparse        sparse trees of depth 63 instead (dst_stree_set, dst_stree_paths), beside a dense 2^20 build
+    python tools/rescue_tree_time.py --wide          wide-key sparse trees of depth 127 (dst_wtree_set beside dst_stree_set at depth 63 with as many keys, dst_wtree_paths,
+                                                     dst_wtree_apply, dst_rescue_verify_paths_w)
     python tools/rescue_tree_time.py --remove        deletion on the depth-63 tree of 2^20 keys that --sparse builds (dst_stree_remove beside a dst_stree_set of the
                                                      same keys, dst_stree_compact after an apply of empties, dst_stree_get beside dst_stree_paths)
     python tools/rescue_tree_time.py --sequence      ordered writes with a witness each (dst_rtree_apply on the 2^20 tree, dst_stree_apply on a depth-63 tree
@@ -39,6 +41,7 @@ ap.add_argument("--sequence", action="store_true", help="time dst_rtree_apply / 
 ap.add_argument("--verify", action="store_true", help="time dst_rescue_verify_writes on the witnesses of dst_rtree_apply / dst_stree_apply (256, 4 096, 65 536 writes), on the host for 256, and dst_rescue_verify_paths of 4 096 paths")
 ap.add_argument("--multiproof", action="store_true", help="time dst_rescue_multiproof_root of 256, 4 096, 65 536 distinct leaves of the dense 2^20 tree and of the depth-63 tree of 2^20 keys beside dst_rescue_verify_paths on the full paths of the same leaves; bytes and digests of both")
 ap.add_argument("--restore", action="store_true", help="time dst_rtree_audit / dst_stree_audit (one launch each) beside the builds of the same trees (dense 2^20; depth 63 with 2^20 keys), and dst_rtree_load / dst_stree_load of their saved forms beside the wall time of the rebuild")
+ap.add_argument("--wide", action="store_true", help="time the wide-key sparse trees: create + one dst_wtree_set of 2^16 and 2^20 random keys at depth 127 beside dst_stree_set of as many keys at depth 63, dst_wtree_paths of 2^16 keys, dst_wtree_apply of 2^12 writes, dst_rescue_verify_paths_w of 2^16 paths of 128 nodes")
 ap.add_argument("sizes", nargs="*", type=int)
 args = ap.parse_args()
 lib = D.lib._open(os.path.abspath(args.lib)) if args.lib else None       # through the binding: one HIP runtime per process
@@ -107,6 +110,85 @@ if args.update:
     assert r == 0 and np.array_equal(out[-n:], one)
     print("dst_rtree_paths of %d indices: %.3f ms wall; %d calls of dst_rtree_path: %.2f ms wall (ctypes, no conversion): %.0f x" % (count, c_many * 1e3, count, c_single * 1e3, c_single / c_many))
     t.close()
+    sys.exit(0)
+if args.wide:
+    def wide_keys(count, seed, bits=127):
+        """-> distinct random keys as words [count, 2] (low half first), shuffled, and as many leaves"""
+        rng = np.random.default_rng(seed)
+        k = rng.integers(0, 1 << 64, size=(count + count // 8 + 16, 2), dtype=np.uint64)
+        k[:, 1] >>= np.uint64(128 - bits)
+        k = np.unique(k, axis=0)
+        rng.shuffle(k)
+        v = rng.integers(0, 1 << 64, size=(count, 2, 2), dtype=np.uint64)
+        v[..., 1] >>= np.uint64(1)
+        return np.ascontiguousarray(k[:count]), v
+
+    def one_set(make, depth, k, v, runs):
+        """create + one set, `runs` times after one warm-up -> (the last tree, device ms of each run, the least wall time in ms)"""
+        ms, wall, t = [], [], None
+        for _ in range(1 + runs):
+            if t is not None:
+                t.close()
+            t0 = time.perf_counter()
+            t = make(depth, device=0, lib=lib)
+            t.set(k, v)
+            wall.append((time.perf_counter() - t0) * 1e3)
+            ms.append(t.info()["last_device_ms"])
+        return t, ms[1:], min(wall[1:])
+
+    big = None
+    for log_keys in (16, 20):
+        count, runs = 1 << log_keys, (args.runs if log_keys < 20 else 1)
+        k, v = wide_keys(count, 300 + log_keys)
+        narrow_k = np.unique(np.random.default_rng(400 + log_keys).integers(0, 1 << 63, size=count + count // 8, dtype=np.uint64))
+        np.random.default_rng(5).shuffle(narrow_k)
+        for name, make, depth, keys, per_node, head in (("dst_stree_set", D.SparseRescueTree, 63, narrow_k[:count], 40, 3072), ("dst_wtree_set", D.WideSparseRescueTree, 127, k, 48, 6144)):
+            t, ms, wall = one_set(make, depth, keys, v, runs)
+            i = t.info()
+            within = sum(1 for l in range(depth) if min(1 << l, count) <= (1 << 15))
+            print("%s of 2^%d random keys into an empty depth-%d tree: %.3f ms on the device (min of %d after one warm-up; all: %s), %d digests, %.3e digests/s over the level launches; "
+                  "%d stored nodes = %.1f per key, %.1f MiB on the device; %d of %d levels within RESCUE_SPREAD_MAX; %.1f ms wall with the plan and the uploads"
+                  % (name, log_keys, depth, min(ms), len(ms), " ".join("%.3f" % x for x in ms), i["last_digests"], i["last_digests"] / (min(ms) * 1e-3), i["nodes"], i["nodes"] / count,
+                     (per_node * i["nodes"] + head) / 2 ** 20, within, depth, wall))
+            if log_keys == 16 and depth == 127:
+                big = t
+            else:
+                t.close()
+    rng = np.random.default_rng(8)
+    stored = big.level(127)[0]
+    absent, _ = wide_keys(1 << 15, 9)
+    ask = np.ascontiguousarray(np.concatenate([stored[rng.integers(0, len(stored), size=1 << 15)], absent]))
+    big.paths_words(ask[:16])                       # warm-up
+    t0 = time.perf_counter(); words = big.paths_words(ask); s_paths = time.perf_counter() - t0
+    print("dst_wtree_paths of 2^16 keys (half stored, half absent) on the 2^16-key depth-127 tree: %.3f ms wall (128 nodes of 128 searched levels each, %.0f MiB back)" % (s_paths * 1e3, words.nbytes / 2 ** 20))
+    root = big.root
+    stats = {}
+    D.verify_paths_wide(root, words[:16], ask[:16], device=0, lib=lib)      # warm-up
+    ms = []
+    for _ in range(args.runs):
+        assert D.verify_paths_wide(root, words, ask, device=0, lib=lib, stats=stats) == (-1, D.DST_PATH_OK)
+        ms.append(stats["device_ms"])
+    chains = len(ask) * 127
+    print("dst_rescue_verify_paths_w of 2^16 paths of 128 nodes: %.3f ms on the device (min of %d; all: %s), %d digests, %.3e digests/s"
+          % (min(ms), len(ms), " ".join("%.3f" % x for x in ms), chains, chains / (min(ms) * 1e-3)))
+    ms, wall = [], []
+    for run in range(1 + args.runs):
+        fresh, v = wide_keys(1 << 11, 50 + run)
+        ops = np.ascontiguousarray(np.concatenate([stored[rng.integers(0, len(stored), size=1 << 11)], fresh]))
+        v2 = np.concatenate([v, v])
+        import ctypes                               # the C call: the binding's conversion to Python ints is not what is timed
+        paths = np.zeros((len(ops) * 128, 2, 2), dtype=np.uint64)
+        roots = np.zeros((len(ops), 2, 2), dtype=np.uint64)
+        vp = lambda x: x.ctypes.data_as(ctypes.c_void_p)  # noqa: E731
+        t0 = time.perf_counter()
+        big._check(big.lib.dst_wtree_apply(big._h, vp(ops), vp(v2), ctypes.c_size_t(len(ops)), vp(paths), vp(roots)))
+        wall.append((time.perf_counter() - t0) * 1e3)
+        i = big.info()
+        ms.append(i["last_device_ms"])
+    ms, wall = ms[1:], wall[1:]
+    print("dst_wtree_apply of 2^12 ordered writes (half to stored keys, half to new ones) with paths and roots: %.3f ms on the device (min of %d after one warm-up; all: %s), %d digests, %.3e digests/s; %.1f ms wall"
+          % (min(ms), len(ms), " ".join("%.3f" % x for x in ms), i["last_digests"], i["last_digests"] / (min(ms) * 1e-3), min(wall)))
+    big.close()
     sys.exit(0)
 if args.sparse or args.remove or args.restore:
     DEPTH = 63

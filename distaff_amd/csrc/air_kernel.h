@@ -413,6 +413,13 @@ __device__ __forceinline__ void air_flow(ACC& acc, const AirArgs& a, const AirCo
     }
 }
 
+// Which outputs of a nested-sum launch are evaluated as a flat sum over basis terms (st_output_basis) instead of nested sums
+// (st_output): a mask by output.  The static instruction counts and the registers decide per instance (profiles/air_stack_basis.md).
+template <int SD, bool DEEP, uint32_t GROUPS>
+constexpr uint32_t air_stack_flat() {
+    return st_flat_default<GROUPS, SD, DEEP>();
+}
+
 // The six RESCR differences of the nested-sum statement (hash.rs:9-35), computed once per point.  Items at and above a known depth are
 // zeros: their round-constant cubes come from the periodic table's values alone, and the inverse-matrix rows are shorter.
 template <int SD, int NS>
@@ -449,8 +456,10 @@ __device__ __forceinline__ void air_stack_nested(ACC& acc, const AirArgs& a, con
     StackHigh high;
     high.push = f.hdf[0]; high.cmp = f.hdf[1]; high.rescr = f.hdf[2]; high.keep = fe_add(f.begin_flag, f.noop_flag);
     if constexpr ((GROUPS & AG_RESCR) != 0) air_rescr_differences<SD, NS>(high.resc, o, nw, per, a.consts);
+    constexpr uint32_t FLAT = air_stack_flat<SD, DEEP, GROUPS>();       // the outputs that are one flat sum over the launch's basis terms
+    StClassSums<st_class_count<GROUPS, SD, DEEP, FLAT>()> classes;
     const uint32_t sbase = 20 + cl + ll;
-    static_for_air<0, NS + 2>([&](auto k_) {
+    auto output = [&](auto k_) {
         constexpr int kk = decltype(k_)::value;
         constexpr int I = kk < NS ? kk : (kk == NS ? ST_AUX0 : ST_AUX1);
         constexpr bool touched = st_touches<I, GROUPS>();
@@ -458,7 +467,7 @@ __device__ __forceinline__ void air_stack_nested(ACC& acc, const AirArgs& a, con
         if constexpr (touched || !EV_OUT) {
             if (I >= 8 || I < sd) {
                 fe v = fe_zero();
-                if constexpr (touched) v = st_output<I, GROUPS, SD, DEEP>(rows, f.lo2, lo0h, f.mid, f.top, high);
+                if constexpr (touched) v = st_output_basis<I, GROUPS, SD, DEEP, FLAT>(rows, classes, f.lo2, lo0h, f.mid, f.top, high);
                 fe* slot = a.ev[I] + pidx;
                 if constexpr (EV_IN) v = touched ? fe_add(v, *slot) : *slot;
                 if constexpr (EV_OUT) *slot = v;
@@ -467,6 +476,18 @@ __device__ __forceinline__ void air_stack_nested(ACC& acc, const AirArgs& a, con
         } else if constexpr (!EV_IN) {
             a.ev[I][pidx] = fe_zero();                           // the first stack launch defines every partial value
         }
+    };
+    // The nested outputs first: they are the last readers of lo2, mid and top, so the class sums, formed once for all flat outputs, replace the
+    // tables in the registers instead of joining them.  (The order of the outputs is free: the emitted sums are exact and the partial
+    // values have an array each.)
+    static_for_air<0, NS + 2>([&](auto k_) {
+        constexpr int kk = decltype(k_)::value;
+        if constexpr (((FLAT >> (kk < NS ? kk : (kk == NS ? ST_AUX0 : ST_AUX1))) & 1u) == 0) output(k_);
+    });
+    st_class_sums<GROUPS, SD, DEEP, FLAT>(classes, f.lo2, lo0h, f.mid, f.top);
+    static_for_air<0, NS + 2>([&](auto k_) {
+        constexpr int kk = decltype(k_)::value;
+        if constexpr (((FLAT >> (kk < NS ? kk : (kk == NS ? ST_AUX0 : ST_AUX1))) & 1u) != 0) output(k_);
     });
 }
 

@@ -6,6 +6,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include <type_traits>
+#include <utility>
 #include "fe.h"
 
 __device__ __forceinline__ fe bnot(const fe& v) { return fe_sub(fe_one(), v); }
@@ -306,4 +307,195 @@ __device__ __forceinline__ fe st_output(const StackRows& s, const fe* lo2, const
     });
     if constexpr ((GROUPS & AG_HIGH) != 0) st_high_degree<I, GROUPS, SDK>(outer, s, h);
     return fe_acc_reduce(outer);
+}
+
+// ---- the same outputs as ONE flat sum over the distinct basis terms of the launch -------------------------------------------------------
+// st_output pays the `mid` and `top` levels again for every output, although mid[b], top[c] and the sums of lo2 entries do not depend on
+// the slot, and merges terms only inside a group of four opcodes.  For slots >= 1 almost every term is one of a handful of plain
+// differences that recur across groups ("shift left by one" is the term of ASSERT, DROP, ADD, MUL, AND and OR; "copy" that of INV, NEG,
+// NOT and, with its sign flipped, of CSWAP2 on the low slots).  By the distributive law alone
+//     output = sum_T K_T * T                    over the DISTINCT basis terms T of the output among ALL selected groups,
+//     K_T    = sum of +- flag(op) = +- top[c] * mid[b] * lo2[a]   over the operations whose term is +-T
+// and every K_T is an add / subtract of a few CLASS SUMS: sums of flags over sets of operations that always appear together, formed
+// once per point (st_class_sums) and shared by the slots.  Nothing about the table entries is assumed (not sum_b mid[b] = 1, and not
+// sum_a lo2[a] = 1, which is false: lo2[2] carries the reference's cf_op_bits[1] quirk), so the statement holds on the cosets where the
+// op bits are not 0 / 1.  st_has and st_desc stay the authority; the merge rule is st_merge's (equal up to sign; computed terms only
+// through the shared values j >= 100).  FLAT is the mask of outputs (bit I) that take this form; the others keep st_output.
+#define ST_NB 32
+struct StBasis { int n; int kind[ST_NB], j[ST_NB], lead[ST_NB]; uint32_t pos[ST_NB], neg[ST_NB]; };   // per basis: leader's kind / j / opcode, operations that contribute with + and with -
+struct StBasisTable {
+    StBasis b[10];                 // per output (slots 0..7, ST_AUX0, ST_AUX1); n = 0 where the output is not flat
+    int nclass; uint32_t cls[32];  // the class sums: disjoint sets of operations (masks by opcode)
+};
+
+template <int I, int... OP> constexpr uint32_t st_has_mask_of(std::integer_sequence<int, OP...>) { return ((st_has<OP, I>() ? (1u << OP) : 0u) | ...); }
+template <int I> constexpr uint32_t st_has_mask() { return st_has_mask_of<I>(std::make_integer_sequence<int, 32>{}); }
+// the opcodes of the low-degree groups a launch selects
+constexpr uint32_t st_group_ops(uint32_t groups) {
+    uint32_t ops = 0;
+    for (int g = 0; g < 8; g++) if ((groups >> g) & 1u) ops |= 0xFu << (4 * g);
+    return ops;
+}
+
+template <int SDK, bool DEEP>
+constexpr StBasis st_basis(uint32_t ops, int I) {
+    StBasis m{};
+    for (int op = 0; op < 32; op++) {
+        if (!((ops >> op) & 1u)) continue;
+        const StDesc d = st_desc<SDK, DEEP>(op, I);
+        if (d.kind == 0) continue;
+        const int cls = d.kind == 5 ? 5 : (d.kind <= 2 ? 1 : 3);           // as st_merge: differences with o[j], +-nw[I], computed
+        const int sign = (d.kind == 2 || d.kind == 4) ? -1 : 1;
+        int e = -1;
+        for (int k = 0; k < m.n; k++) {
+            const int kc = m.kind[k] == 5 ? 5 : (m.kind[k] <= 2 ? 1 : 3);
+            if (kc != cls) continue;
+            if (cls == 3 || (cls == 1 && m.j[k] == d.j) || (cls == 5 && d.j >= 100 && m.j[k] == d.j)) e = k;
+        }
+        if (e < 0) { e = m.n++; m.kind[e] = d.kind; m.j[e] = d.j; m.lead[e] = op; m.pos[e] = 1u << op; }
+        else {
+            const int lead_sign = (m.kind[e] == 2 || m.kind[e] == 4) ? -1 : 1;
+            if (sign * lead_sign > 0) m.pos[e] |= 1u << op; else m.neg[e] |= 1u << op;
+        }
+    }
+    return m;
+}
+
+template <uint32_t GROUPS, int SDK, bool DEEP, uint32_t FLAT>
+constexpr StBasisTable st_basis_table() {
+    StBasisTable t{};
+    const uint32_t has[10] = {st_has_mask<0>(), st_has_mask<1>(), st_has_mask<2>(), st_has_mask<3>(), st_has_mask<4>(), st_has_mask<5>(), st_has_mask<6>(),
+                              st_has_mask<7>(), st_has_mask<ST_AUX0>(), st_has_mask<ST_AUX1>()};
+    const uint32_t ops = st_group_ops(GROUPS & (AG_LOW0 | AG_LOW1));
+    int sig[32][10] = {};          // where an operation sits: +-(basis + 1) per flat output
+    for (int I = 0; I < 10; I++) {
+        if (!((FLAT >> I) & 1u)) continue;
+        t.b[I] = st_basis<SDK, DEEP>(ops & has[I], I);
+        for (int e = 0; e < t.b[I].n; e++)
+            for (int op = 0; op < 32; op++) {
+                if ((t.b[I].pos[e] >> op) & 1u) sig[op][I] = e + 1;
+                if ((t.b[I].neg[e] >> op) & 1u) sig[op][I] = -(e + 1);
+            }
+    }
+    // operations that sit in the same basis with the same sign in EVERY flat output form one class
+    int first[32] = {};
+    for (int op = 0; op < 32; op++) {
+        bool used = false;
+        for (int I = 0; I < 10; I++) used = used || sig[op][I] != 0;
+        if (!used) continue;
+        int k = -1;
+        for (int c = 0; c < t.nclass && k < 0; c++) {
+            bool same = true;
+            for (int I = 0; I < 10; I++) same = same && sig[op][I] == sig[first[c]][I];
+            if (same) k = c;
+        }
+        if (k < 0) { k = t.nclass++; first[k] = op; }
+        t.cls[k] |= 1u << op;
+    }
+    return t;
+}
+template <uint32_t GROUPS, int SDK, bool DEEP, uint32_t FLAT> struct StBasisOf { static constexpr StBasisTable T = st_basis_table<GROUPS, SDK, DEEP, FLAT>(); };
+template <uint32_t GROUPS, int SDK, bool DEEP, uint32_t FLAT> constexpr int st_class_count() { return StBasisOf<GROUPS, SDK, DEEP, FLAT>::T.nclass; }
+
+// Which outputs of a launch take the flat form: slots >= 1 whose computed terms (each needs the full flag of its own operation, two
+// multiplications) are few.  Slot 0 and the auxiliary constraints are computed terms throughout: there the nested levels of st_output,
+// which never form a flag, are the cheaper statement.
+template <uint32_t GROUPS, int SDK, bool DEEP>
+constexpr uint32_t st_flat_default() {
+    constexpr StBasisTable all = st_basis_table<GROUPS, SDK, DEEP, 0x0FEu>();
+    uint32_t flat = 0;
+    for (int I = 1; I < 8; I++) {
+        int computed = 0, members = 0;
+        for (int e = 0; e < all.b[I].n; e++) {
+            if (all.b[I].kind[e] == 5) computed++;
+            for (int op = 0; op < 32; op++) members += (int)(((all.b[I].pos[e] | all.b[I].neg[e]) >> op) & 1u);
+        }
+        if (all.b[I].n > 0 && computed <= 2 && members > all.b[I].n) flat |= 1u << I;
+    }
+    return flat;
+}
+
+template <int N> struct StClassSums { fe k[N > 0 ? N : 1]; };
+
+// sum of the lo2 entries of the operations `ops` (a 4-bit mask) of group `base` (lo0h stands for lo2[0] in group 0, see st_output)
+template <int BASE, uint32_t OPS>
+__device__ __forceinline__ fe st_lo_sum(const fe* lo2, const fe& lo0h) {
+    fe v = fe_zero(); bool any = false;
+    static_for_air<0, 4>([&](auto a_) {
+        constexpr int a = decltype(a_)::value;
+        if constexpr (((OPS >> a) & 1u) != 0) {
+            const fe x = (BASE == 0 && a == 0) ? lo0h : lo2[a];
+            v = any ? fe_add(v, x) : x; any = true;
+        }
+    });
+    return v;
+}
+// sum over the operations of one class of top[c] * mid[b] * lo2[a], as sum over the groups of mt[4c + b] * (sum of the group's lo2
+// entries) with mt[4c + b] = mid[b] * top[c]: one multiplication for a class inside one group, else one sum of products
+template <uint32_t OPS>
+__device__ __forceinline__ fe st_class_sum(const fe* lo2, const fe& lo0h, const fe* mt) {
+    constexpr int ng = ((OPS & 0xFu) != 0) + ((OPS & 0xF0u) != 0) + ((OPS & 0xF00u) != 0) + ((OPS & 0xF000u) != 0) + ((OPS & 0xF0000u) != 0) + ((OPS & 0xF00000u) != 0) +
+                       ((OPS & 0xF000000u) != 0) + ((OPS & 0xF0000000u) != 0);
+    fe_acc sum; fe_acc_zero(sum);
+    fe only = fe_zero();
+    static_for_air<0, 8>([&](auto g_) {
+        constexpr int g = decltype(g_)::value;
+        constexpr uint32_t grp = (OPS >> (4 * g)) & 0xFu;
+        if constexpr (grp != 0) {
+            const fe lo = st_lo_sum<4 * g, grp>(lo2, lo0h);
+            if constexpr (ng == 1) only = fe_mul(mt[g], lo); else fe_acc_mac(sum, mt[g], lo);
+        }
+    });
+    if constexpr (ng == 1) return only; else return fe_acc_reduce(sum);
+}
+template <uint32_t GROUPS, int SDK, bool DEEP, uint32_t FLAT>
+__device__ __forceinline__ void st_class_sums(StClassSums<st_class_count<GROUPS, SDK, DEEP, FLAT>()>& cs, const fe* lo2, const fe& lo0h, const fe* mid, const fe* top) {
+    using B = StBasisOf<GROUPS, SDK, DEEP, FLAT>;
+    fe mt[8];                       // only the groups some class has operations in
+    static_for_air<0, 8>([&](auto g_) {
+        constexpr int g = decltype(g_)::value;
+        constexpr bool used = [] { for (int k = 0; k < B::T.nclass; k++) if ((B::T.cls[k] >> (4 * g)) & 0xFu) return true; return false; }();
+        if constexpr (used) mt[g] = fe_mul(mid[g & 3], top[g >> 2]);
+    });
+    static_for_air<0, B::T.nclass>([&](auto k_) {
+        constexpr int k = decltype(k_)::value;
+        cs.k[k] = st_class_sum<B::T.cls[k]>(lo2, lo0h, mt);
+    });
+}
+
+// output I of the selected operations: flat where FLAT says so -- per basis term one coefficient (adds / subtracts of class sums) and
+// one product, ONE reduction, the high-degree / flow products in the same accumulator -- and st_output elsewhere
+template <int I, uint32_t GROUPS, int SDK, bool DEEP, uint32_t FLAT>
+__device__ __forceinline__ fe st_output_basis(const StackRows& s, const StClassSums<st_class_count<GROUPS, SDK, DEEP, FLAT>()>& cs, const fe* lo2, const fe& lo0h, const fe* mid,
+                                              const fe* top, const StackHigh& h) {
+    if constexpr (((FLAT >> I) & 1u) == 0) return st_output<I, GROUPS, SDK, DEEP>(s, lo2, lo0h, mid, top, h);
+    else {
+        using B = StBasisOf<GROUPS, SDK, DEEP, FLAT>;
+        fe_acc outer; fe_acc_zero(outer);
+        static_for_air<0, B::T.b[I].n>([&](auto e_) {
+            constexpr int e = decltype(e_)::value;
+            constexpr uint32_t pos = B::T.b[I].pos[e], neg = B::T.b[I].neg[e];
+            // the leader's class comes first (it is in pos), so the coefficient starts from a plain copy
+            fe cf = fe_zero(); bool any = false;
+            static_for_air<0, B::T.nclass>([&](auto k_) {
+                constexpr int k = decltype(k_)::value;
+                if constexpr ((B::T.cls[k] & pos) != 0) { cf = any ? fe_add(cf, cs.k[k]) : cs.k[k]; any = true; }
+            });
+            static_for_air<0, B::T.nclass>([&](auto k_) {
+                constexpr int k = decltype(k_)::value;
+                if constexpr ((B::T.cls[k] & neg) != 0) cf = fe_sub(cf, cs.k[k]);
+            });
+            constexpr int ii = I < 8 ? I : 0;
+            constexpr int kind = B::T.b[I].kind[e], j = B::T.b[I].j[e] < 0 ? 0 : (B::T.b[I].j[e] < 12 ? B::T.b[I].j[e] : 0);
+            fe term;
+            if constexpr (kind == 1) term = fe_sub(s.o[j], s.nw[ii]);
+            else if constexpr (kind == 2) term = fe_sub(s.nw[ii], s.o[j]);
+            else if constexpr (kind == 3) term = s.nw[ii];
+            else if constexpr (kind == 4) term = fe_neg(s.nw[ii]);
+            else term = st_term<B::T.b[I].lead[e], I>(s);
+            fe_acc_mac(outer, cf, term);
+        });
+        if constexpr ((GROUPS & AG_HIGH) != 0) st_high_degree<I, GROUPS, SDK>(outer, s, h);
+        return fe_acc_reduce(outer);
+    }
 }

@@ -514,6 +514,12 @@ int k_rescue_stree_open(hipStream_t stream, const fe* nodes, const uint64_t* pre
 int k_rescue_stree_lookup(hipStream_t stream, const fe* nodes, const uint64_t* pref, const uint64_t* levels, const fe* empties, const uint64_t* prefix, const uint32_t* level, fe* out, size_t count);
 // out[2 i ..] = the leaf at indices[i] and stored[i] = 1, or the empty leaf and 0: one search of the leaf level [lstart, lstart + lcnt); empty on the host
 int k_rescue_stree_get(hipStream_t stream, const fe* nodes, const uint64_t* pref, size_t lstart, size_t lcnt, const fe* empty, const uint64_t* indices, fe* out, uint8_t* stored, size_t count);
+// the compact multiproof of a wide tree: flat[s] = the flat position of the node (level[s], prefix[s]) or STREE_NEW when it is not stored, rank[s] = the
+// stored nodes of its block of 256 before it, totals[b] = those of block b; then out = the stored nodes alone, packed in the order of s (all device)
+#define RESCUE_LOCATE_BLOCK 256u
+int k_rescue_stree_locate(hipStream_t stream, const stree_wide* pref, const uint64_t* levels, const stree_wide* prefix, const uint32_t* level, uint32_t* flat, uint32_t* rank, uint32_t* totals,
+                          size_t count);
+int k_rescue_stree_pack(hipStream_t stream, const fe* nodes, const uint32_t* flat, const uint32_t* rank, const uint32_t* totals, fe* out, size_t count);
 // flags[i] = whether leaves[i] (2 elements) is the empty leaf (host)
 int k_rescue_stree_empty_leaves(hipStream_t stream, const fe* leaves, const fe* empty, uint8_t* flags, size_t count);
 // ordered writes (host/tree_sequence.h): the versions vin of one level -> vout, those of the level above, for `count` operations; src / own = this

@@ -413,18 +413,32 @@ static int stree_apply(T* t, const typename T::key* indices, const uint8_t* leav
 }
 
 // ---- save, load, audit (tree_blob.h) --------------------------------------------------------------------------------------------------------------
+// what the two widths differ in on the way to bytes and back: the blob kind, its length, a prefix as little-endian bytes, a prefix as decimal text
+static uint32_t st_blob_kind(const dst_stree*) { return TBLOB_SPARSE; }
+static uint32_t st_blob_kind(const dst_wtree*) { return TBLOB_WIDE; }
+static void st_put_key(uint8_t* at, uint64_t q) { tblob_put_u64(at, q); }
+static void st_put_key(uint8_t* at, u128 q) { tblob_put_u64(at, (uint64_t)q); tblob_put_u64(at + 8, (uint64_t)(q >> 64)); }
+static void st_get_key(const uint8_t* at, uint64_t& q) { q = tblob_u64(at); }
+static void st_get_key(const uint8_t* at, u128& q) { q = (u128)tblob_u64(at) | ((u128)tblob_u64(at + 8) << 64); }
+static std::string st_key_text(u128 q) {
+    std::string digits;
+    do { digits.insert(digits.begin(), (char)('0' + (int)(q % 10))); q /= 10; } while (q);
+    return digits;
+}
 // the saved tree: the header, the level lengths, the prefixes and the nodes, all in the order of the flat positions (the leaf level first): copies
-int dst_stree_save(const dst_stree* t, uint8_t* out, size_t cap, size_t* len) {
+template <class T>
+static int stree_save(const T* t, uint8_t* out, size_t cap, size_t* len) {
+    typedef typename T::key K;
     if (int r = st_enter(t)) return r;
     if (!len) return st_fail(t, DST_ERR_ARG, "null pointer");
     const size_t total = t->shape.total(), D = t->depth;
-    *len = (size_t)tblob_sparse_bytes(t->depth, total);
+    *len = (size_t)(TBLOB_HEADER + 8 * ((uint64_t)D + 1) + (32 + sizeof(K)) * (uint64_t)total);
     if (!out) return DST_OK;                                                                // size query
     if (cap < *len) return st_fail(t, DST_ERR_ARG, "the buffer is smaller than the saved tree");
-    tblob_put_header(out, TBLOB_SPARSE, t->depth, reinterpret_cast<const uint8_t*>(t->empties + 2 * D), t->shape.cnt[D], total);
+    tblob_put_header(out, st_blob_kind(t), t->depth, reinterpret_cast<const uint8_t*>(t->empties + 2 * D), t->shape.cnt[D], total);
     uint8_t* at = out + TBLOB_HEADER;
     for (size_t k = 0; k <= D; k++, at += 8) tblob_put_u64(at, t->shape.cnt[D - k]);
-    for (size_t j = 0; j < total; j++, at += 8) tblob_put_u64(at, t->shape.pref[j]);
+    for (size_t j = 0; j < total; j++, at += sizeof(K)) st_put_key(at, t->shape.pref[j]);
     if (total == 0) return DST_OK;
     if (t->device < 0) { memcpy(at, t->host.data(), 32 * total); return DST_OK; }
     RT_HIP(t->err, hipSetDevice(t->device));
@@ -489,14 +503,16 @@ static int stree_audit(const T* t, int32_t* bad_level, typename T::key* bad_pref
 }
 // a tree from its saved form: the E_l come from the empty leaf as in dst_stree_create, nothing else is hashed -- a device tree is one allocation
 // and four copies into it, the nodes straight from the blob -- unless the caller asks for the audit
-int dst_stree_load(int device, const uint8_t* blob, size_t len, uint32_t audit, dst_stree** out) {
-    std::string& g_stree_error = dst_stree::global_error();
+template <class T>
+static int stree_load(int device, const uint8_t* blob, size_t len, uint32_t audit, T** out) {
+    typedef typename T::key K;
+    std::string& g_error = T::global_error();
     if (out) *out = nullptr;
-    if (!blob || !out) { g_stree_error = "null pointer"; return DST_ERR_ARG; }
+    if (!blob || !out) { g_error = "null pointer"; return DST_ERR_ARG; }
     tblob_view v;
-    if (const char* why = tblob_parse(blob, len, TBLOB_SPARSE, v)) { g_stree_error = why; return DST_ERR_ARG; }
-    std::unique_ptr<dst_stree> t(new (std::nothrow) dst_stree);
-    if (!t) { g_stree_error = "out of host memory"; return DST_ERR_HIP; }
+    if (const char* why = tblob_parse(blob, len, st_blob_kind((const T*)nullptr), v)) { g_error = why; return DST_ERR_ARG; }
+    std::unique_ptr<T> t(new (std::nothrow) T);
+    if (!t) { g_error = "out of host memory"; return DST_ERR_HIP; }
     const size_t D = v.depth, total = (size_t)v.nodes;
     t->device = device < 0 ? -1 : device; t->depth = v.depth;
     memcpy(t->empties + 2 * D, v.empty, 32);
@@ -504,19 +520,19 @@ int dst_stree_load(int device, const uint8_t* blob, size_t len, uint32_t audit, 
         const u128 in[4] = {t->empties[2 * l + 2], t->empties[2 * l + 3], t->empties[2 * l + 2], t->empties[2 * l + 3]};
         rescue_digest_many_host(in, 1, t->empties + 2 * l);
     }
-    uint64_t lv[128] = {0};
+    uint64_t lv[2 * T::L] = {0};
     auto copies = [&]() -> int {                                                            // [nodes][empties][levels][prefixes], as stree_apply_device lays it out:
         uint8_t* d = t->dev;                                                                // the nodes go up straight from the caller's blob, no second host image
         if (total) RT_HIP(t->err, hipMemcpyAsync(d, v.values, 32 * total, hipMemcpyHostToDevice, t->stream));
-        RT_HIP(t->err, hipMemcpyAsync(d + 32 * total, t->empties, 2048, hipMemcpyHostToDevice, t->stream));
-        RT_HIP(t->err, hipMemcpyAsync(d + 32 * total + 2048, lv, 1024, hipMemcpyHostToDevice, t->stream));
-        if (total) RT_HIP(t->err, hipMemcpyAsync(d + 32 * total + 3072, t->shape.pref.data(), 8 * total, hipMemcpyHostToDevice, t->stream));
+        RT_HIP(t->err, hipMemcpyAsync(d + 32 * total, t->empties, T::empties_bytes, hipMemcpyHostToDevice, t->stream));
+        RT_HIP(t->err, hipMemcpyAsync(d + 32 * total + T::empties_bytes, lv, T::levels_bytes, hipMemcpyHostToDevice, t->stream));
+        if (total) RT_HIP(t->err, hipMemcpyAsync(d + 32 * total + T::head_bytes, t->shape.pref.data(), sizeof(K) * total, hipMemcpyHostToDevice, t->stream));
         return DST_OK;
     };
     auto upload = [&]() -> int {
         for (size_t l = 0; l <= D; l++) { lv[2 * l] = t->shape.start[l]; lv[2 * l + 1] = t->shape.cnt[l]; }
         if (int r = rtree_stage(t.get(), 0)) return r;
-        RT_HIP(t->err, hipMalloc((void**)&t->dev, 40 * total + 3072));
+        RT_HIP(t->err, hipMalloc((void**)&t->dev, T::generation_bytes(total)));
         const int r = copies();
         const hipError_t e = hipStreamSynchronize(t->stream);                               // also after a failed copy: the sources are the caller's and this frame's
         if (r != DST_OK) return r;
@@ -524,25 +540,25 @@ int dst_stree_load(int device, const uint8_t* blob, size_t len, uint32_t audit, 
         return DST_OK;
     };
     try {
-        stree_shape& sh = t->shape;
+        stree_shape_t<K>& sh = t->shape;
         sh.depth = v.depth;
         sh.pref.resize(total);
-        for (size_t j = 0; j < total; j++) sh.pref[j] = tblob_u64(v.prefixes + 8 * j);
+        for (size_t j = 0; j < total; j++) st_get_key(v.prefixes + sizeof(K) * j, sh.pref[j]);
         size_t at = 0;
         for (size_t k = 0; k <= D; k++) { sh.start[D - k] = at; sh.cnt[D - k] = (size_t)tblob_u64(v.counts + 8 * k); at += sh.cnt[D - k]; }
-        if (device >= 0) { if (int r = upload()) { g_stree_error = t->err; return r; } }
+        if (device >= 0) { if (int r = upload()) { g_error = t->err; return r; } }
         else { t->host.assign(2 * total, 0); if (total) memcpy(t->host.data(), v.values, 32 * total); }
         if (audit) {
             uint64_t key = 0;
             double ms = 0;
-            if (int r = stree_audit_run(t.get(), &key, &ms)) { g_stree_error = t->err; return r; }
+            if (int r = stree_audit_run(t.get(), &key, &ms)) { g_error = t->err; return r; }
             if (key != ~(uint64_t)0) {
-                g_stree_error = "audit: the node of level " + std::to_string(key >> 32) + " with prefix " + std::to_string(sh.pref[sh.start[key >> 32] + (size_t)(key & 0xFFFFFFFFu)]) +
-                                " is not the digest of its children";
+                g_error = "audit: the node of level " + std::to_string(key >> 32) + " with prefix " + st_key_text(sh.pref[sh.start[key >> 32] + (size_t)(key & 0xFFFFFFFFu)]) +
+                          " is not the digest of its children";
                 return DST_ERR_ARG;
             }
         }
-    } catch (const std::bad_alloc&) { g_stree_error = "out of host memory"; return DST_ERR_HIP; }
+    } catch (const std::bad_alloc&) { g_error = "out of host memory"; return DST_ERR_HIP; }
     *out = t.release();
     return DST_OK;
 }
@@ -566,6 +582,8 @@ int dst_stree_tapes_many(const dst_stree* t, const uint64_t* indices, size_t cou
 }
 int dst_stree_apply(dst_stree* t, const uint64_t* indices, const uint8_t* leaves, size_t count, uint8_t* paths, uint8_t* roots) { return stree_apply(t, indices, leaves, count, paths, roots); }
 int dst_stree_audit(const dst_stree* t, int32_t* bad_level, uint64_t* bad_prefix, double* device_ms) { return stree_audit(t, bad_level, bad_prefix, device_ms); }
+int dst_stree_save(const dst_stree* t, uint8_t* out, size_t cap, size_t* len) { return stree_save(t, out, cap, len); }
+int dst_stree_load(int device, const uint8_t* blob, size_t len, uint32_t audit, dst_stree** out) { return stree_load(device, blob, len, audit, out); }
 
 // ---- ... and dst_wtree_* over 16-byte keys: little-endian integers at any alignment, copied into u128 before the call of the same name reads them ----
 struct wt_keys {
@@ -606,6 +624,8 @@ int dst_wtree_audit(const dst_wtree* t, int32_t* bad_level, uint8_t bad_prefix[1
     if (r == DST_OK) memcpy(bad_prefix, &q, 16);
     return r;
 }
+int dst_wtree_save(const dst_wtree* t, uint8_t* out, size_t cap, size_t* len) { return stree_save(t, out, cap, len); }
+int dst_wtree_load(int device, const uint8_t* blob, size_t len, uint32_t audit, dst_wtree** out) { return stree_load(device, blob, len, audit, out); }
 #undef WT_KEYS
 // overwrites one stored node where it lives and hashes nothing: how the tests give an audit something to find in a tree that cannot be loaded from
 // changed bytes.  Test build only; the product library keeps the entry point and answers DST_ERR_STATE

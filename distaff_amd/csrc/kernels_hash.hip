@@ -497,6 +497,54 @@ __global__ void rescue_stree_lookup_kernel(const fe* __restrict__ nodes, const K
     const size_t start = levels[2 * l], pos = stree_find(pref + start, levels[2 * l + 1], prefix[s]);
     out[t] = pos != STREE_ABSENT ? nodes[2 * (start + pos) + (t & 1)] : empties[2 * l + (t & 1)];
 }
+// the compact multiproof of a wide tree (dst_wtree_multiproof), two launches of LOCATE_THREADS lanes a block, one lane per asked node.  The first
+// finds node s = (level[s], prefix[s]) in its level's list and leaves flat[s] = its flat position, or STREE_NEW when it is not stored, and rank[s]
+// = how many stored nodes the block has before s (an inclusive scan over the block's flags in LDS), with the block's count in totals[block].  The
+// second packs the stored nodes: block b starts at the sum of totals[0 .. b) -- every lane adds a stride of them, a tree in LDS adds the lanes --
+// and lane s copies nodes[flat[s]] to out[base + rank[s]].  Barriers and LDS only, no cross-lane instructions: the host emulation runs them too.
+#define LOCATE_THREADS RESCUE_LOCATE_BLOCK
+template <class K>
+__global__ void __launch_bounds__(LOCATE_THREADS) rescue_stree_locate_kernel(const K* __restrict__ pref, const uint64_t* __restrict__ levels, const K* __restrict__ prefix,
+                                                                            const uint32_t* __restrict__ level, uint32_t* __restrict__ flat, uint32_t* __restrict__ rank,
+                                                                            uint32_t* __restrict__ totals, size_t count) {
+    __shared__ uint32_t scan[LOCATE_THREADS];
+    const size_t s = (size_t)blockIdx.x * LOCATE_THREADS + threadIdx.x;
+    uint32_t at = STREE_NEW;
+    if (s < count) {
+        const uint32_t l = level[s];
+        const size_t start = levels[2 * l], pos = stree_find(pref + start, levels[2 * l + 1], prefix[s]);
+        if (pos != STREE_ABSENT) at = (uint32_t)(start + pos);
+    }
+    const uint32_t stored = at != STREE_NEW ? 1u : 0u;
+    scan[threadIdx.x] = stored;
+    __syncthreads();
+    for (uint32_t d = 1; d < LOCATE_THREADS; d <<= 1) {
+        const uint32_t add = threadIdx.x >= d ? scan[threadIdx.x - d] : 0u;
+        __syncthreads();
+        scan[threadIdx.x] += add;
+        __syncthreads();
+    }
+    if (s < count) { flat[s] = at; rank[s] = scan[threadIdx.x] - stored; }
+    if (threadIdx.x == LOCATE_THREADS - 1u) totals[blockIdx.x] = scan[threadIdx.x];
+}
+__global__ void __launch_bounds__(LOCATE_THREADS) rescue_stree_pack_kernel(const fe* __restrict__ nodes, const uint32_t* __restrict__ flat, const uint32_t* __restrict__ rank,
+                                                                          const uint32_t* __restrict__ totals, fe* __restrict__ out, size_t count) {
+    __shared__ uint32_t sum[LOCATE_THREADS];
+    uint32_t mine = 0;
+    for (uint32_t b = threadIdx.x; b < blockIdx.x; b += LOCATE_THREADS) mine += totals[b];
+    sum[threadIdx.x] = mine;
+    __syncthreads();
+    for (uint32_t d = LOCATE_THREADS / 2u; d >= 1u; d >>= 1) {
+        if (threadIdx.x < d) sum[threadIdx.x] += sum[threadIdx.x + d];
+        __syncthreads();
+    }
+    const size_t s = (size_t)blockIdx.x * LOCATE_THREADS + threadIdx.x;
+    if (s >= count) return;                                            // after the last barrier
+    const uint32_t at = flat[s];
+    if (at == STREE_NEW) return;
+    const size_t to = (size_t)sum[0] + rank[s];
+    out[2 * to] = nodes[2 * (size_t)at]; out[2 * to + 1] = nodes[2 * (size_t)at + 1];
+}
 // the leaves alone (dst_stree_get): one lane per index, one search of the leaf level [lstart, lstart + lcnt); a key that is not stored gives the
 // empty leaf (e0, e1) and stored[i] = 0
 template <class K>
@@ -569,6 +617,16 @@ int k_rescue_stree_get(hipStream_t stream, const fe* nodes, const uint64_t* pref
 }
 int k_rescue_stree_get(hipStream_t stream, const fe* nodes, const stree_wide* pref, size_t lstart, size_t lcnt, const fe* empty, const stree_wide* indices, fe* out, uint8_t* stored, size_t count) {
     return rescue_stree_get(stream, nodes, pref, lstart, lcnt, empty, indices, out, stored, count);
+}
+int k_rescue_stree_locate(hipStream_t stream, const stree_wide* pref, const uint64_t* levels, const stree_wide* prefix, const uint32_t* level, uint32_t* flat, uint32_t* rank, uint32_t* totals,
+                          size_t count) {
+    hipLaunchKernelGGL(rescue_stree_locate_kernel<stree_wide>, dim3((unsigned)((count + LOCATE_THREADS - 1) / LOCATE_THREADS)), dim3(LOCATE_THREADS), 0, stream, pref, levels, prefix, level, flat,
+                       rank, totals, count);
+    return hipGetLastError() == hipSuccess ? 0 : -1;
+}
+int k_rescue_stree_pack(hipStream_t stream, const fe* nodes, const uint32_t* flat, const uint32_t* rank, const uint32_t* totals, fe* out, size_t count) {
+    hipLaunchKernelGGL(rescue_stree_pack_kernel, dim3((unsigned)((count + LOCATE_THREADS - 1) / LOCATE_THREADS)), dim3(LOCATE_THREADS), 0, stream, nodes, flat, rank, totals, out, count);
+    return hipGetLastError() == hipSuccess ? 0 : -1;
 }
 int k_rescue_stree_empty_leaves(hipStream_t stream, const fe* leaves, const fe* empty, uint8_t* flags, size_t count) {
     hipLaunchKernelGGL(rescue_stree_empty_leaves_kernel, dim3((unsigned)((count + HASH_THREADS - 1) / HASH_THREADS)), dim3(HASH_THREADS), 0, stream, leaves, empty[0], empty[1], flags, count);

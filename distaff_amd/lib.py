@@ -67,7 +67,9 @@ EXPORTS = ["dst_ctx_create", "dst_ctx_destroy", "dst_last_error", "dst_phase_ms"
            "dst_rtree_save", "dst_rtree_load", "dst_rtree_audit", "dst_stree_save", "dst_stree_load", "dst_stree_audit",
            "dst_wtree_create", "dst_wtree_set", "dst_wtree_remove", "dst_wtree_compact", "dst_wtree_get", "dst_wtree_root", "dst_wtree_paths", "dst_wtree_apply",
            "dst_wtree_tapes_many", "dst_wtree_read_level", "dst_wtree_info", "dst_wtree_audit", "dst_wtree_destroy", "dst_wtree_last_error", "dst_wtree_test_set_node",
-           "dst_rescue_path_roots_w", "dst_rescue_verify_paths_w", "dst_rescue_verify_writes_w", "dst_rescue_path_tapes_w"]
+           "dst_rescue_path_roots_w", "dst_rescue_verify_paths_w", "dst_rescue_verify_writes_w", "dst_rescue_path_tapes_w",
+           "dst_rescue_empty_nodes", "dst_rescue_multiproof_size_w", "dst_wtree_multiproof", "dst_rescue_multiproof_root_w", "dst_rescue_verify_multiproof_w",
+           "dst_rescue_multiproof_paths_w", "dst_rescue_multiproof_last_levels", "dst_wtree_save", "dst_wtree_load"]
 
 
 class DistaffError(RuntimeError):
@@ -534,6 +536,106 @@ def multiproof_paths(n, indices, leaves, nodes, device=0, lib=None, stats=None, 
     return [[(v[2 * (i * n + k)], v[2 * (i * n + k) + 1]) for k in range(n)] for i in range(idx.size)], tuple(arr_to_ints(root))
 
 
+def empty_nodes(n, empty_leaf=(0, 0), words=False, lib=None):
+    """E_0 .. E_{n-1}, the value of an empty subtree of every level of a tree whose paths have n nodes and whose empty leaf is `empty_leaf`
+    (dst_rescue_empty_nodes; host only, n - 1 digests) -> a list of n pairs of ints (words=True: uint64 words [n, 2, 2]): the table the compact
+    checks take.  Compute it once per (empty leaf, depth) -- and compute it: the checks believe it."""
+    lib = lib or load()
+    e = _elements([tuple(empty_leaf)], 2)
+    out = np.zeros((max(int(n), 1), 2, 2), dtype=np.uint64)
+    r = lib.dst_rescue_empty_nodes(_ptr(e), ctypes.c_uint32(n), _ptr(out))
+    if r != DST_OK:
+        raise DistaffError(r, _rtree_error(lib) or "dst_rescue_empty_nodes failed")
+    return out if words else _pairs(out)
+
+
+def multiproof_size_wide(n, indices, lib=None):
+    """multiproof_size for indices of up to 127 bits, Python ints, and 2 <= n <= 128 (dst_rescue_multiproof_size_w): the plain sizes (M, digests)"""
+    lib = lib or load()
+    idx, ip = _wide_keys(indices)
+    m, d = ctypes.c_size_t(0), ctypes.c_uint64(0)
+    r = lib.dst_rescue_multiproof_size_w(ctypes.c_uint32(n), ip, ctypes.c_size_t(idx.shape[0]), ctypes.byref(m), ctypes.byref(d))
+    if r != DST_OK:
+        raise DistaffError(r, _rtree_error(lib) or "dst_rescue_multiproof_size_w failed")
+    return m.value, d.value
+
+
+class _WideProof:
+    """the arguments the three wide checks share: indices, leaves, nodes, and for the compact form the bits and the table"""
+    def __init__(self, n, indices, leaves, nodes, absent_bits, empties):
+        self.idx, self.ip = _wide_keys(indices)
+        self.count = self.idx.shape[0]
+        self.leaves = _nodes_for(leaves, self.count, "leaves")
+        self.nodes = _elements(nodes, 2) if len(nodes) else np.zeros((0, 2, 2), dtype=np.uint64)
+        self.bits = np.frombuffer(bytes(absent_bits), dtype=np.uint8) if absent_bits is not None else None
+        self.table = None
+        if empties is not None:
+            self.table = _elements(empties, 2)
+            if self.table.shape[0] != n:
+                raise DistaffError(DST_ERR_ARG, "empties: one node per level, %d of them" % n)
+        self.spare = np.zeros(1, dtype=np.uint8)                           # a proof without supplied nodes still has a (zero-length) bit string
+
+    def args(self):
+        """what stands between `n` and the outputs of each call"""
+        bits = None if self.bits is None else (_ptr(self.bits) if self.bits.size else _ptr(self.spare))
+        return (self.ip, _ptr(self.leaves) if self.count else None, ctypes.c_size_t(self.count), _ptr(self.nodes) if self.nodes.shape[0] else None,
+                ctypes.c_size_t(self.nodes.shape[0]), bits, _ptr(self.table) if self.table is not None else None)
+
+
+def _wide_stats(lib, stats, ms, digests=None):
+    if stats is not None:
+        stats["device_ms"], stats["levels"] = ms.value, lib.dst_rescue_multiproof_last_levels()
+        if digests is not None:
+            stats["digests"] = digests.value
+
+
+def multiproof_root_wide(n, indices, leaves, nodes, absent_bits=None, empties=None, device=0, lib=None, stats=None):
+    """multiproof_root over indices of up to 127 bits (dst_rescue_multiproof_root_w).  Plain: `nodes` are all M supplied nodes.  Compact:
+    `absent_bits` (bytes, as WideSparseRescueTree.batch_proof returns them) says which supplied nodes are empty subtrees and not among `nodes`,
+    and `empties` is the table of empty_nodes(n, empty_leaf); parents of two empty subtrees are not hashed.  stats receives digests (parents
+    actually computed), levels (levels that had a job: the launches of a device call) and device_ms."""
+    lib = lib or load()
+    a = _WideProof(n, indices, leaves, nodes, absent_bits, empties)
+    out = np.zeros((2, 2), dtype=np.uint64)
+    d, ms = ctypes.c_uint64(0), ctypes.c_double(0)
+    r = lib.dst_rescue_multiproof_root_w(ctypes.c_int(device), ctypes.c_uint32(n), *a.args(), _ptr(out), ctypes.byref(d), ctypes.byref(ms))
+    if r != DST_OK:
+        raise DistaffError(r, _rtree_error(lib) or "dst_rescue_multiproof_root_w failed")
+    _wide_stats(lib, stats, ms, d)
+    return tuple(arr_to_ints(out))
+
+
+def verify_multiproof_wide(root, n, indices, leaves, nodes, absent_bits=None, empties=None, device=0, lib=None, stats=None):
+    """whether the plain or compact multiproof resolves to `root` (dst_rescue_verify_multiproof_w) -> bool; stats receives levels and device_ms"""
+    lib = lib or load()
+    a = _WideProof(n, indices, leaves, nodes, absent_bits, empties)
+    r0 = _nodes_for([tuple(root)], 1, "roots")
+    ok, ms = ctypes.c_int(0), ctypes.c_double(0)
+    r = lib.dst_rescue_verify_multiproof_w(ctypes.c_int(device), _ptr(r0), ctypes.c_uint32(n), *a.args(), ctypes.byref(ok), ctypes.byref(ms))
+    if r != DST_OK:
+        raise DistaffError(r, _rtree_error(lib) or "dst_rescue_verify_multiproof_w failed")
+    _wide_stats(lib, stats, ms)
+    return bool(ok.value)
+
+
+def multiproof_paths_wide(n, indices, leaves, nodes, absent_bits=None, empties=None, device=0, lib=None, stats=None, words=False):
+    """the full authentication paths a plain or compact multiproof stands for (dst_rescue_multiproof_paths_w) -> (paths, root), paths as
+    WideSparseRescueTree.paths returns them (words=True: uint64 words [count, n, 2, 2]): what verify_paths_wide and path_tapes_wide take"""
+    lib = lib or load()
+    a = _WideProof(n, indices, leaves, nodes, absent_bits, empties)
+    out = np.zeros((max(a.count, 1), max(n, 1), 2, 2), dtype=np.uint64)
+    root = np.zeros((2, 2), dtype=np.uint64)
+    ms = ctypes.c_double(0)
+    r = lib.dst_rescue_multiproof_paths_w(ctypes.c_int(device), ctypes.c_uint32(n), *a.args(), _ptr(out), _ptr(root), ctypes.byref(ms))
+    if r != DST_OK:
+        raise DistaffError(r, _rtree_error(lib) or "dst_rescue_multiproof_paths_w failed")
+    _wide_stats(lib, stats, ms)
+    if words:
+        return out[:a.count], tuple(arr_to_ints(root))
+    v = arr_to_ints(out[:a.count])
+    return [[(v[2 * (i * n + k)], v[2 * (i * n + k) + 1]) for k in range(n)] for i in range(a.count)], tuple(arr_to_ints(root))
+
+
 def _tree_save(tree, call):
     """save() of either tree: the size query, then the bytes"""
     n = ctypes.c_size_t(0)
@@ -914,7 +1016,7 @@ class SparseRescueTree(_SparseTree):
 class WideSparseRescueTree(_SparseTree):
     """A sparse Rescue Merkle tree over keys of up to 127 bits (``dst_wtree``), 1 <= depth <= 127: the tree SparseRescueTree is, for keys that
     are hashes.  Keys are Python ints; level() returns its prefixes as uint64 words [m, 2] (low half first; arr_to_ints turns them into
-    ints) and audit() names a prefix as an int.  Multiproofs and save / load are not available for wide trees yet."""
+    ints) and audit() names a prefix as an int.  The batch opening is batch_proof(), plain or compact; to_blob() / from_blob() save and restore."""
     _PREFIX = "dst_wtree_"
 
     @staticmethod
@@ -928,6 +1030,41 @@ class WideSparseRescueTree(_SparseTree):
     @staticmethod
     def _as_key(word):
         return arr_to_ints(word)[0]
+
+    def batch_proof(self, keys, compact=True, words=False):
+        """the multiproof of the distinct keys `keys`, stored or not (dst_wtree_multiproof) -> (leaves, nodes, absent_bits).  compact=True:
+        absent_bits is a bytes object with bit m set when supplied node m is not stored -- an empty subtree -- and `nodes` holds the stored ones
+        alone; compact=False: the plain form, every supplied node, absent_bits None.  What multiproof_root_wide, verify_multiproof_wide and
+        multiproof_paths_wide take.  The plain size query needs no look at the tree, so the buffers are made for M nodes and the tree is asked
+        once: on a device tree two launches whatever len(keys) is, and only stored nodes come back."""
+        idx, ip = self._keys(keys)
+        count = idx.shape[0]
+        call = self.lib.dst_wtree_multiproof
+        s, m = ctypes.c_size_t(0), ctypes.c_size_t(0)
+        self._check(call(self._h, ip, ctypes.c_size_t(count), None, None, ctypes.c_size_t(0), ctypes.byref(m), None, None))      # M: the plan alone
+        leaves = np.zeros((count, 2, 2), dtype=np.uint64)
+        nodes = np.zeros((max(m.value, 1), 2, 2), dtype=np.uint64)         # a set that needs no sibling still asks for the leaves
+        bits = np.zeros((m.value + 7) // 8 + 1, dtype=np.uint8)
+        if count:
+            self._check(call(self._h, ip, ctypes.c_size_t(count), _ptr(leaves), _ptr(nodes), ctypes.c_size_t(m.value), ctypes.byref(s), _ptr(bits) if compact else None, ctypes.byref(m)))
+        nodes, bits = nodes[:s.value], bits[:(m.value + 7) // 8]
+        absent = bits.tobytes() if compact else None
+        return (leaves, nodes, absent) if words else (_pairs(leaves), _pairs(nodes), absent)
+
+    def to_blob(self):
+        """the tree as bytes (dst_wtree_save): SparseRescueTree.save with blob kind 3 and 16-byte prefixes, 64 + 8 * (depth + 1) + 48 * nodes
+        bytes; the same bytes whether the tree lives on the host or on a device"""
+        return _tree_save(self, self.lib.dst_wtree_save)
+
+    @classmethod
+    def from_blob(cls, blob, device=0, audit=False, lib=None):
+        """the tree to_blob() wrote, on `device` (dst_wtree_load), without hashing it again; SparseRescueTree.load's refusals, with all 128 bits
+        of a prefix compared, and audit=True as there"""
+        t = cls.__new__(cls)
+        t.lib = lib or load()
+        t._h = _tree_load(t.lib, t.lib.dst_wtree_load, lambda l: t._error(None), blob, device, audit)
+        t.depth = t.info()["depth"]
+        return t
 
     def test_set_node(self, level, index, node):
         """overwrites entry `index` of level `level`'s node list with the pair `node`, hashing nothing (dst_wtree_test_set_node; the test build

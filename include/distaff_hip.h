@@ -406,9 +406,7 @@ DST_API const char* dst_stree_last_error(const dst_stree* t);     /* t may be NU
  * Each call has the semantics, the argument checks (DST_ERR_ARG, found on the host before anything is queued, the tree unchanged), the host
  * path for device < 0, the launch count per call, the last_digests and last_device_ms, and the rule that a HIP error inside a call that changes
  * the tree leaves it unusable, of the dst_stree_* call of the same name; dst_wtree_info fills a dst_stree_info_t.  Beyond those, DST_ERR_ARG:
- * more than 2^40 keys in one call.
- * NOT YET AVAILABLE for wide trees: multiproofs (dst_stree_multiproof, dst_rescue_multiproof_*) and save / load (dst_stree_save,
- * dst_stree_load); a host persists a wide tree through dst_wtree_read_level and rebuilds it with one dst_wtree_set. */
+ * more than 2^40 keys in one call.  Multiproofs, plain and compact, and save / load follow below the path tools. */
 typedef struct dst_wtree dst_wtree;
 DST_API int dst_wtree_create(int device, uint32_t depth /* 1 .. 127 */, const uint8_t empty_leaf[32] /* NULL: (0, 0) */, dst_wtree** out);   /* dst_stree_create */
 DST_API int dst_wtree_set(dst_wtree* t, const uint8_t* keys /* count*16 */, const uint8_t* leaves /* count*32 */, size_t count);              /* dst_stree_set */
@@ -431,7 +429,7 @@ DST_API int dst_wtree_audit(const dst_wtree* t, int32_t* bad_level, uint8_t bad_
  * audit has something to find */
 DST_API int dst_wtree_test_set_node(dst_wtree* t, uint32_t level, uint64_t index, const uint8_t node[32]);
 DST_API void dst_wtree_destroy(dst_wtree* t);
-DST_API const char* dst_wtree_last_error(const dst_wtree* t);     /* t may be NULL: the error of the calling thread's last failed dst_wtree_create */
+DST_API const char* dst_wtree_last_error(const dst_wtree* t);     /* t may be NULL: the error of the calling thread's last failed dst_wtree_create / dst_wtree_load */
 /* the path tools without a tree over 16-byte indices: 2 <= n <= 128, indices[i] below 2^(n-1) as a whole; everything else -- arguments, verdicts,
  * `why`, first_bad, the one launch of a device >= 0 call, device_ms, errors filed with dst_rtree_last_error(NULL) -- as dst_rescue_path_roots,
  * dst_rescue_verify_paths, dst_rescue_verify_writes and dst_rescue_path_tapes.  The direction bit of level k is bit k of the whole index. */
@@ -444,6 +442,56 @@ DST_API int dst_rescue_verify_writes_w(int device, const uint8_t root_before[32]
                                        uint32_t* why, uint8_t root_after[32] /* may be NULL */, double* device_ms);
 DST_API int dst_rescue_path_tapes_w(const uint8_t* paths /* count*n*32 */, uint32_t n, const uint8_t* indices /* count*16 */, size_t count, uint32_t what,
                                     uint8_t* tape_a, uint8_t* tape_b, size_t cap_elems_each, size_t* elems_each);
+
+/* ---- multiproofs of wide trees, plain and COMPACT ------------------------------------------------------------------------------------------------
+ * The multiproof above over 16-byte indices and 2 <= n <= 128: the same node set, the same order (level n - 1 first, ascending by position within
+ * a level), M and `digests` as dst_rescue_multiproof_size counts them.  A path of a deep sparse tree is mostly empty subtrees -- of the 118 nodes per key that a
+ * plain proof of 256 keys of a 2^20-key tree of depth 127 supplies, 11.5 are stored (profiles/rescue_tree.md, "Wide batch proofs and restore") --
+ * so the wide calls also have a COMPACT form that neither ships such a sibling nor hashes a parent of two empty subtrees:
+ *   absent_bits, ceil(M / 8) bytes: bit m (bit m & 7 of byte m >> 3; padding bits 0) is set when supplied node m is NOT STORED in the tree; `nodes`
+ *   then holds only the S = M - popcount stored ones, in the same order.  "Not stored" is by absence, not by value, so a host tree and a device
+ *   tree give the same bits: a key stored with the empty value has stored ancestors until dst_wtree_compact.
+ *   empties, n*32 bytes: E_0 .. E_{n-1}, the value of an empty subtree of every level (dst_rescue_empty_nodes), which the checking side computes
+ *   once per (empty leaf, depth).  THE TABLE IS BELIEVED: a check with a wrong table checks against another tree; compute it, do not receive it.
+ * A leaf is known-empty when its 32 bytes equal E_{n-1}, a supplied node when its bit is set, a parent exactly when both children are; such a
+ * parent is E_l of its level and is never hashed.  *digests = the parents actually computed; a proof in which everything is known-empty resolves
+ * to E_0 with 0 digests and no launch.  With absent_bits == NULL a call is the plain form: `nodes` holds all M, empties must be NULL.
+ * dst_rescue_empty_nodes (host only): out[32 l ..) = E_l for l = 0 .. n - 1 with E_{n-1} = the empty leaf, the chain dst_wtree_create computes.
+ * dst_wtree_multiproof: the leaves of `count` distinct keys below 2^depth, stored or not (an absent key has the leaf E_depth: absence is proven
+ * by the same call), and the supplied nodes.  absent_bits == NULL: plain, *num_nodes = M, byte-equal to dst_stree_multiproof wherever both
+ * trees exist.  Otherwise compact: absent_bits receives the bits, nodes the S stored nodes, *num_nodes = S.  *total (may be NULL) = M.  nodes ==
+ * NULL is the size query (a compact one looks the nodes up; absent_bits is then not written).  DST_ERR_ARG as dst_stree_multiproof.  On a device
+ * tree at most two launches whatever count is: one locates the count + M nodes in the level lists and leaves their flat positions on the device
+ * -- the host receives 4 bytes per node -- and one packs the stored leaves and nodes, which alone come back; no E_l crosses the bus, and a tree
+ * without nodes launches nothing.
+ * dst_rescue_multiproof_root_w / dst_rescue_verify_multiproof_w / dst_rescue_multiproof_paths_w: the narrow calls with absent_bits and empties
+ * behind num_nodes.  DST_ERR_ARG, found on the host before anything is queued, beyond the narrow calls': num_nodes != M - popcount(absent_bits)
+ * (plain: != M), a nonzero padding bit, absent_bits without empties or empties without absent_bits, an element of empties not below p.  device
+ * >= 0: one upload (the table with it), one launch per level THAT HAS A JOB, one gather launch for the expansion, one synchronisation, one copy
+ * back; device < 0: the same plan on the host.  dst_rescue_multiproof_last_levels: how many levels had a job in the calling thread's last
+ * successful dst_rescue_multiproof_root* / verify_multiproof* / multiproof_paths* call.  Errors: dst_rtree_last_error(NULL). */
+DST_API int dst_rescue_empty_nodes(const uint8_t empty_leaf[32] /* NULL: (0, 0) */, uint32_t n /* 2 .. 128 */, uint8_t* out /* n*32 */);
+DST_API int dst_rescue_multiproof_size_w(uint32_t n, const uint8_t* indices /* count*16 */, size_t count, size_t* num_nodes, uint64_t* digests);
+DST_API int dst_wtree_multiproof(const dst_wtree* t, const uint8_t* keys /* count*16 */, size_t count, uint8_t* leaves /* count*32 */,
+                                 uint8_t* nodes /* cap_nodes*32, or NULL */, size_t cap_nodes, size_t* num_nodes,
+                                 uint8_t* absent_bits /* ceil(M/8) bytes, or NULL */, size_t* total /* may be NULL */);
+DST_API int dst_rescue_multiproof_root_w(int device, uint32_t n, const uint8_t* indices /* count*16 */, const uint8_t* leaves /* count*32 */, size_t count,
+                                         const uint8_t* nodes /* num_nodes*32 */, size_t num_nodes, const uint8_t* absent_bits /* or NULL */,
+                                         const uint8_t* empties /* n*32, or NULL */, uint8_t root[32], uint64_t* digests /* may be NULL */, double* device_ms /* may be NULL */);
+DST_API int dst_rescue_verify_multiproof_w(int device, const uint8_t root[32], uint32_t n, const uint8_t* indices /* count*16 */, const uint8_t* leaves /* count*32 */,
+                                           size_t count, const uint8_t* nodes /* num_nodes*32 */, size_t num_nodes, const uint8_t* absent_bits /* or NULL */,
+                                           const uint8_t* empties /* n*32, or NULL */, int* ok, double* device_ms /* may be NULL */);
+DST_API int dst_rescue_multiproof_paths_w(int device, uint32_t n, const uint8_t* indices /* count*16 */, const uint8_t* leaves /* count*32 */, size_t count,
+                                          const uint8_t* nodes /* num_nodes*32 */, size_t num_nodes, const uint8_t* absent_bits /* or NULL */,
+                                          const uint8_t* empties /* n*32, or NULL */, uint8_t* paths /* count*n*32 */, uint8_t root[32], double* device_ms /* may be NULL */);
+DST_API uint32_t dst_rescue_multiproof_last_levels(void);
+/* save / load of a wide tree: dst_stree_save / dst_stree_load with BLOB KIND 3 -- the header of kind 2 with depth 1 .. 127, then depth + 1 level
+ * lengths as u64, every level's prefixes as 16-byte little-endian integers, every level's nodes, the leaf level first; exactly 64 + 8 * (depth +
+ * 1) + 48 * nodes bytes, the same from a host tree and a device tree.  Load refuses what dst_stree_load refuses, comparing all 128 bits of a
+ * prefix, and the kinds 1 and 2 (dst_stree_load refuses kind 3); audit == 0 hashes nothing, audit != 0 runs dst_wtree_audit and names a bad node
+ * in the text.  Failures of load: dst_wtree_last_error(NULL). */
+DST_API int dst_wtree_save(const dst_wtree* t, uint8_t* out /* cap bytes, or NULL */, size_t cap, size_t* len);
+DST_API int dst_wtree_load(int device, const uint8_t* blob, size_t len, uint32_t audit, dst_wtree** out);
 
 /* ---- host-side helpers that the Rust host would otherwise take from `rand` (they run on the CPU) -------------------- */
 DST_API void dst_prng_vector(const uint8_t seed[32], uint32_t count, uint8_t* out /* count*16 */);          /* field.rs:271 */

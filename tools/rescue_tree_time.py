@@ -6,6 +6,8 @@ device's own modular-multiplication rate sets.
     python tools/rescue_tree_time.py --sparse        sparse trees of depth 63 instead (dst_stree_set, dst_stree_paths), beside a dense 2^20 build
     python tools/rescue_tree_time.py --wide          wide-key sparse trees of depth 127 (dst_wtree_set beside dst_stree_set at depth 63 with as many keys, dst_wtree_paths,
                                                      dst_wtree_apply, dst_rescue_verify_paths_w)
+    python tools/rescue_tree_time.py --wide-batch    compact and plain multiproofs of the depth-127 tree of 2^20 keys beside the path check (bytes, digests, levels, device
+                                                     time), and dst_wtree_save / dst_wtree_load beside the set that builds the tree
     python tools/rescue_tree_time.py --remove        deletion on the depth-63 tree of 2^20 keys that --sparse builds (dst_stree_remove beside a dst_stree_set of the
                                                      same keys, dst_stree_compact after an apply of empties, dst_stree_get beside dst_stree_paths)
     python tools/rescue_tree_time.py --sequence      ordered writes with a witness each (dst_rtree_apply on the 2^20 tree, dst_stree_apply on a depth-63 tree
@@ -42,6 +44,7 @@ ap.add_argument("--verify", action="store_true", help="time dst_rescue_verify_wr
 ap.add_argument("--multiproof", action="store_true", help="time dst_rescue_multiproof_root of 256, 4 096, 65 536 distinct leaves of the dense 2^20 tree and of the depth-63 tree of 2^20 keys beside dst_rescue_verify_paths on the full paths of the same leaves; bytes and digests of both")
 ap.add_argument("--restore", action="store_true", help="time dst_rtree_audit / dst_stree_audit (one launch each) beside the builds of the same trees (dense 2^20; depth 63 with 2^20 keys), and dst_rtree_load / dst_stree_load of their saved forms beside the wall time of the rebuild")
 ap.add_argument("--wide", action="store_true", help="time the wide-key sparse trees: create + one dst_wtree_set of 2^16 and 2^20 random keys at depth 127 beside dst_stree_set of as many keys at depth 63, dst_wtree_paths of 2^16 keys, dst_wtree_apply of 2^12 writes, dst_rescue_verify_paths_w of 2^16 paths of 128 nodes")
+ap.add_argument("--wide-batch", action="store_true", help="compact and plain multiproofs (dst_wtree_multiproof, dst_rescue_verify_multiproof_w) of 256 and 4 096 keys -- members, absent, half and half -- of the depth-127 tree of 2^20 random keys beside dst_rescue_verify_paths_w on the full paths: bytes, digests, levels launched, device ms; dst_wtree_save / dst_wtree_load beside the set that builds the tree")
 ap.add_argument("sizes", nargs="*", type=int)
 args = ap.parse_args()
 lib = D.lib._open(os.path.abspath(args.lib)) if args.lib else None       # through the binding: one HIP runtime per process
@@ -111,18 +114,94 @@ if args.update:
     print("dst_rtree_paths of %d indices: %.3f ms wall; %d calls of dst_rtree_path: %.2f ms wall (ctypes, no conversion): %.0f x" % (count, c_many * 1e3, count, c_single * 1e3, c_single / c_many))
     t.close()
     sys.exit(0)
-if args.wide:
-    def wide_keys(count, seed, bits=127):
-        """-> distinct random keys as words [count, 2] (low half first), shuffled, and as many leaves"""
-        rng = np.random.default_rng(seed)
-        k = rng.integers(0, 1 << 64, size=(count + count // 8 + 16, 2), dtype=np.uint64)
-        k[:, 1] >>= np.uint64(128 - bits)
-        k = np.unique(k, axis=0)
-        rng.shuffle(k)
-        v = rng.integers(0, 1 << 64, size=(count, 2, 2), dtype=np.uint64)
-        v[..., 1] >>= np.uint64(1)
-        return np.ascontiguousarray(k[:count]), v
+def wide_keys(count, seed, bits=127):
+    """-> distinct random keys as words [count, 2] (low half first), shuffled, and as many leaves"""
+    rng = np.random.default_rng(seed)
+    k = rng.integers(0, 1 << 64, size=(count + count // 8 + 16, 2), dtype=np.uint64)
+    k[:, 1] >>= np.uint64(128 - bits)
+    k = np.unique(k, axis=0)
+    rng.shuffle(k)
+    v = rng.integers(0, 1 << 64, size=(count, 2, 2), dtype=np.uint64)
+    v[..., 1] >>= np.uint64(1)
+    return np.ascontiguousarray(k[:count]), v
 
+
+if args.wide_batch:
+    # compact and plain multiproofs of the depth-127 tree of 2^20 random keys (the keys of --wide), the path check they replace, and save / load
+    depth, n, runs = 127, 128, args.runs
+    k, v = wide_keys(1 << 20, 320)
+
+    def timed(fn, repeat):
+        """-> (the last result, the least wall ms of `repeat` calls after one warm-up)"""
+        out, wall = fn(), []
+        for _ in range(repeat):
+            t0 = time.perf_counter()
+            out = fn()
+            wall.append((time.perf_counter() - t0) * 1e3)
+        return out, min(wall)
+
+    t0 = time.perf_counter()
+    tree = D.WideSparseRescueTree(depth, device=0, lib=lib)
+    tree.set(k, v)
+    set_wall = (time.perf_counter() - t0) * 1e3
+    i = tree.info()
+    print("dst_wtree_set of 2^20 random keys into an empty depth-127 tree (one run): %.1f ms on the device, %.1f ms wall, %d digests, %d stored nodes = %.1f per key"
+          % (i["last_device_ms"], set_wall, i["last_digests"], i["nodes"], i["nodes"] / len(k)))
+    root = tree.root
+    table = D.empty_nodes(n, lib=lib, words=True)
+    absent_all, _ = wide_keys(1 << 12, 9)
+    rng = np.random.default_rng(8)
+    members_all = np.ascontiguousarray(k[rng.permutation(len(k))[:1 << 12]])
+    outcome = {}
+    for count in (256, 4096):
+        for mix, ask in (("members only", members_all[:count]), ("absent only", absent_all[:count]),
+                         ("half and half", np.concatenate([members_all[:count // 2], absent_all[:count // 2]]))):
+            ask = np.ascontiguousarray(ask)
+            (leaves_c, nodes_c, bits), wall_c = timed(lambda: tree.batch_proof(ask, words=True), runs)
+            (leaves_p, nodes_p, _), wall_p = timed(lambda: tree.batch_proof(ask, compact=False, words=True), runs)
+            words, wall_paths = timed(lambda: tree.paths_words(ask), runs)
+            bytes_c, bytes_p = leaves_c.nbytes + nodes_c.nbytes + len(bits), leaves_p.nbytes + nodes_p.nbytes
+
+            def device_ms(fn):
+                s, ms = {}, []
+                fn(s)                                   # warm-up
+                for _ in range(runs):
+                    assert fn(s) in (True, (-1, D.DST_PATH_OK))
+                    ms.append(s["device_ms"])
+                return min(ms), dict(s)
+            ms_c, s_c = device_ms(lambda s: D.verify_multiproof_wide(root, n, ask, leaves_c, nodes_c, bits, table, device=0, lib=lib, stats=s))
+            ms_p, s_p = device_ms(lambda s: D.verify_multiproof_wide(root, n, ask, leaves_p, nodes_p, device=0, lib=lib, stats=s))
+            ms_v, _ = device_ms(lambda s: D.verify_paths_wide(root, words, ask, leaves=leaves_p, device=0, lib=lib, stats=s))
+            d = {}
+            D.multiproof_root_wide(n, ask, leaves_c, nodes_c, bits, table, device=-1 if count == 256 else 0, lib=lib, stats=d)
+            _, plain_digests = D.multiproof_size_wide(n, ask, lib=lib)
+            outcome[(count, mix)] = (ms_c, ms_v)
+            print("%d keys, %s: plain %d bytes (%d nodes), compact %d bytes (%d nodes + %d bytes of bits), paths %d bytes; digests compact %d (%.1f per key) in %d levels launched, plain %d in %d; "
+                  "device ms: verify_multiproof_wide compact %.3f, plain %.3f, verify_paths_wide on the full paths %.3f (each the min of %d after one warm-up); "
+                  "wall ms: batch_proof compact %.2f, plain %.2f, paths %.2f"
+                  % (count, mix, bytes_p, len(nodes_p), bytes_c, len(nodes_c), len(bits), words.nbytes, d["digests"], d["digests"] / count, s_c["levels"], plain_digests, s_p["levels"],
+                     ms_c, ms_p, ms_v, runs, wall_c, wall_p, wall_paths))
+    for count in (256, 4096):
+        ms_c, ms_v = outcome[(count, "absent only")]
+        print("the condition, %d absent keys: compact check %.3f ms %s verify_paths_wide %.3f ms on the device (factor %.2f)" % (count, ms_c, "<" if ms_c < ms_v else ">=", ms_v, ms_v / ms_c))
+    blob, save_wall = timed(tree.to_blob, 3)
+    print("to_blob: %d bytes, %.1f ms wall (min of 3 after one warm-up; one copy of the nodes from the device)" % (len(blob), save_wall))
+    for audit in (False, True):
+        wall, audit_ms = [], []
+        for _ in range(1 + 3):
+            t0 = time.perf_counter()
+            loaded = D.WideSparseRescueTree.from_blob(blob, device=0, audit=audit, lib=lib)
+            wall.append((time.perf_counter() - t0) * 1e3)
+            assert loaded.root == root
+            if audit:
+                loaded.audit()
+                audit_ms.append(loaded.audit_ms)
+            loaded.close()
+        print("from_blob %s audit: %.1f ms wall (min of 3 after one warm-up)%s; the set that builds the tree: %.1f ms on the device, %.1f ms wall"
+              % ("with" if audit else "without", min(wall[1:]), ", dst_wtree_audit alone %.1f ms on the device" % min(audit_ms[1:]) if audit else "", i["last_device_ms"], set_wall))
+    tree.close()
+    sys.exit(0)
+if args.wide:
     def one_set(make, depth, k, v, runs):
         """create + one set, `runs` times after one warm-up -> (the last tree, device ms of each run, the least wall time in ms)"""
         ms, wall, t = [], [], None

@@ -628,6 +628,8 @@ int dst_proof_info(const uint8_t* proof, size_t len, dst_proof_info_t* info) {
 #include "host/stree_impl.h"
 // ---- checking paths and the witnesses of ordered writes (dst_rescue_path_roots, dst_rescue_verify_*, their _w forms): no tree, no context -----
 #include "host/path_verify_impl.h"
+// ---- following ordered writes with held paths (dst_rescue_refresh_paths, its _w form): the same checks, then the paths under the new root ------
+#include "host/path_refresh_impl.h"
 // ---- compressed batch openings (dst_rescue_multiproof_*, dst_rtree_multiproof, dst_stree_multiproof): every shared ancestor once ------------
 #include "host/multiproof_impl.h"
 

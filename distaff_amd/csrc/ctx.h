@@ -543,5 +543,11 @@ int k_rescue_tree_audit(hipStream_t stream, const fe* nodes, size_t leaves, unsi
 int k_rescue_stree_audit(hipStream_t stream, const fe* nodes, const uint64_t* pref, const uint64_t* levels, const fe* empties, uint32_t depth, size_t first, size_t count,
                          unsigned long long* first_bad);
 int k_rescue_path_roots(hipStream_t stream, const fe* paths, uint32_t n, const stree_wide* indices, size_t count, const fe* alt_leaves, uint32_t mode, fe* out /* 2 per chain */, uint32_t* bad);
+// following writes (host/path_refresh.h): the 2 count chains of RESCUE_PATH_BOTH in ONE launch, the substitute-leaf chains also storing their node after
+// every level k = 1 .. n - 2: out = the 2 count roots, then mid[k - 1][i], n - 2 levels of count nodes.  Then the refreshed paths in one launch: out[j][k] =
+// sel[j][k] < 0 ? held[j][k] : the node of write sel[j][k] for position k (its leaf for k <= 1, mid[k - 2][sel] above).  All device
+int k_rescue_path_chains(hipStream_t stream, const fe* paths, uint32_t n, const uint64_t* indices, size_t count, const fe* leaves, fe* out /* 2 count roots | (n - 2) count nodes */, uint32_t* bad);
+int k_rescue_path_chains(hipStream_t stream, const fe* paths, uint32_t n, const stree_wide* indices, size_t count, const fe* leaves, fe* out, uint32_t* bad);
+int k_rescue_path_refresh(hipStream_t stream, const fe* held, const int32_t* sel, const fe* leaves, const fe* mid, size_t count, uint32_t n, size_t held_paths, fe* out, uint32_t* bad);
 int k_rescue_stree_audit(hipStream_t stream, const fe* nodes, const stree_wide* pref, const uint64_t* levels, const fe* empties, uint32_t depth, size_t first, size_t count,
                          unsigned long long* first_bad);

@@ -13,9 +13,10 @@ static int pv_fail(int code, const char* why) { g_rtree_error = why; return code
 static const char* const PV_NOT_BELOW_P = "an element of the paths, leaves or roots is not below the modulus";
 
 // the chains of `count` paths on the host: one level of ALL chains per rescue_digest_many_host call, so that its two-at-a-time form runs on full
-// groups.  out = 2 elements per chain, in the order of k_rescue_path_roots.  The caller has checked that every element is below p.
+// groups.  out = 2 elements per chain, in the order of k_rescue_path_roots.  The caller has checked that every element is below p.  mid (or
+// nullptr; RESCUE_PATH_BOTH) receives what k_rescue_path_chains stores: the substitute-leaf chain of path i after level k at mid[k - 1][i], k <= n - 2
 template <class K>
-static void path_roots_host(const uint8_t* paths, uint32_t n, const K* indices, size_t count, const uint8_t* leaves, uint32_t mode, u128* out) {
+static void path_roots_host(const uint8_t* paths, uint32_t n, const K* indices, size_t count, const uint8_t* leaves, uint32_t mode, u128* out, u128* mid = nullptr) {
     const size_t chains = mode == RESCUE_PATH_BOTH ? 2 * count : count;
     std::vector<u128> in(4 * chains);
     for (size_t c = 0; c < chains; c++) {                                  // the running value starts as the leaf
@@ -30,6 +31,8 @@ static void path_roots_host(const uint8_t* paths, uint32_t n, const K* indices, 
             memcpy(in.data() + 4 * c + 2 * (1 - right), paths + 32 * ((size_t)n * i + k), 32);
         }
         rescue_digest_many_host(in.data(), chains, out);
+        if (mid && k + 1 < n)
+            memcpy(mid + 2 * (size_t)(k - 1) * count, out + 2 * count, 32 * count);
     }
 }
 

@@ -715,10 +715,15 @@ int k_rescue_tree_scatter_from(hipStream_t stream, fe* nodes, const uint32_t* po
 //      (RESCUE_PATH_OWN), with alt[i] in its place (RESCUE_PATH_ALT), or both over one copy of the paths (RESCUE_PATH_BOTH: chain c < count is
 //      path c with its own leaf, chain count + i path i with alt[i]).  out[c] = what chain c resolves to; `bad` receives 1 when an element a
 //      chain reads -- its leaf, every sibling -- is not below p. ---------------------------------------------------------------------------------
+// Following writes (dst_rescue_refresh_paths, host/path_refresh.h) needs the chains of the written leaves node by node, not only their ends: with
+// STORE (RESCUE_PATH_BOTH only) the substitute-leaf chain of path i (c = count + i) also writes its running digest after level k = 1 .. n - 2 to
+// mid[k - 1][i] -- level-major, n - 2 levels of `count` nodes, so that neighbouring chains store side by side -- where mid = out + 2 chains: the
+// chain nodes follow the roots in one buffer, so both forms take the same
+// arguments.  Each lane form states the chain once, STORE is a compile-time switch, and the instantiations without it are the code they were.
 // the six-lanes-of-eight form (rescue_parent_spread): lanes 5, 4 hold l0, l1 and lanes 3, 2 hold r0, r1.  After the permutation the digest sits in
 // lanes 5, 4; it reaches the side bit k - 1 of the index names through the group's LDS slots 5, 4, and the other side loads path[k].  A group past
-// the end is given chain 0, keeps the barriers and stores nothing.
-template <class K>
+// the end is given chain 0, keeps the barriers and stores nothing.  The lanes that hand the digest over are the lanes that store it: no barrier more.
+template <class K, bool STORE = false>
 __global__ void __launch_bounds__(RESCUE_THREADS) rescue_path_root_spread_kernel(const fe* __restrict__ paths, uint32_t n, const K* __restrict__ indices, size_t count,
                                                                                 const fe* __restrict__ alt, uint32_t mode, size_t chains, fe* __restrict__ out, uint32_t* __restrict__ bad) {
     __shared__ fe xch[RESCUE_THREADS];
@@ -740,7 +745,10 @@ __global__ void __launch_bounds__(RESCUE_THREADS) rescue_path_root_spread_kernel
     rescue_permute_lane(v, e, xs);
 #pragma unroll 1
     for (uint32_t k = 2; k < n; k++) {
-        if (e == 5u || e == 4u) xs[e] = v;
+        if (e == 5u || e == 4u) {
+            xs[e] = v;
+            if (STORE && live && c >= count) out[2 * (chains + (k - 2u) * count + i) + (5u - e)] = v;        // mid[k - 2][i]: the node after level k - 1
+        }
         __syncthreads();
         v = fe_zero();
         if (works) {
@@ -757,7 +765,7 @@ __global__ void __launch_bounds__(RESCUE_THREADS) rescue_path_root_spread_kernel
 }
 // one chain per lane, for more chains than RESCUE_SPREAD_MAX: the digest is stated once, in a loop over the levels; only the running digest, the
 // index and the chain's base address live across it.  Lanes read their paths n * 32 bytes apart: a level is milliseconds of arithmetic.
-template <class K>
+template <class K, bool STORE = false>
 __global__ void __launch_bounds__(RESCUE_THREADS) rescue_path_root_kernel(const fe* __restrict__ paths, uint32_t n, const K* __restrict__ indices, size_t count,
                                                                          const fe* __restrict__ alt, uint32_t mode, size_t chains, fe* __restrict__ out, uint32_t* __restrict__ bad) {
     const size_t c = (size_t)blockIdx.x * RESCUE_THREADS + threadIdx.x;
@@ -775,24 +783,56 @@ __global__ void __launch_bounds__(RESCUE_THREADS) rescue_path_root_kernel(const 
         const bool right = stree_bit(idx, k - 1u);                     // the running node is the right child: the sibling goes first
         const fe c0 = d0, c1 = d1;
         rescue_digest4(rescue_pick(right, s0, c0), rescue_pick(right, s1, c1), rescue_pick(right, c0, s0), rescue_pick(right, c1, s1), d0, d1);
+        if (STORE && c >= count && k + 1u < n) {                       // mid[k - 1][i]: the node after level k
+            fe* const m = out + 2 * (chains + (k - 1u) * count + i);
+            m[0] = d0; m[1] = d1;
+        }
     }
     out[2 * c] = d0; out[2 * c + 1] = d1;
 }
+// the refreshed paths (host/path_refresh.h): one lane per (held path, position k, element).  sel = the write that supplies the position, below 0
+// to keep the held node; position 0 takes the written leaf, position k >= 1 the write's chain node at height k - 1 -- the written leaf again for
+// k = 1, mid[k - 2][sel] above (level-major over `count` writes).  Every element of the held paths is read, and `bad` receives 1 when one is not below p.
+__global__ void rescue_path_refresh_kernel(const fe* __restrict__ held, const int32_t* __restrict__ sel, const fe* __restrict__ leaves, const fe* __restrict__ mid, size_t count, uint32_t n,
+                                           size_t total /* held paths * n * 2 */, fe* __restrict__ out, uint32_t* __restrict__ bad) {
+    const size_t t = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (t >= total) return;
+    const uint32_t k = (uint32_t)((t >> 1) % n), el = (uint32_t)(t & 1);
+    fe v = held[t];
+    if (!rescue_canonical(v)) *bad = 1u;
+    const int32_t s = sel[t >> 1];
+    if (s >= 0) v = k <= 1u ? leaves[2 * (size_t)s + el] : mid[2 * ((size_t)(k - 2u) * count + (size_t)s) + el];
+    out[t] = v;
+}
+// store: RESCUE_PATH_BOTH, and out is 2 count roots followed by n - 2 levels of count chain nodes
 template <class K>
-static int rescue_path_roots(hipStream_t stream, const fe* paths, uint32_t n, const K* indices, size_t count, const fe* alt_leaves, uint32_t mode, fe* out, uint32_t* bad) {
+static int rescue_path_roots(hipStream_t stream, const fe* paths, uint32_t n, const K* indices, size_t count, const fe* alt_leaves, uint32_t mode, fe* out, bool store, uint32_t* bad) {
     const size_t chains = mode == RESCUE_PATH_BOTH ? 2 * count : count;
     const bool spread = chains <= RESCUE_SPREAD_MAX;
     const size_t per_block = spread ? RESCUE_THREADS / 8 : RESCUE_THREADS;
     const dim3 grid((unsigned)((chains + per_block - 1) / per_block)), block(RESCUE_THREADS);
-    if (spread) hipLaunchKernelGGL(rescue_path_root_spread_kernel<K>, grid, block, 0, stream, paths, n, indices, count, alt_leaves, mode, chains, out, bad);
+    if (store && spread) hipLaunchKernelGGL((rescue_path_root_spread_kernel<K, true>), grid, block, 0, stream, paths, n, indices, count, alt_leaves, mode, chains, out, bad);
+    else if (store) hipLaunchKernelGGL((rescue_path_root_kernel<K, true>), grid, block, 0, stream, paths, n, indices, count, alt_leaves, mode, chains, out, bad);
+    else if (spread) hipLaunchKernelGGL(rescue_path_root_spread_kernel<K>, grid, block, 0, stream, paths, n, indices, count, alt_leaves, mode, chains, out, bad);
     else hipLaunchKernelGGL(rescue_path_root_kernel<K>, grid, block, 0, stream, paths, n, indices, count, alt_leaves, mode, chains, out, bad);
     return hipGetLastError() == hipSuccess ? 0 : -1;
 }
 int k_rescue_path_roots(hipStream_t stream, const fe* paths, uint32_t n, const uint64_t* indices, size_t count, const fe* alt_leaves, uint32_t mode, fe* out, uint32_t* bad) {
-    return rescue_path_roots(stream, paths, n, indices, count, alt_leaves, mode, out, bad);
+    return rescue_path_roots(stream, paths, n, indices, count, alt_leaves, mode, out, false, bad);
 }
 int k_rescue_path_roots(hipStream_t stream, const fe* paths, uint32_t n, const stree_wide* indices, size_t count, const fe* alt_leaves, uint32_t mode, fe* out, uint32_t* bad) {
-    return rescue_path_roots(stream, paths, n, indices, count, alt_leaves, mode, out, bad);
+    return rescue_path_roots(stream, paths, n, indices, count, alt_leaves, mode, out, false, bad);
+}
+int k_rescue_path_chains(hipStream_t stream, const fe* paths, uint32_t n, const uint64_t* indices, size_t count, const fe* leaves, fe* out, uint32_t* bad) {
+    return rescue_path_roots(stream, paths, n, indices, count, leaves, RESCUE_PATH_BOTH, out, true, bad);
+}
+int k_rescue_path_chains(hipStream_t stream, const fe* paths, uint32_t n, const stree_wide* indices, size_t count, const fe* leaves, fe* out, uint32_t* bad) {
+    return rescue_path_roots(stream, paths, n, indices, count, leaves, RESCUE_PATH_BOTH, out, true, bad);
+}
+int k_rescue_path_refresh(hipStream_t stream, const fe* held, const int32_t* sel, const fe* leaves, const fe* mid, size_t count, uint32_t n, size_t held_paths, fe* out, uint32_t* bad) {
+    const size_t total = 2 * held_paths * n;
+    hipLaunchKernelGGL(rescue_path_refresh_kernel, dim3((unsigned)((total + HASH_THREADS - 1) / HASH_THREADS)), dim3(HASH_THREADS), 0, stream, held, sel, leaves, mid, count, n, total, out, bad);
+    return hipGetLastError() == hipSuccess ? 0 : -1;
 }
 
 // ---- multiproofs (dst_rescue_multiproof_root, dst_rescue_verify_multiproof, dst_rescue_multiproof_paths; host/multiproof_plan.h): the leaves of a

@@ -60,7 +60,7 @@ EXPORTS = ["dst_ctx_create", "dst_ctx_destroy", "dst_last_error", "dst_phase_ms"
            "dst_rtree_destroy", "dst_rtree_last_error", "dst_rtree_update", "dst_rtree_update_ms", "dst_rtree_paths", "dst_rtree_tapes_many",
            "dst_stree_create", "dst_stree_set", "dst_stree_root", "dst_stree_paths", "dst_stree_tapes_many", "dst_stree_read_level", "dst_stree_info",
            "dst_stree_destroy", "dst_stree_last_error", "dst_rtree_apply", "dst_stree_apply", "dst_rescue_path_tapes",
-           "dst_rescue_path_roots", "dst_rescue_verify_paths", "dst_rescue_verify_writes",
+           "dst_rescue_path_roots", "dst_rescue_verify_paths", "dst_rescue_verify_writes", "dst_rescue_refresh_paths", "dst_rescue_refresh_paths_w", "dst_rescue_refresh_last_gather_ms",
            "dst_stree_remove", "dst_stree_compact", "dst_stree_get",
            "dst_rescue_multiproof_size", "dst_rtree_multiproof", "dst_stree_multiproof", "dst_rescue_multiproof_root", "dst_rescue_verify_multiproof",
            "dst_rescue_multiproof_paths",
@@ -132,6 +132,9 @@ def _open(path):
     lib = ctypes.CDLL(path)
     lib.dst_last_error.restype = ctypes.c_char_p
     lib.dst_last_error.argtypes = [ctypes.c_void_p]
+    if hasattr(lib, "dst_rescue_refresh_last_gather_ms"):              # a library named by DISTAFF_HIP_LIB may predate it
+        lib.dst_rescue_refresh_last_gather_ms.restype = ctypes.c_double
+        lib.dst_rescue_refresh_last_gather_ms.argtypes = []
     if hasattr(lib, "dst_last_bad_step"):                              # a library named by DISTAFF_HIP_LIB may predate it
         lib.dst_last_bad_step.restype = ctypes.c_int64
         lib.dst_last_bad_step.argtypes = [ctypes.c_void_p]
@@ -282,6 +285,13 @@ def _rtree_error(lib, handle=None):
     return (lib.dst_rtree_last_error(handle) or b"").decode()
 
 
+def _refresh_gather_ms(lib):
+    """dst_rescue_refresh_last_gather_ms of a library however it was opened (the tests pass handles that did not come through _open)"""
+    lib.dst_rescue_refresh_last_gather_ms.restype = ctypes.c_double
+    lib.dst_rescue_refresh_last_gather_ms.argtypes = []
+    return lib.dst_rescue_refresh_last_gather_ms()
+
+
 def rescue_digest(values, device=0, lib=None):
     """utils::hasher::digest (src/utils/hasher.rs:12) of every 4-tuple of `values` (a sequence of 4-tuples of ints, or uint64 words
     [count, 4, 2]) through dst_rescue_digest_many -> uint64 words [count, 2, 2] (arr_to_ints turns them into ints).  device >= 0: on that GPU;
@@ -429,6 +439,43 @@ def verify_writes(root_before, indices, paths, leaves, roots=None, device=0, lib
     if stats is not None:
         stats["device_ms"] = ms.value
     return first.value, why.value, tuple(arr_to_ints(after))
+
+
+def refresh_paths(root_before, indices, paths, leaves, held_indices, held_paths, roots=None, device=0, lib=None, stats=None, _wide=False):
+    """the paths a client holds, carried across the ordered writes of an apply() without the tree (dst_rescue_refresh_paths) -> (first_bad, why,
+    root_after, new_paths): the writes are checked as verify_writes checks them; when they hold, new_paths[j] is the path of held_indices[j] under
+    root_after (a list of lists of pairs of ints), else new_paths is None.  `paths` and `held_paths` in either shape verify_writes accepts.  The held
+    paths themselves are not checked: verify_paths(root_after, new_paths, held_indices) does that.  On a device: one launch for all 2 * count chains
+    and one that gathers the paths; stats (a dict) receives device_ms, events around both, and gather_ms, the second launch's part of it."""
+    lib = lib or load()
+    idx, hidx = _Keys(indices, _wide), _Keys(held_indices, _wide)
+    w, n = _path_words(paths, idx.size)
+    hw, hn = _path_words(held_paths, hidx.size)
+    if idx.size and hidx.size and hn != n:
+        raise DistaffError(DST_ERR_ARG, "paths of one length")
+    n = n if idx.size else hn
+    new = _nodes_for(leaves, idx.size, "leaves")
+    claimed = _nodes_for(roots, idx.size, "roots") if roots is not None else None
+    r0 = _nodes_for([tuple(root_before)], 1, "roots")
+    after = np.zeros((2, 2), dtype=np.uint64)
+    out = np.zeros((max(hidx.size, 1), n, 2, 2), dtype=np.uint64)
+    first, why, ms = ctypes.c_int64(-1), ctypes.c_uint32(0), ctypes.c_double(0)
+    r = getattr(lib, "dst_rescue_refresh_paths" + idx.suffix)(ctypes.c_int(device), _ptr(r0), _ptr(w) if idx.size else None, ctypes.c_uint32(n), idx.ptr, _ptr(new) if idx.size else None,
+                                     _ptr(claimed) if claimed is not None and idx.size else None, ctypes.c_size_t(idx.size), hidx.ptr, _ptr(hw) if hidx.size else None,
+                                     ctypes.c_size_t(hidx.size), _ptr(out), ctypes.byref(first), ctypes.byref(why), _ptr(after), ctypes.byref(ms))
+    if r != DST_OK:
+        raise DistaffError(r, _rtree_error(lib) or "dst_rescue_refresh_paths failed")
+    if stats is not None:
+        stats["device_ms"], stats["gather_ms"] = ms.value, _refresh_gather_ms(lib)
+    if first.value >= 0:
+        return first.value, why.value, tuple(arr_to_ints(after)), None
+    nodes = _pairs(out[:hidx.size])
+    return first.value, why.value, tuple(arr_to_ints(after)), [nodes[j * n:(j + 1) * n] for j in range(hidx.size)]
+
+
+def refresh_paths_wide(root_before, indices, paths, leaves, held_indices, held_paths, roots=None, device=0, lib=None, stats=None):
+    """refresh_paths for the witnesses of WideSparseRescueTree.apply: paths of up to 128 nodes, indices of up to 127 bits (dst_rescue_refresh_paths_w)"""
+    return refresh_paths(root_before, indices, paths, leaves, held_indices, held_paths, roots, device, lib, stats, _wide=True)
 
 
 def path_tapes_wide(paths, indices, what=3, lib=None):

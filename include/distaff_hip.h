@@ -236,6 +236,28 @@ DST_API int dst_rescue_verify_writes(int device, const uint8_t root_before[32], 
                                      const uint8_t* leaves /* count*32 */, const uint8_t* roots /* count*32, or NULL */, size_t count,
                                      int64_t* first_bad, uint32_t* why, uint8_t root_after[32], double* device_ms);
 
+/* following ordered writes with HELD PATHS, without the tree: a client that holds a root and the paths of `held` keys of its own receives the
+ * witnesses of a dst_rtree_apply / dst_stree_apply batch and leaves with root_after and its paths under root_after.  The writes are verified
+ * first, exactly as dst_rescue_verify_writes verifies them with the same arguments -- first_bad, why and root_after are that call's.  Nothing is
+ * written from witnesses that do not hold: when *first_bad >= 0 the call returns DST_OK and out_paths is untouched to the byte.  Otherwise
+ * out_paths[j] is the path of held_indices[j] after the last write: with c_i[0] = leaves[i], c_i[t] = digest(c_i[t-1], paths[i][t]) ordered by
+ * bit t-1 of indices[i] (the nodes above write i's leaf right after it), node 0 is leaves[i] of the LAST write i with indices[i] ==
+ * held_indices[j], node k >= 1 is c_i[k-1] of the LAST write i with indices[i] >> (k-1) == (held_indices[j] >> (k-1)) ^ 1, and a node no write
+ * supplies is held_paths[j]'s.  THE HELD PATHS ARE NOT CHECKED: one that resolved to root_before resolves to root_after; one that did not is the
+ * caller's problem, found with dst_rescue_verify_paths(root_after, out_paths, ...).  Held indices may repeat; out_paths may be held_paths
+ * itself.  held = 0: the call is dst_rescue_verify_writes.  count = 0: out_paths is a copy of held_paths, root_after = root_before.
+ * DST_ERR_ARG as above, before anything is written, also for a held index not below 2^(n-1), held >= 2^31 and an element of held_paths not
+ * below p.  device >= 0: one upload, ONE launch for all 2*count chains, one launch that gathers the paths, one synchronisation, one copy back,
+ * whatever count, held and n are; *device_ms: events around the two launches.  device < 0: on the host, one thread, no HIP call. */
+DST_API int dst_rescue_refresh_paths(int device, const uint8_t root_before[32], const uint8_t* paths /* count*n*32 */, uint32_t n, const uint64_t* indices,
+                                     const uint8_t* leaves /* count*32 */, const uint8_t* roots /* count*32, or NULL */, size_t count,
+                                     const uint64_t* held_indices, const uint8_t* held_paths /* held*n*32 */, size_t held,
+                                     uint8_t* out_paths /* held*n*32; may be held_paths itself */,
+                                     int64_t* first_bad, uint32_t* why, uint8_t root_after[32] /* may be NULL */, double* device_ms);
+/* of *device_ms of the calling thread's last dst_rescue_refresh_paths / dst_rescue_refresh_paths_w, the part of the launch that gathers the paths
+ * (an event between the two launches); 0 when that call ran on the host, gathered nothing or failed before its launches */
+DST_API double dst_rescue_refresh_last_gather_ms(void);
+
 /* ---- compressed batch openings (multiproofs): the paths of many leaves without the nodes they share.  `count` independent paths are
  * count*n*32 bytes and count*(n-1) digests to check, however much of the tree they share; a multiproof ships every needed node once and its
  * check computes every shared ancestor once.  It is the node set of the reference's BatchMerkleProof (prove_batch / verify_batch,
@@ -442,6 +464,12 @@ DST_API int dst_rescue_verify_writes_w(int device, const uint8_t root_before[32]
                                        uint32_t* why, uint8_t root_after[32] /* may be NULL */, double* device_ms);
 DST_API int dst_rescue_path_tapes_w(const uint8_t* paths /* count*n*32 */, uint32_t n, const uint8_t* indices /* count*16 */, size_t count, uint32_t what,
                                     uint8_t* tape_a, uint8_t* tape_b, size_t cap_elems_each, size_t* elems_each);
+/* dst_rescue_refresh_paths over 16-byte little-endian indices and held indices, 2 <= n <= 128: the witnesses of dst_wtree_apply */
+DST_API int dst_rescue_refresh_paths_w(int device, const uint8_t root_before[32], const uint8_t* paths /* count*n*32 */, uint32_t n, const uint8_t* indices /* count*16 */,
+                                       const uint8_t* leaves /* count*32 */, const uint8_t* roots /* count*32, or NULL */, size_t count,
+                                       const uint8_t* held_indices /* held*16 */, const uint8_t* held_paths /* held*n*32 */, size_t held,
+                                       uint8_t* out_paths /* held*n*32; may be held_paths itself */,
+                                       int64_t* first_bad, uint32_t* why, uint8_t root_after[32] /* may be NULL */, double* device_ms);
 
 /* ---- multiproofs of wide trees, plain and COMPACT ------------------------------------------------------------------------------------------------
  * The multiproof above over 16-byte indices and 2 <= n <= 128: the same node set, the same order (level n - 1 first, ascending by position within

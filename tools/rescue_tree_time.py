@@ -14,6 +14,8 @@ device's own modular-multiplication rate sets.
                                                      of 2^20 keys), beside the loop of single-leaf updates and single paths they replace
     python tools/rescue_tree_time.py --verify        checking the witnesses of those ordered writes (dst_rescue_verify_writes, one launch) beside the apply that
                                                      made them, the same check on the host for 256 writes, and dst_rescue_verify_paths of 4 096 paths
+    python tools/rescue_tree_time.py --refresh       following those writes with held paths (dst_rescue_refresh_paths: the chain launch that also stores its nodes, then
+                                                     a gather) beside dst_rescue_verify_writes on the same batches, and beside asking the tree for the paths again
     python tools/rescue_tree_time.py --multiproof    compressed batch openings: bytes, digests and the device time of dst_rescue_multiproof_root beside
                                                      dst_rescue_verify_paths on the full paths of the same leaves (K = 256, 4 096, 65 536; both trees above)
     python tools/rescue_tree_time.py --restore       save, restore, audit: dst_rtree_audit beside dst_rtree_build_ms of the dense 2^20 tree, dst_stree_audit beside the
@@ -41,6 +43,7 @@ ap.add_argument("--sparse", action="store_true", help="time dst_stree_set (2^12,
 ap.add_argument("--remove", action="store_true", help="time dst_stree_remove of 1, 256, 65 536 stored keys of the 2^20-key depth-63 tree, each just after a dst_stree_set of the same keys; dst_stree_compact after an apply of 65 536 empties; dst_stree_get of 4 096 keys beside dst_stree_paths")
 ap.add_argument("--sequence", action="store_true", help="time dst_rtree_apply / dst_stree_apply (1, 256, 4 096, 65 536 ordered writes) and, for 256, the loop of update + path calls")
 ap.add_argument("--verify", action="store_true", help="time dst_rescue_verify_writes on the witnesses of dst_rtree_apply / dst_stree_apply (256, 4 096, 65 536 writes), on the host for 256, and dst_rescue_verify_paths of 4 096 paths")
+ap.add_argument("--refresh", action="store_true", help="time dst_rescue_refresh_paths (256 and 4 096 held paths across 256, 4 096, 65 536 ordered writes) beside dst_rescue_verify_writes on the same batches: dense 2^20, sparse depth 63 with 2^20 keys, wide depth 127 with 2^16 keys")
 ap.add_argument("--multiproof", action="store_true", help="time dst_rescue_multiproof_root of 256, 4 096, 65 536 distinct leaves of the dense 2^20 tree and of the depth-63 tree of 2^20 keys beside dst_rescue_verify_paths on the full paths of the same leaves; bytes and digests of both")
 ap.add_argument("--restore", action="store_true", help="time dst_rtree_audit / dst_stree_audit (one launch each) beside the builds of the same trees (dense 2^20; depth 63 with 2^20 keys), and dst_rtree_load / dst_stree_load of their saved forms beside the wall time of the rebuild")
 ap.add_argument("--wide", action="store_true", help="time the wide-key sparse trees: create + one dst_wtree_set of 2^16 and 2^20 random keys at depth 127 beside dst_stree_set of as many keys at depth 63, dst_wtree_paths of 2^16 keys, dst_wtree_apply of 2^12 writes, dst_rescue_verify_paths_w of 2^16 paths of 128 nodes")
@@ -545,6 +548,102 @@ if args.multiproof:
 
     time_multiproofs("sparse depth %d, 2^20 keys" % DEPTH, s, DEPTH + 1, sparse_draw, s.lib.dst_stree_multiproof, s.paths_words)
     s.close()
+    sys.exit(0)
+if args.refresh:
+    import ctypes
+    REFRESH_SEED = 4040
+    vp = lambda x: x.ctypes.data_as(ctypes.c_void_p)  # noqa: E731
+
+    def time_refreshes(name, tree, apply, open_paths, n, draw, wide=False):
+        """dst_rescue_refresh_paths beside dst_rescue_verify_writes on the same batch, in this process: per repeat the held paths are opened (wall,
+        for orientation: what a client without the call would ask the tree for again), the batch is applied, its witnesses are verified and the
+        held paths are refreshed; the refreshed paths are then the tree's.  Device ms: events around the chain launch (verify), around the chain
+        launch and the gather (refresh), around the gather alone (dst_rescue_refresh_last_gather_ms).  Wall of refresh: the C call with the plan, the upload and the copy back."""
+        rng = np.random.default_rng(REFRESH_SEED)
+        L = tree.lib
+        verify, refresh = (L.dst_rescue_verify_writes_w, L.dst_rescue_refresh_paths_w) if wide else (L.dst_rescue_verify_writes, L.dst_rescue_refresh_paths)
+        first, why, dms, after = ctypes.c_int64(0), ctypes.c_uint32(0), ctypes.c_double(0), np.zeros((2, 2), dtype=np.uint64)
+        for count in (256, 4096, 65536):
+            for held in (256, 4096):
+                v_ms, r_ms, g_ms, r_wall, p_wall = [], [], [], [], []
+                for _ in range(1 + args.runs):      # the first is the warm-up: code
+                    idx, new = draw(rng, count)
+                    hidx = np.ascontiguousarray(np.concatenate([idx[rng.integers(0, count, size=held // 4)], draw(rng, held - held // 4)[0]]))   # a quarter of the held keys are written
+                    t0 = time.perf_counter()
+                    mine = open_paths(hidx)
+                    p_wall.append((time.perf_counter() - t0) * 1e3)
+                    paths, roots = np.zeros((count, n, 2, 2), dtype=np.uint64), np.zeros((count, 2, 2), dtype=np.uint64)
+                    before = D.ints_to_arr(tree.root)
+                    assert apply(tree._h, vp(idx), vp(new), ctypes.c_size_t(count), vp(paths), vp(roots)) == 0
+                    common = (ctypes.c_int(0), vp(before), vp(paths), ctypes.c_uint32(n), vp(idx), vp(new), vp(roots), ctypes.c_size_t(count))
+                    tail = (ctypes.byref(first), ctypes.byref(why), vp(after), ctypes.byref(dms))
+                    assert verify(*(common + tail)) == 0 and (first.value, why.value) == (-1, 0)
+                    v_ms.append(dms.value)
+                    t0 = time.perf_counter()
+                    r = refresh(*(common + (vp(hidx), vp(mine), ctypes.c_size_t(held), vp(mine)) + tail))
+                    r_wall.append((time.perf_counter() - t0) * 1e3)
+                    assert r == 0 and (first.value, why.value) == (-1, 0) and tuple(D.arr_to_ints(after)) == tree.root
+                    r_ms.append(dms.value)
+                    g_ms.append(D.lib._refresh_gather_ms(L))
+                    assert mine.tobytes() == open_paths(hidx).tobytes()
+                v_ms, r_ms, g_ms, r_wall, p_wall = v_ms[1:], r_ms[1:], g_ms[1:], r_wall[1:], p_wall[1:]
+                print("%s: %d writes, %d held paths of %d nodes (%s): refresh_paths %.3f ms on the device (min of %d after one warm-up; all: %s); verify_writes of the same batches %.3f ms "
+                      "(min; all: %s); the gather launch alone %.3f ms (min; all: %s); refresh - verify = %+.3f ms (min - min; the gather and the %d bytes the chains store per write); refresh %.2f ms wall with the plan (min; all: %s); "
+                      "tree.paths(held) %.2f ms wall (min)"
+                      % (name, count, held, n, "six-lane form" if 2 * count <= (1 << 15) else "one-lane form", min(r_ms), len(r_ms), " ".join("%.3f" % x for x in r_ms), min(v_ms),
+                         " ".join("%.3f" % x for x in v_ms), min(g_ms), " ".join("%.3f" % x for x in g_ms), min(r_ms) - min(v_ms), 32 * (n - 2), min(r_wall), " ".join("%.2f" % x for x in r_wall), min(p_wall)))
+
+    def words_draw(draw_keys):
+        def draw(rng, count):
+            new = rng.integers(0, 1 << 64, size=(count, 2, 2), dtype=np.uint64)
+            new[..., 1] >>= np.uint64(1)
+            idx = draw_keys(rng, count)
+            again = np.nonzero(rng.random(count) < 0.1)[0]          # about a tenth of the writes repeat an earlier key
+            again = again[again > 0]
+            idx[again] = idx[(rng.random(again.size) * again).astype(np.int64)]
+            return np.ascontiguousarray(idx), new
+        return draw
+
+    log_leaves = 20
+    t = D.RescueTree(leaves(log_leaves), device=0, lib=lib)
+
+    def dense_paths(idx):
+        out = np.zeros((idx.shape[0], log_leaves + 1, 2, 2), dtype=np.uint64)
+        assert t.lib.dst_rtree_paths(t._h, vp(idx), ctypes.c_size_t(idx.shape[0]), vp(out)) == 0
+        return out
+
+    time_refreshes("dense 2^%d leaves" % log_leaves, t, t.lib.dst_rtree_apply, dense_paths, log_leaves + 1, words_draw(lambda rng, count: rng.integers(0, 1 << log_leaves, size=count).astype(np.uint64)))
+    t.close()
+    rng0 = np.random.default_rng(REFRESH_SEED + 1)
+    keys = np.unique(rng0.integers(0, 1 << 63, size=(1 << 20) + (1 << 17), dtype=np.uint64))
+    rng0.shuffle(keys)
+    keys = keys[:1 << 20]
+    v = rng0.integers(0, 1 << 64, size=(keys.size, 2, 2), dtype=np.uint64)
+    v[..., 1] >>= np.uint64(1)
+    s = D.SparseRescueTree(63, device=0, lib=lib)
+    s.set(keys, v)
+
+    def sparse_keys(rng, count):                    # half stored keys, half new ones
+        idx = rng.integers(0, 1 << 63, size=count, dtype=np.uint64)
+        stored = np.nonzero(rng.random(count) < 0.5)[0]
+        idx[stored] = keys[rng.integers(0, keys.size, size=stored.size)]
+        return idx
+
+    time_refreshes("sparse depth 63, 2^20 keys", s, s.lib.dst_stree_apply, s.paths_words, 64, words_draw(sparse_keys))
+    s.close()
+    wk, wv = wide_keys(1 << 16, REFRESH_SEED + 2)
+    w = D.WideSparseRescueTree(127, device=0, lib=lib)
+    w.set(wk, wv)
+
+    def wide_draw(rng, count):
+        idx = rng.integers(0, 1 << 64, size=(count, 2), dtype=np.uint64)
+        idx[:, 1] >>= np.uint64(1)
+        stored = np.nonzero(rng.random(count) < 0.5)[0]
+        idx[stored] = wk[rng.integers(0, len(wk), size=stored.size)]
+        return idx
+
+    time_refreshes("wide depth 127, 2^16 keys", w, w.lib.dst_wtree_apply, w.paths_words, 128, words_draw(wide_draw), wide=True)
+    w.close()
     sys.exit(0)
 if args.sequence or args.verify:
     import ctypes
